@@ -7,14 +7,19 @@ A "step" = one pass of the hot path over one batch of synthetic input per GPU:
   * N > 1 : configs[3], "Batch 16384 G1 scalar-muls sharded across 8 MI355X" = 2048 instances = 16 proofs per GPU per
     step (N = 8 is literally configs[3]; N = 2, 4 keep the same per-GPU shard so the curve is weak scaling).
 Independent proofs shard across GPUs with no data-path collective; RCCL only all-gathers the Merkle caps of every proof.
-Every step proves DIFFERENT inputs (fresh 256-bit scalars and a fresh assignment of base points per step and rank).
-After the timed region every proof of the last step is verified with bn254s_verify and one of them is re-proven alone
-(bn254s_prove_g1) and compared word for word, so nothing is timed that was not checked.
+Every step proves DIFFERENT inputs (fresh 256-bit scalars and a fresh assignment of base points per step and rank); the
+inputs of step i are the same in every run with the same arguments.
+
+A plain run only sets up, warms up, times the K steps and prints the line (with `--dump-outputs DIR` it also writes what the
+last timed step computed, see dump_outputs).  `--full` adds everything else the line used to carry, after the clock stopped:
+every proof of the last step is verified with bn254s_verify and one of them is re-proven alone (bn254s_prove_g1) and compared
+word for word (`checked`), the same K steps one at a time (`sequential_steps`), the NTT / leaf-hash rooflines, one tall proof,
+the G2 / Fq-exp kinds and the CPU baseline (the last three can still be dropped with --no-extras / --no-cpu-baseline).
 
 `--workload map_to_g2` runs configs[4] instead ("fq_exp STARK + map_to_g2 pipeline, 4096 Fq2 inputs"): the 4096 inputs are
 sharded contiguously over the ranks (64 Fq-exp + 32 G2 proofs in total), caps gathered the same way.
 
-Launch: `python bench.py --gpus N --steps K --warmup W` (N = 1), or for N > 1
+Launch: `python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]` (N = 1), or for N > 1
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P
  bench.py --gpus N --steps K --warmup W`.  Rank 0 prints ONE JSON line.
 """
@@ -88,6 +93,43 @@ def gather_caps(local_caps: np.ndarray, dist, device):
     out = [torch.empty_like(t) for _ in range(dist.get_world_size())]
     dist.all_gather(out, t)
     return torch.stack(out).cpu().numpy().view(np.uint64)
+
+
+DUMP_BYTES = 63 * 10**6      # --dump-outputs: under 64 MB in all (over all ranks), the .npy headers included
+
+
+def u64_as_f64(a) -> np.ndarray:
+    """u64 words as exact float64: a trailing axis of 2 = (low 32 bits, high 32 bits)."""
+    a = np.asarray(a, dtype=np.uint64)
+    return np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).astype(np.float64)
+
+
+def proof_arrays(prefix: str, proofs, budget: int) -> dict:
+    """What a caller gets from a list of proofs, in at most `budget` bytes: `<prefix>_degree_bits`, `_outputs` [n, ...],
+    `_caps` [n, 192] and `_words` [m, len] of m proofs - all n when their words fit, else a fixed seeded sample;
+    `_words_index` holds the indices of the m proofs."""
+    n = len(proofs)
+    out = {f"{prefix}_degree_bits": np.array([p.degree_bits for p in proofs], np.float64),
+           f"{prefix}_outputs": u64_as_f64(np.stack([p.outputs for p in proofs])),
+           f"{prefix}_caps": u64_as_f64(caps_of(proofs))}
+    if n:
+        budget -= sum(a.nbytes for a in out.values()) + n * 8
+        m = min(n, max(1, budget // (proofs[0].words.size * 16)))
+        idx = np.arange(n) if m == n else np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+        out[f"{prefix}_words"] = u64_as_f64(np.stack([proofs[i].words for i in idx]))
+        out[f"{prefix}_words_index"] = idx.astype(np.float64)
+    return out
+
+
+def dump_outputs(path: str, arrays: dict, rank: int, world: int):
+    """Writes every array as <path>/<name>.npy (float32 / float64 only; ranks > 1 prefix their files with rank<r>_)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES // world:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BYTES // world} of one rank")
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), a)
 
 
 def host_cpu_share() -> int:
@@ -272,10 +314,39 @@ def run_g1(args, pk, torch, synth, ctx, rank, world, dist, device, gather_device
         t = torch.tensor([dt], device=gather_device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-
-    # ---- check what was timed (every rank, after the clock stopped): all proofs of the last step verify, the gathered
-    # caps are the proofs' caps, and one proof equals the single-proof entry point word for word
+    if args.dump_outputs:   # what the last timed step computed: the proofs of this rank's batch
+        dump_outputs(args.dump_outputs, proof_arrays("proof", proofs, DUMP_BYTES // world), rank, world)
     s, x, o = inputs[n_steps - 1]
+    total_proofs = world * ppg * args.steps
+    stage_ms = {k: v / max(n_acc, 1) for k, v in stage_acc.items()}
+    cfg = "configs[1]: batch of 1024 G1 scalar-muls on 1 GPU per step = 8 proofs x 128 instances" if world == 1 and ppg == 8 else \
+        (f"configs[3] shard: {per_rank} G1 scalar-muls = {ppg} proofs x 128 instances per GPU per step "
+         f"({world * per_rank} per step over {world} GPUs" + ("; N = 8 is the 16384 of configs[3])" if ppg == 16 else ")"))
+    out = {
+        "metric": "G1 scalar-mul STARK proofs/sec (256-bit scalars)",
+        "value": round(total_proofs / dt, 3),
+        "unit": "proofs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u64 (Goldilocks p = 2^64-2^32+1; BN254 Fq as 10x26-bit Montgomery limbs)",
+        "data": "synthetic (fresh random 256-bit scalars and point assignment every step)",
+        "config": {"workload": cfg + ", 2^16 rows, W=781, standard_fast_config",
+                   "proofs_per_step_per_gpu": ppg, "instances_per_proof": INSTANCES_PER_PROOF, "steps_in_flight": depth,
+                   "parallelism": "1 GPU, no collective" if world == 1 else
+                                  f"{world} ranks x independent proofs, one RCCL all-gather of the Merkle caps per step"},
+        "scalar_muls_per_s": round(total_proofs * INSTANCES_PER_PROOF / dt, 1),
+        "stage_ms_per_proof": {k: round(v, 3) for k, v in stage_ms.items()},
+    }
+    if not args.full:
+        return out if rank == 0 else None
+
+    # ---- --full: check what was timed (every rank, after the clock stopped): all proofs of the last step verify, the gathered
+    # caps are the proofs' caps, and one proof equals the single-proof entry point word for word
     checked = {"verified_proofs": 0, "caps_match": False, "batch_equals_single": False}
     for j, p in enumerate(proofs):
         lo = j * INSTANCES_PER_PROOF
@@ -297,7 +368,6 @@ def run_g1(args, pk, torch, synth, ctx, rank, world, dist, device, gather_device
     if rank != 0:
         return None
 
-    total_proofs = world * ppg * args.steps
     sequential = None
     if depth > 1 and world == 1:  # the same K steps again, one at a time (after the clock of the headline stopped)
         sync()
@@ -307,7 +377,6 @@ def run_g1(args, pk, torch, synth, ctx, rank, world, dist, device, gather_device
         ds = time.perf_counter() - ts
         sequential = {"value": round(total_proofs / ds, 3), "unit": "proofs/s", "ms_per_step": round(ds / args.steps * 1e3, 3),
                       "note": "--steps-in-flight 1: every batch is collected before the next one is queued"}
-    stage_ms = {k: v / max(n_acc, 1) for k, v in stage_acc.items()}
     # roofline of the NTT/LDE stage (north-star kernel): HIP-event time of the NTT launches of the two commitments of a
     # proof, measured on the proof's own stream inside the timed region.
     ntt_ms = stage_ms.get("trace_ntt", 0.0) + stage_ms.get("aux_ntt", 0.0)
@@ -383,30 +452,9 @@ def run_g1(args, pk, torch, synth, ctx, rank, world, dist, device, gather_device
                     "scalar_muls_per_s": round(1024 / tdt, 1), "verified": True}
         except Exception as e:
             tall = {"error": str(e)}
-    cfg = "configs[1]: batch of 1024 G1 scalar-muls on 1 GPU per step = 8 proofs x 128 instances" if world == 1 and ppg == 8 else \
-        (f"configs[3] shard: {per_rank} G1 scalar-muls = {ppg} proofs x 128 instances per GPU per step "
-         f"({world * per_rank} per step over {world} GPUs" + ("; N = 8 is the 16384 of configs[3])" if ppg == 16 else ")"))
-    out = {
-        "metric": "G1 scalar-mul STARK proofs/sec (256-bit scalars)",
-        "value": round(total_proofs / dt, 3),
-        "unit": "proofs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u64 (Goldilocks p = 2^64-2^32+1; BN254 Fq as 10x26-bit Montgomery limbs)",
-        "data": "synthetic (fresh random 256-bit scalars and point assignment every step)",
-        "config": {"workload": cfg + ", 2^16 rows, W=781, standard_fast_config",
-                   "proofs_per_step_per_gpu": ppg, "instances_per_proof": INSTANCES_PER_PROOF, "steps_in_flight": depth,
-                   "parallelism": "1 GPU, no collective" if world == 1 else
-                                  f"{world} ranks x independent proofs, one RCCL all-gather of the Merkle caps per step"},
+    out.update({
         "checked": checked,
         "sequential_steps": sequential,
-        "scalar_muls_per_s": round(total_proofs * INSTANCES_PER_PROOF / dt, 1),
-        "stage_ms_per_proof": {k: round(v, 3) for k, v in stage_ms.items()},
         "one_tall_proof_of_1024": tall,
         "roofline": {"bound": "hbm", "kernel": "ntt_lde stage = iNTT + both coset NTTs (k_ntt_* launches) over the 781 trace "
                                                "+ 456 aux columns of one proof",
@@ -420,7 +468,7 @@ def run_g1(args, pk, torch, synth, ctx, rank, world, dist, device, gather_device
                                    "note": "same launches with no other stream on the GPU (bn254s_bench_ntt)"},
                      "valu_floor": valu_floor},
         "roofline_alu": alu,
-    }
+    })
     if world == 1 and not args.no_extras:
         out["other_kinds"] = other_kinds(ctx, synth)
     if world == 1 and not args.no_cpu_baseline:
@@ -480,16 +528,23 @@ def run_map_to_g2(args, pk, torch, synth, ctx, rank, world, dist, device, gather
         t = torch.tensor([dt], device=gather_device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # check the last step: every proof verifies against the job arrays the library returned
     uu, oo, pts, fq_jobs, g2_jobs, pf, pg = last
-    fs, fx = np.ascontiguousarray(fq_jobs[:, :4]), np.ascontiguousarray(fq_jobs[:, 4:])
-    gs, gx = np.ascontiguousarray(g2_jobs[:, :4]), np.ascontiguousarray(g2_jobs[:, 4:])
-    for i, p in enumerate(pf):
-        a = 128 * i
-        ctx.verify(2, p.words, p.degree_bits, fs[a:a + 128], fx[a:a + 128], None, p.outputs)
-    for i, p in enumerate(pg):
-        a = 128 * i
-        ctx.verify(1, p.words, p.degree_bits, gs[a:a + 128], gx[a:a + 128], oo[a:a + 128], p.outputs)
+    if args.dump_outputs:   # what the last timed step computed: everything bn254s_map_to_g2 returned to this rank
+        arrays = {"points": u64_as_f64(pts), "fq_jobs": u64_as_f64(fq_jobs), "g2_jobs": u64_as_f64(g2_jobs)}
+        budget = (DUMP_BYTES // world - sum(a.nbytes for a in arrays.values())) // 2
+        arrays.update(proof_arrays("fq_proof", pf, budget))
+        arrays.update(proof_arrays("g2_proof", pg, budget))
+        dump_outputs(args.dump_outputs, arrays, rank, world)
+    if args.full:
+        # check the last step: every proof verifies against the job arrays the library returned
+        fs, fx = np.ascontiguousarray(fq_jobs[:, :4]), np.ascontiguousarray(fq_jobs[:, 4:])
+        gs, gx = np.ascontiguousarray(g2_jobs[:, :4]), np.ascontiguousarray(g2_jobs[:, 4:])
+        for i, p in enumerate(pf):
+            a = 128 * i
+            ctx.verify(2, p.words, p.degree_bits, fs[a:a + 128], fx[a:a + 128], None, p.outputs)
+        for i, p in enumerate(pg):
+            a = 128 * i
+            ctx.verify(1, p.words, p.degree_bits, gs[a:a + 128], gx[a:a + 128], oo[a:a + 128], p.outputs)
     if rank != 0:
         return None
     n_fq, n_g2 = 0, 0
@@ -497,7 +552,7 @@ def run_map_to_g2(args, pk, torch, synth, ctx, rank, world, dist, device, gather
         a, b = split_range(r, world, total)
         f, g = map_to_g2_proof_counts(b - a)
         n_fq, n_g2 = n_fq + f, n_g2 + g
-    return {
+    out = {
         "metric": "map_to_g2 inputs/sec (fq_exp STARK + G2 scalar-mul STARK pipeline)",
         "value": round(total * args.steps / dt, 2),
         "unit": "inputs/s",
@@ -511,8 +566,10 @@ def run_map_to_g2(args, pk, torch, synth, ctx, rank, world, dist, device, gather
                    "parallelism": "1 GPU, no collective" if world == 1 else
                                   f"{world} ranks, one RCCL all-gather of the Merkle caps per step"},
         "proofs_per_s": round((n_fq + n_g2) * args.steps / dt, 2),
-        "checked": {"verified_proofs_rank0_last_step": len(pf) + len(pg)},
     }
+    if args.full:
+        out["checked"] = {"verified_proofs_rank0_last_step": len(pf) + len(pg)}
+    return out
 
 
 def main():
@@ -527,9 +584,17 @@ def main():
     ap.add_argument("--steps-in-flight", type=int, default=0,
                     help="batches open at a time (k: step i + k is queued before step i is collected; 1: sequential; default: as "
                          "many as keep 32 proofs queued = the library's slots: 4 steps of 8 proofs on one GPU, 2 steps of 16 on several)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the G2 / Fq-exp / tall-proof figures reported beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also check the last step's proofs and measure the figures reported beside the "
+                         "headline (sequential steps, rooflines, tall proof, other kinds, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; a u64 word is (low, high) 32 bits)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the G2 / Fq-exp / tall-proof figures reported beside the headline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import plonky2_bn254_amd as pk   # first: sets GPU_MAX_HW_QUEUES before the HIP runtime initialises
     import torch

@@ -93,3 +93,36 @@ def test_step_inputs_change_every_step_and_rank():
         assert s.shape == (8, 4) and s.dtype == np.uint64 and s.flags["C_CONTIGUOUS"]
         assert sorted(map(tuple, x)) == sorted(map(tuple, xs)) and sorted(map(tuple, o)) == sorted(map(tuple, offs))
     assert (a[0] >> np.uint64(63)).any()                                # scalars use all 256 bits
+
+
+def test_dump_outputs_are_exact_float_and_bounded(tmp_path):
+    """--dump-outputs: u64 words survive the float64 (low, high) split bit for bit; proofs whose words exceed the budget are
+    replaced by a fixed seeded sample; only float arrays are written."""
+    import bench
+
+    class FakeProof:
+        degree_bits = 16
+
+        def __init__(self, i):
+            r = np.random.default_rng(i)
+            self.words = r.integers(0, 1 << 64, size=5000, dtype=np.uint64)
+            self.outputs = r.integers(0, 1 << 64, size=1024, dtype=np.uint64)
+
+        def caps(self):
+            return self.words[:192]
+
+    proofs = [FakeProof(i) for i in range(8)]
+    full = bench.proof_arrays("proof", proofs, bench.DUMP_BYTES)
+    w = full["proof_words"]
+    assert w.dtype == np.float64 and w.shape == (8, 5000, 2)
+    assert np.array_equal(w[..., 0].astype(np.uint64) | (w[..., 1].astype(np.uint64) << np.uint64(32)),
+                          np.stack([p.words for p in proofs]))
+    budget = 300000
+    part = bench.proof_arrays("proof", proofs, budget)
+    assert sum(a.nbytes for a in part.values()) <= budget
+    idx = part["proof_words_index"].astype(int)
+    assert 0 < len(idx) < 8 and np.array_equal(idx, bench.proof_arrays("proof", proofs, budget)["proof_words_index"])
+    assert np.array_equal(part["proof_words"], full["proof_words"][idx])
+    bench.dump_outputs(str(tmp_path), part, 0, 1)
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in part)
+    assert all(np.load(os.path.join(tmp_path, k + ".npy")).dtype == np.float64 for k in part)

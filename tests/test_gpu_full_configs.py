@@ -143,7 +143,8 @@ def _run_bench_2_ranks(extra, port, timeout):
 
 def test_bench_two_ranks_g1_child_process(gpu_ctx):
     gpu_ctx.trim()        # the two child processes need the device memory this process's idle workspaces hold
-    out = _run_bench_2_ranks(["--steps", "2", "--warmup", "1", "--steps-in-flight", "1", "--no-extras", "--no-cpu-baseline"], 29711, 900)
+    out = _run_bench_2_ranks(["--steps", "2", "--warmup", "1", "--steps-in-flight", "1", "--full", "--no-extras", "--no-cpu-baseline"],
+                             29711, 900)
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["warmup"] == 1 and out["scaling"] == "weak"
     assert out["unit"] == "proofs/s" and out["value"] > 0 and out["higher_is_better"] is True
     assert out["config"]["proofs_per_step_per_gpu"] == 16 and "configs[3] shard: 2048 G1 scalar-muls" in out["config"]["workload"]
@@ -154,7 +155,7 @@ def test_bench_two_ranks_g1_child_process(gpu_ctx):
 
 def test_bench_two_ranks_map_to_g2_child_process(gpu_ctx):
     gpu_ctx.trim()
-    out = _run_bench_2_ranks(["--steps", "1", "--warmup", "1", "--workload", "map_to_g2"], 29713, 900)
+    out = _run_bench_2_ranks(["--steps", "1", "--warmup", "1", "--workload", "map_to_g2", "--full"], 29713, 900)
     assert out["n_gpus"] == 2 and out["unit"] == "inputs/s" and out["value"] > 0 and out["scaling"] == "strong"
     assert "configs[4]" in out["config"]["workload"] and "4096 Fq2 inputs = 64 Fq-exp proofs + 32 G2 proofs" in out["config"]["workload"]
     assert out["checked"]["verified_proofs_rank0_last_step"] == 32 + 16
@@ -168,9 +169,37 @@ def test_bench_cap_gather_over_rccl_one_rank(gpu_ctx):
     env = dict(os.environ, BENCH_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT="29717", HSA_ENABLE_IPC_MODE_LEGACY="0", BN254S_SLOTS="16")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--steps-in-flight", "2",
-           "--no-extras", "--no-cpu-baseline"]
+           "--full", "--no-extras", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["checked"] == {"verified_proofs": 8, "caps_match": True, "batch_equals_single": True}
     assert out["value"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_step(gpu_ctx, tmp_path):
+    """A plain bench run (no --full) prints the headline without the post-run figures, and --dump-outputs writes the proofs of
+    its last timed step: decoded back to u64 words they verify against the inputs bench.py draws for that step."""
+    gpu_ctx.trim()
+    env = dict(os.environ, BN254S_SLOTS="16")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--steps-in-flight", "2",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 2 and out["unit"] == "proofs/s" and out["higher_is_better"] is True
+    assert abs(out["value"] - 8 * 2 / (out["ms_per_step"] * 2e-3)) < 0.05 * out["value"]
+    assert not {"checked", "sequential_steps", "roofline", "roofline_alu", "other_kinds", "cpu_baseline"} & set(out)
+
+    def u64(name):
+        a = np.load(os.path.join(tmp_path, name + ".npy"))
+        assert a.dtype == np.float64 and a.shape[-1] == 2
+        return a[..., 0].astype(np.uint64) | (a[..., 1].astype(np.uint64) << np.uint64(32))
+    words, outputs, caps = u64("proof_words"), u64("proof_outputs"), u64("proof_caps")
+    assert words.shape[0] == outputs.shape[0] == caps.shape[0] == 8
+    assert np.array_equal(np.load(os.path.join(tmp_path, "proof_words_index.npy")), np.arange(8))
+    _, xs, offs = synth.g1_inputs(1024, seed=bench.SEED0 + 1)
+    s, x, o = bench.step_inputs((xs, offs), 2, 0)        # warm-up step 0, timed steps 1 and 2
+    for j in range(8):
+        sl = slice(128 * j, 128 * j + 128)
+        gpu_ctx.verify(0, np.ascontiguousarray(words[j]), 16, s[sl], x[sl], o[sl], np.ascontiguousarray(outputs[j]))

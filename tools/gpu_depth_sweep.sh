@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 run() {
   d=$1; shift
   echo -n "depth $d $* : "
-  env "$@" python bench.py --steps 12 --warmup 2 --no-extras --no-cpu-baseline --steps-in-flight $d 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'ntt_ms', d['roofline']['ms'])"
+  env "$@" python bench.py --full --steps 12 --warmup 2 --no-extras --no-cpu-baseline --steps-in-flight $d 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'ntt_ms', d['roofline']['ms'])"
 }
 for rep in 1 2; do
 run 1 BN254S_SLOTS=8

@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 run() {
   d=$1; shift
   echo -n "depth $d $* : "
-  env "$@" python bench.py --steps 24 --warmup 4 --no-extras --no-cpu-baseline --steps-in-flight $d 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'ntt_ms', d['roofline']['ms'], 'excl', d['roofline']['exclusive']['ms'], d['roofline'].get('valu_floor'))"
+  env "$@" python bench.py --full --steps 24 --warmup 4 --no-extras --no-cpu-baseline --steps-in-flight $d 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'ntt_ms', d['roofline']['ms'], 'excl', d['roofline']['exclusive']['ms'], d['roofline'].get('valu_floor'))"
 }
 run 3 BN254S_SLOTS=24
 run 4 BN254S_SLOTS=32

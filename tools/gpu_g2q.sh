@@ -6,5 +6,4 @@ mkdir -p gpurun_out
 make -C oracle > /dev/null
 timeout -k 10 900 python -m pytest tests -m gpu -x -q -k "g2 or fq or verify or stream or config" --durations=5 > gpurun_out/pytest_g2q.log 2>&1 || { tail -40 gpurun_out/pytest_g2q.log; exit 1; }
 tail -8 gpurun_out/pytest_g2q.log
-python bench.py --steps 10 --warmup 2 --no-cpu-baseline > gpurun_out/bench_g2q.json 2> gpurun_out/bench_g2q.err || { tail -20 gpurun_out/bench_g2q.err; exit 1; }
-python -c "import json; d=json.loads(open('gpurun_out/bench_g2q.json').read().strip().splitlines()[-1]); print(d['value'], json.dumps(d['other_kinds']))"
+(set -o pipefail; python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], json.dumps(d['other_kinds']))")

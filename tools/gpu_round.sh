@@ -7,6 +7,5 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q -k "$1" > gpurun_out/pytes
 tail -3 gpurun_out/pytest_sel.log
 python bench.py --steps 24 --warmup 4 > gpurun_out/bench_a.json 2> gpurun_out/bench_a.err || { tail -20 gpurun_out/bench_a.err; exit 1; }
 cat gpurun_out/bench_a.json
-python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_b.err || { tail -20 gpurun_out/bench_b.err; exit 1; }
-python -c "import json; d=json.load(open('gpurun_out/bench_default.json')); print('default run:', d['value'], d['ms_per_step'], d['config']['steps_in_flight'], d['sequential_steps'])"
+(set -o pipefail; python bench.py --full | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('default run:', d['value'], d['ms_per_step'], d['config']['steps_in_flight'], d['sequential_steps'])") || exit 1
 python tools/stage_times.py > gpurun_out/stage_times.txt 2>&1; cat gpurun_out/stage_times.txt

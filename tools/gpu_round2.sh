@@ -9,7 +9,7 @@ python tools/stage_times.py > gpurun_out/stage_times.txt 2>&1; cat gpurun_out/st
 python tools/oracle_threads.py 16 32 64 128 > gpurun_out/oracle_threads.txt 2>&1; cat gpurun_out/oracle_threads.txt
 run() {
   echo -n "$* : "
-  env "$@" python bench.py --steps 24 --warmup 4 --no-extras --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'ntt_ms', d['roofline']['ms'])"
+  env "$@" python bench.py --full --steps 24 --warmup 4 --no-extras --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], 'ntt_ms', d['roofline']['ms'])"
 }
 run A=1
 run BN254S_BIG_COST_HASH=4
