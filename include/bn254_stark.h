@@ -32,7 +32,7 @@
  * Threading: one call at a time per context (one host thread enters the context at a time); any number of contexts (one per
  * GPU / per host thread).  A batch opened with bn254s_prove_batch_begin stays in flight after _begin returns: until its _end
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
- * _batch* / bn254s_map_to_g2) queues behind the open batches on the same worker pool and runs on a free slot (stream +
+ * _batch* / bn254s_map_to_g2 / bn254s_g1_msm) queues behind the open batches on the same worker pool and runs on a free slot (stream +
  * workspace) of its own, so it can never share device state with a proof of the open batch; bn254s_verify, _commit_values,
  * _generate_trace and the _bench_* calls use the context's own stream and buffers and are independent of open batches.
  */
@@ -217,6 +217,23 @@ int bn254s_hash_to_fq2(const uint64_t* input, size_t len, uint64_t* out /* 8 */)
 /* n inputs of `len` elements each at once, on the device (inputs[n][len] -> out[n][8]); same values as n calls of the above. */
 int bn254s_hash_to_fq2_batch(bn254s_ctx* ctx, const uint64_t* inputs, size_t n, size_t len, uint64_t* out);
 
+/* g1_msm (src/utils/g1_msm.rs:22-36): the reference folds offset_0 = R (a random non-infinity point, set_random_g1),
+ * offset_{i+1} = s_i x_i + offset_i with one G1 scalar-mul job per link, proves the n jobs (s_i, x_i, offset_i) in one G1
+ * STARK (hook.rs:63-71) and returns msm = offset_n - R (G1Target::add: never infinity, a doubling is allowed).
+ * bn254s_g1_msm_chain computes the witness chain on the device as a parallel prefix sum (products s_i x_i, a scan of the points,
+ * one batched inversion; csrc/g1_msm.hip): offsets_out[0..n] = R, R + s_0 x_0, ..., R + sum s_j x_j ((n + 1) x 8 words) and
+ * result = offsets_out[n] - R (8 words).  Device front-end only, no proof.  BN254S_E_INVALID_POINT if some offset_i (i >= 1) is
+ * the point at infinity (bn254s_last_error names the first such i) or if offset_n == R (the result would be infinity). */
+int bn254s_g1_msm_chain(bn254s_ctx* ctx, const uint64_t* scalars /* n x 4 */, const uint64_t* x /* n x 8 */,
+                        const uint64_t* offset /* R, 8 words */, size_t n, uint64_t* offsets_out, uint64_t* result /* 8 */);
+/* The chain plus the proofs of its n jobs (s_i, x_i, offset_i), cut into ceil(n / per_proof) G1 proofs exactly as
+ * bn254s_prove_batch cuts them (per_proof = n <= 16384: one proof, the hook's shape).  offsets_out may be NULL.  The outputs of
+ * the proofs (computed by the trace generator on its own) are checked word for word against offsets_out[1..n]: a mismatch is
+ * BN254S_E_INTERNAL.  On any error every proof of the call is freed and its slot in proofs is NULL.  per_proof > 16384:
+ * BN254S_E_UNSUPPORTED before any device work. */
+int bn254s_g1_msm(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
+                  const uint64_t* offset, size_t n, size_t per_proof, uint64_t* result, uint64_t* offsets_out,
+                  bn254s_proof** proofs);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

@@ -513,6 +513,10 @@ int g1_generate_trace_device(const u64* d_scalars, const u64* d_x, const u64* d_
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+void launch_g1_dbl_chain(const u64* d_x, int n, u64* px, u64* py, u64* pz, hipStream_t st) {
+  k_g1_dbl_chain_coop<<<(unsigned)((n + 15) / 16), 64, 0, st>>>(d_x, n, px, py, pz);
+}
+
 // loads this translation unit's code object (the HIP runtime defers that to the first launch otherwise)
 void trace_g1_module_warm() {
   hipFuncAttributes a;

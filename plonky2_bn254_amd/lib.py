@@ -75,6 +75,8 @@ def load_library():
                                        C.c_size_t]
     lib.bn254s_map_to_g2.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     lib.bn254s_hash_to_fq2.argtypes = [vp, C.c_size_t, vp]
+    lib.bn254s_g1_msm_chain.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
+    lib.bn254s_g1_msm.argtypes = [vp, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(vp)]
     lib.bn254s_hash_to_fq2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bn254s_ctl_values.argtypes = [C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_commit_values.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
@@ -291,6 +293,31 @@ class Context:
         return (pts, fq_jobs, g2_jobs, [Proof(self._lib, C.c_void_p(pf[i])) for i in range(n_fq)],
                 [Proof(self._lib, C.c_void_p(pg[i])) for i in range(n_g2)])
 
+    def g1_msm_chain(self, scalars, x, offset):
+        """scalars [n,4], x [n,8], offset = R [8] -> (offsets [n+1,8], result [8]): the witness chain of g1_msm
+        (offsets[i] = R + sum_{j<i} s_j x_j, result = offsets[n] - R) on the device, no proof (bn254s_g1_msm_chain)."""
+        scalars, x, offset = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, offset))
+        n = scalars.shape[0]
+        offs = np.zeros((n + 1, 8), np.uint64)
+        res = np.zeros(8, np.uint64)
+        self._check(self._lib.bn254s_g1_msm_chain(self._h, _ptr(scalars), _ptr(x), _ptr(offset), n, _ptr(offs), _ptr(res)),
+                    "bn254s_g1_msm_chain")
+        return offs, res
+
+    def g1_msm(self, scalars, x, offset, per_proof=128, params: Optional[Params] = None):
+        """-> (result [8], offsets [n+1,8], proofs): the chain plus the G1 proofs of its n jobs (s_i, x_i, offsets[i]), cut into
+        ceil(n / per_proof) proofs like prove_batch (bn254s_g1_msm).  Check it with verify_g1_msm."""
+        params = params or default_params()
+        scalars, x, offset = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, offset))
+        n = scalars.shape[0]
+        k = (n + per_proof - 1) // per_proof
+        offs = np.zeros((n + 1, 8), np.uint64)
+        res = np.zeros(8, np.uint64)
+        outs = (C.c_void_p * k)()
+        self._check(self._lib.bn254s_g1_msm(self._h, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof, _ptr(res),
+                                            _ptr(offs), outs), "bn254s_g1_msm")
+        return res, offs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+
     def hash_to_fq2_batch(self, inputs: np.ndarray) -> np.ndarray:
         """inputs [n, len] Goldilocks elements -> u [n, 8]: hash_to_fq2 (hash_to_g2.rs:76-87) of every row, on the device."""
         inputs = np.ascontiguousarray(inputs, dtype=np.uint64)
@@ -403,6 +430,53 @@ def verify_host(kind, words, degree_bits, scalars, x, offset, outputs, params: O
         raise VerifyError(buf.value.decode())
     if rc != 0:
         raise RuntimeError(f"bn254s_verify_host failed with {rc}: {buf.value.decode()}")
+
+
+def verify_g1_msm(scalars, x, R, result, offsets, proofs, per_proof, ctx: Optional[Context] = None, params: Optional[Params] = None):
+    """Checks a g1_msm: the linkage (offsets[0] == R, the outputs of proof i are offsets[lo + 1 .. hi] for its jobs lo .. hi - 1,
+    result == offsets[n] - R in Python integer arithmetic, tools/synth.py) and every proof (Context.verify with a context, else
+    verify_host) against its jobs (s_i, x_i, offsets[i]).  `proofs`: objects with `words`, `degree_bits` and `outputs`, such as
+    Proof.  Returns None or raises VerifyError naming the first broken link or the rejected proof."""
+    from tools import synth
+    scalars, x, R, result, offsets = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, R, result, offsets))
+    n = scalars.shape[0]
+    offsets = offsets.reshape(-1, 8)
+    if x.shape != (n, 8) or offsets.shape != (n + 1, 8) or R.size != 8 or result.size != 8:
+        raise VerifyError(f"g1_msm: shapes: scalars {scalars.shape}, x {x.shape}, offsets {offsets.shape}, R {R.shape}, result {result.shape}")
+    if len(proofs) != (n + per_proof - 1) // per_proof:
+        raise VerifyError(f"g1_msm: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    if not np.array_equal(offsets[0], R.reshape(8)):
+        raise VerifyError("g1_msm: offsets[0] != R")
+    for i, pr in enumerate(proofs):
+        lo, hi = i * per_proof, min(n, (i + 1) * per_proof)
+        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 8)
+        if outs.shape[0] != hi - lo:
+            raise VerifyError(f"g1_msm: proof {i} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+        bad = np.nonzero(np.any(outs != offsets[lo + 1:hi + 1], axis=1))[0]
+        if bad.size:
+            j = lo + int(bad[0])
+            raise VerifyError(f"g1_msm: output {j} of proof {i} != offsets[{j + 1}] (link s_{j} x_{j} + offset_{j})")
+
+    def pt(w):
+        return (synth.words_to_int(w[:4]), synth.words_to_int(w[4:]))
+
+    o, r = pt(offsets[n]), pt(R.reshape(8))
+    try:
+        want = synth.g1_add(o, (r[0], (-r[1]) % synth.P))
+    except ValueError:
+        raise VerifyError("g1_msm: offsets[n] == R, the result would be the point at infinity") from None
+    if pt(result.reshape(8)) != want:
+        raise VerifyError("g1_msm: result != offsets[n] - R")
+    for i, pr in enumerate(proofs):
+        lo, hi = i * per_proof, min(n, (i + 1) * per_proof)
+        s_, x_, o_ = (np.ascontiguousarray(a[lo:hi]) for a in (scalars, x, offsets))
+        try:
+            if ctx is not None:
+                ctx.verify(0, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+            else:
+                verify_host(0, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+        except VerifyError as e:
+            raise VerifyError(f"g1_msm: proof {i} (jobs {lo}..{hi - 1}) rejected: {e}") from None
 
 
 class BatchInFlight:

@@ -99,5 +99,11 @@ extern "C" {
     pub fn bn254s_map_to_g2(ctx: *mut Bn254sCtx, params: *const Bn254sParams, u: *const u64, offsets: *const u64, n: usize,
                             out_points: *mut u64, fq_jobs: *mut u64, g2_jobs: *mut u64, fq_proofs: *mut *mut Bn254sProof,
                             g2_proofs: *mut *mut Bn254sProof) -> c_int;
+    /// g1_msm (src/utils/g1_msm.rs:22-36): offsets_out[0..=n] = R, R + s_0 x_0, ..., ((n + 1) x 8 words), result = offsets_out[n] - R
+    pub fn bn254s_g1_msm_chain(ctx: *mut Bn254sCtx, scalars: *const u64, x: *const u64, offset: *const u64, n: usize,
+                               offsets_out: *mut u64, result: *mut u64) -> c_int;
+    /// the chain plus ceil(n / per_proof) G1 proofs of its jobs (s_i, x_i, offset_i); offsets_out may be null
+    pub fn bn254s_g1_msm(ctx: *mut Bn254sCtx, params: *const Bn254sParams, scalars: *const u64, x: *const u64, offset: *const u64,
+                         n: usize, per_proof: usize, result: *mut u64, offsets_out: *mut u64, proofs: *mut *mut Bn254sProof) -> c_int;
     pub fn bn254s_hash_to_fq2(input: *const u64, len: usize, out: *mut u64) -> c_int;
 }

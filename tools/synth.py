@@ -155,6 +155,38 @@ def words_to_int(w) -> int:
     return sum(int(v) << (64 * i) for i, v in enumerate(w))
 
 
+# ---- g1_msm (reference src/utils/g1_msm.rs:22-36) ----------------------------------------------------------------------
+def g1_msm_chain(scalars, xs, R):
+    """The reference's sequential fold offset_0 = R, offset_{i+1} = s_i x_i + offset_i, msm = offset_n - R, with a Jacobian
+    accumulator so that infinite partial sums pass through.  scalars [n,4] / xs [n,8] / R [8] in ABI words (or int pairs for the
+    points).  Returns (offsets: n + 1 affine (x, y) int pairs, None for infinity; msm: affine pair, None for infinity)."""
+    def pt(p):
+        return (words_to_int(p[:4]), words_to_int(p[4:])) if len(p) == 8 else (int(p[0]), int(p[1]))
+
+    def affine(j):
+        x, y, z = j
+        if z == 0:
+            return None
+        zi = pow(z, -1, P)
+        return (x * zi * zi % P, y * zi * zi * zi % P)
+
+    r = pt(R)
+    acc = (r[0], r[1], 1)
+    offsets = [r]
+    for s, x in zip(scalars, xs):
+        k = (words_to_int(s) if not isinstance(s, int) else s) % R_ORDER
+        if k:
+            acc = _jac_add_affine(acc, g1_mul(k, pt(x)))
+        offsets.append(affine(acc))
+    msm = affine(_jac_add_affine(acc, (r[0], (-r[1]) % P)))
+    return offsets, msm
+
+
+def g1_points_to_words(pts):
+    """Affine int pairs -> uint64 [len, 8] ABI words."""
+    return np.array([_to_words(p[0]) + _to_words(p[1]) for p in pts], dtype=np.uint64).reshape(-1, 8)
+
+
 # ---- Fq2 = Fq[u]/(u^2+1) and G2 (y^2 = x^3 + b2) over Python ints ---------------------------------------
 G2_B = (19485874751759354771024239261021720505790618469301721065564631296452457478373,
         266929791119991161246907387137283842545076965332900288569378510910307636690)   # src/curves/g2.rs:29-36
