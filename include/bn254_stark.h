@@ -32,9 +32,10 @@
  * Threading: one call at a time per context (one host thread enters the context at a time); any number of contexts (one per
  * GPU / per host thread).  A batch opened with bn254s_prove_batch_begin stays in flight after _begin returns: until its _end
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
- * _batch* / bn254s_map_to_g2 / bn254s_g1_msm) queues behind the open batches on the same worker pool and runs on a free slot (stream +
- * workspace) of its own, so it can never share device state with a proof of the open batch; bn254s_verify, _commit_values,
- * _generate_trace and the _bench_* calls use the context's own stream and buffers and are independent of open batches.
+ * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm) queues behind the open batches on the same worker pool and runs
+ * on a free slot (stream + workspace) of its own, so it can never share device state with a proof of the open batch;
+ * bn254s_verify, _commit_values, _generate_trace and the _bench_* calls use the context's own stream and buffers and are
+ * independent of open batches.
  */
 #ifndef BN254_STARK_H
 #define BN254_STARK_H
@@ -232,6 +233,21 @@ int bn254s_g1_msm_chain(bn254s_ctx* ctx, const uint64_t* scalars /* n x 4 */, co
  * BN254S_E_INTERNAL.  On any error every proof of the call is freed and its slot in proofs is NULL.  per_proof > 16384:
  * BN254S_E_UNSUPPORTED before any device work. */
 int bn254s_g1_msm(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
+                  const uint64_t* offset, size_t n, size_t per_proof, uint64_t* result, uint64_t* offsets_out,
+                  bn254s_proof** proofs);
+/* g2_msm: the G2 twin of g1_msm.  The reference has no g2_msm; this is the circuit of g1_msm.rs:22-36 written with its G2 gadgets
+ * (set_random_g2 for R, g2_scalar_mul per link, G2Target::neg / add, curves/g2.rs:93-150): offset_0 = R (non-infinity),
+ * offset_{i+1} = s_i x_i + offset_i, msm = offset_n - R.  Points are 16 words (x.c0, x.c1, y.c0, y.c1).  Scalars are used as
+ * the full 256-bit values, as the G2 trace computes them: for x_i outside the r-torsion subgroup s x_i != (s mod r) x_i.
+ * bn254s_g2_msm_chain (csrc/g2_msm.hip): offsets_out[0..n] ((n + 1) x 16 words) and result = offsets_out[n] - R (16 words) on the
+ * device, no proof.  BN254S_E_INVALID_POINT if some offset_i (i >= 1) is the point at infinity (bn254s_last_error names the
+ * first such i) or if offset_n == R; offset_n == -R doubles. */
+int bn254s_g2_msm_chain(bn254s_ctx* ctx, const uint64_t* scalars /* n x 4 */, const uint64_t* x /* n x 16 */,
+                        const uint64_t* offset /* R, 16 words */, size_t n, uint64_t* offsets_out /* (n + 1) x 16 */,
+                        uint64_t* result /* 16 */);
+/* The chain plus the G2 proofs of its n jobs (bn254s_prove_batch, kind 1), with the same arguments, checks, linkage check and
+ * error handling as bn254s_g1_msm.  per_proof > 16384 (the 2^23-row proof): BN254S_E_UNSUPPORTED before any device work. */
+int bn254s_g2_msm(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
                   const uint64_t* offset, size_t n, size_t per_proof, uint64_t* result, uint64_t* offsets_out,
                   bn254s_proof** proofs);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */

@@ -484,6 +484,12 @@ int g2_generate_trace_device(const u64* d_scalars, const u64* d_x, const u64* d_
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+void launch_g2_dbl_chain(const u64* d_x, int n, u64* pts, u64* znorm, hipStream_t st) {
+  const size_t v = 4 * (size_t)NPTS * n;
+  Soa2 px{pts, pts + v}, py{pts + 2 * v, pts + 3 * v}, pz{pts + 4 * v, pts + 5 * v};
+  k_g2_dbl_chain_coop<<<(unsigned)((n + 7) / 8), 64, 0, st>>>(d_x, n, px, py, pz, znorm);
+}
+
 // ======================================== Fq exp ==============================================================
 // table per instance: 0 = one, 1+k = C_k = P_{k-1} * x^(2^k), 257+k = x^(2^k)
 __global__ __launch_bounds__(64) void k_fq_chain(const u64* __restrict__ scalars, const u64* __restrict__ xs, int n,

@@ -77,6 +77,8 @@ def load_library():
     lib.bn254s_hash_to_fq2.argtypes = [vp, C.c_size_t, vp]
     lib.bn254s_g1_msm_chain.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_g1_msm.argtypes = [vp, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(vp)]
+    lib.bn254s_g2_msm_chain.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
+    lib.bn254s_g2_msm.argtypes = [vp, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(vp)]
     lib.bn254s_hash_to_fq2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bn254s_ctl_values.argtypes = [C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_commit_values.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
@@ -293,30 +295,46 @@ class Context:
         return (pts, fq_jobs, g2_jobs, [Proof(self._lib, C.c_void_p(pf[i])) for i in range(n_fq)],
                 [Proof(self._lib, C.c_void_p(pg[i])) for i in range(n_g2)])
 
-    def g1_msm_chain(self, scalars, x, offset):
-        """scalars [n,4], x [n,8], offset = R [8] -> (offsets [n+1,8], result [8]): the witness chain of g1_msm
-        (offsets[i] = R + sum_{j<i} s_j x_j, result = offsets[n] - R) on the device, no proof (bn254s_g1_msm_chain)."""
+    def _msm_chain(self, fn, w, scalars, x, offset):
         scalars, x, offset = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, offset))
         n = scalars.shape[0]
-        offs = np.zeros((n + 1, 8), np.uint64)
-        res = np.zeros(8, np.uint64)
-        self._check(self._lib.bn254s_g1_msm_chain(self._h, _ptr(scalars), _ptr(x), _ptr(offset), n, _ptr(offs), _ptr(res)),
-                    "bn254s_g1_msm_chain")
+        offs = np.zeros((n + 1, w), np.uint64)
+        res = np.zeros(w, np.uint64)
+        self._check(getattr(self._lib, fn)(self._h, _ptr(scalars), _ptr(x), _ptr(offset), n, _ptr(offs), _ptr(res)), fn)
         return offs, res
 
-    def g1_msm(self, scalars, x, offset, per_proof=128, params: Optional[Params] = None):
-        """-> (result [8], offsets [n+1,8], proofs): the chain plus the G1 proofs of its n jobs (s_i, x_i, offsets[i]), cut into
-        ceil(n / per_proof) proofs like prove_batch (bn254s_g1_msm).  Check it with verify_g1_msm."""
+    def _msm(self, fn, w, scalars, x, offset, per_proof, params):
         params = params or default_params()
         scalars, x, offset = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, offset))
         n = scalars.shape[0]
         k = (n + per_proof - 1) // per_proof
-        offs = np.zeros((n + 1, 8), np.uint64)
-        res = np.zeros(8, np.uint64)
+        offs = np.zeros((n + 1, w), np.uint64)
+        res = np.zeros(w, np.uint64)
         outs = (C.c_void_p * k)()
-        self._check(self._lib.bn254s_g1_msm(self._h, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof, _ptr(res),
-                                            _ptr(offs), outs), "bn254s_g1_msm")
+        self._check(getattr(self._lib, fn)(self._h, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof, _ptr(res),
+                                           _ptr(offs), outs), fn)
         return res, offs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+
+    def g1_msm_chain(self, scalars, x, offset):
+        """scalars [n,4], x [n,8], offset = R [8] -> (offsets [n+1,8], result [8]): the witness chain of g1_msm
+        (offsets[i] = R + sum_{j<i} s_j x_j, result = offsets[n] - R) on the device, no proof (bn254s_g1_msm_chain)."""
+        return self._msm_chain("bn254s_g1_msm_chain", 8, scalars, x, offset)
+
+    def g1_msm(self, scalars, x, offset, per_proof=128, params: Optional[Params] = None):
+        """-> (result [8], offsets [n+1,8], proofs): the chain plus the G1 proofs of its n jobs (s_i, x_i, offsets[i]), cut into
+        ceil(n / per_proof) proofs like prove_batch (bn254s_g1_msm).  Check it with verify_g1_msm."""
+        return self._msm("bn254s_g1_msm", 8, scalars, x, offset, per_proof, params)
+
+    def g2_msm_chain(self, scalars, x, offset):
+        """scalars [n,4], x [n,16], offset = R [16] -> (offsets [n+1,16], result [16]): the witness chain of g2_msm
+        (offsets[i] = R + sum_{j<i} s_j x_j with the unreduced 256-bit s_j, result = offsets[n] - R) on the device, no proof
+        (bn254s_g2_msm_chain)."""
+        return self._msm_chain("bn254s_g2_msm_chain", 16, scalars, x, offset)
+
+    def g2_msm(self, scalars, x, offset, per_proof=128, params: Optional[Params] = None):
+        """-> (result [16], offsets [n+1,16], proofs): the chain plus the G2 proofs of its n jobs (s_i, x_i, offsets[i]), cut into
+        ceil(n / per_proof) proofs like prove_batch(1, ...) (bn254s_g2_msm).  Check it with verify_g2_msm."""
+        return self._msm("bn254s_g2_msm", 16, scalars, x, offset, per_proof, params)
 
     def hash_to_fq2_batch(self, inputs: np.ndarray) -> np.ndarray:
         """inputs [n, len] Goldilocks elements -> u [n, 8]: hash_to_fq2 (hash_to_g2.rs:76-87) of every row, on the device."""
@@ -432,51 +450,68 @@ def verify_host(kind, words, degree_bits, scalars, x, offset, outputs, params: O
         raise RuntimeError(f"bn254s_verify_host failed with {rc}: {buf.value.decode()}")
 
 
+def _verify_msm(tag, kind, w, pt, neg, add, scalars, x, R, result, offsets, proofs, per_proof, ctx, params):
+    """The checks of verify_g1_msm / verify_g2_msm for points of w words: pt(words) -> affine point, neg / add the group law."""
+    scalars, x, R, result, offsets = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, R, result, offsets))
+    n = scalars.shape[0]
+    offsets = offsets.reshape(-1, w)
+    if x.shape != (n, w) or offsets.shape != (n + 1, w) or R.size != w or result.size != w:
+        raise VerifyError(f"{tag}: shapes: scalars {scalars.shape}, x {x.shape}, offsets {offsets.shape}, R {R.shape}, result {result.shape}")
+    if len(proofs) != (n + per_proof - 1) // per_proof:
+        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    if not np.array_equal(offsets[0], R.reshape(w)):
+        raise VerifyError(f"{tag}: offsets[0] != R")
+    for i, pr in enumerate(proofs):
+        lo, hi = i * per_proof, min(n, (i + 1) * per_proof)
+        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, w)
+        if outs.shape[0] != hi - lo:
+            raise VerifyError(f"{tag}: proof {i} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+        bad = np.nonzero(np.any(outs != offsets[lo + 1:hi + 1], axis=1))[0]
+        if bad.size:
+            j = lo + int(bad[0])
+            raise VerifyError(f"{tag}: output {j} of proof {i} != offsets[{j + 1}] (link s_{j} x_{j} + offset_{j})")
+    try:
+        want = add(pt(offsets[n]), neg(pt(R.reshape(w))))
+    except ValueError:
+        raise VerifyError(f"{tag}: offsets[n] == R, the result would be the point at infinity") from None
+    if pt(result.reshape(w)) != want:
+        raise VerifyError(f"{tag}: result != offsets[n] - R")
+    for i, pr in enumerate(proofs):
+        lo, hi = i * per_proof, min(n, (i + 1) * per_proof)
+        s_, x_, o_ = (np.ascontiguousarray(a[lo:hi]) for a in (scalars, x, offsets))
+        try:
+            if ctx is not None:
+                ctx.verify(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+            else:
+                verify_host(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+        except VerifyError as e:
+            raise VerifyError(f"{tag}: proof {i} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+
+
 def verify_g1_msm(scalars, x, R, result, offsets, proofs, per_proof, ctx: Optional[Context] = None, params: Optional[Params] = None):
     """Checks a g1_msm: the linkage (offsets[0] == R, the outputs of proof i are offsets[lo + 1 .. hi] for its jobs lo .. hi - 1,
     result == offsets[n] - R in Python integer arithmetic, tools/synth.py) and every proof (Context.verify with a context, else
     verify_host) against its jobs (s_i, x_i, offsets[i]).  `proofs`: objects with `words`, `degree_bits` and `outputs`, such as
     Proof.  Returns None or raises VerifyError naming the first broken link or the rejected proof."""
     from tools import synth
-    scalars, x, R, result, offsets = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, R, result, offsets))
-    n = scalars.shape[0]
-    offsets = offsets.reshape(-1, 8)
-    if x.shape != (n, 8) or offsets.shape != (n + 1, 8) or R.size != 8 or result.size != 8:
-        raise VerifyError(f"g1_msm: shapes: scalars {scalars.shape}, x {x.shape}, offsets {offsets.shape}, R {R.shape}, result {result.shape}")
-    if len(proofs) != (n + per_proof - 1) // per_proof:
-        raise VerifyError(f"g1_msm: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
-    if not np.array_equal(offsets[0], R.reshape(8)):
-        raise VerifyError("g1_msm: offsets[0] != R")
-    for i, pr in enumerate(proofs):
-        lo, hi = i * per_proof, min(n, (i + 1) * per_proof)
-        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 8)
-        if outs.shape[0] != hi - lo:
-            raise VerifyError(f"g1_msm: proof {i} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
-        bad = np.nonzero(np.any(outs != offsets[lo + 1:hi + 1], axis=1))[0]
-        if bad.size:
-            j = lo + int(bad[0])
-            raise VerifyError(f"g1_msm: output {j} of proof {i} != offsets[{j + 1}] (link s_{j} x_{j} + offset_{j})")
 
     def pt(w):
         return (synth.words_to_int(w[:4]), synth.words_to_int(w[4:]))
 
-    o, r = pt(offsets[n]), pt(R.reshape(8))
-    try:
-        want = synth.g1_add(o, (r[0], (-r[1]) % synth.P))
-    except ValueError:
-        raise VerifyError("g1_msm: offsets[n] == R, the result would be the point at infinity") from None
-    if pt(result.reshape(8)) != want:
-        raise VerifyError("g1_msm: result != offsets[n] - R")
-    for i, pr in enumerate(proofs):
-        lo, hi = i * per_proof, min(n, (i + 1) * per_proof)
-        s_, x_, o_ = (np.ascontiguousarray(a[lo:hi]) for a in (scalars, x, offsets))
-        try:
-            if ctx is not None:
-                ctx.verify(0, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-            else:
-                verify_host(0, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-        except VerifyError as e:
-            raise VerifyError(f"g1_msm: proof {i} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+    _verify_msm("g1_msm", 0, 8, pt, lambda p: (p[0], (-p[1]) % synth.P), synth.g1_add, scalars, x, R, result, offsets, proofs,
+                per_proof, ctx, params)
+
+
+def verify_g2_msm(scalars, x, R, result, offsets, proofs, per_proof, ctx: Optional[Context] = None, params: Optional[Params] = None):
+    """Checks a g2_msm like verify_g1_msm checks a g1_msm: the linkage, result == offsets[n] - R in Python integer arithmetic over
+    Fq2 (tools/synth.py) and every G2 proof (kind 1) against its jobs.  Returns None or raises VerifyError ("g2_msm: ...")."""
+    from tools import synth
+
+    def neg(p):
+        return (p[0], ((-p[1][0]) % synth.P, (-p[1][1]) % synth.P))
+
+    _verify_msm("g2_msm", 1, 16, synth.g2_from_words, neg, synth.g2_add, scalars, x, R, result, offsets, proofs, per_proof, ctx,
+                params)
 
 
 class BatchInFlight:

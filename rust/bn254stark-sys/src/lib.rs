@@ -105,5 +105,12 @@ extern "C" {
     /// the chain plus ceil(n / per_proof) G1 proofs of its jobs (s_i, x_i, offset_i); offsets_out may be null
     pub fn bn254s_g1_msm(ctx: *mut Bn254sCtx, params: *const Bn254sParams, scalars: *const u64, x: *const u64, offset: *const u64,
                          n: usize, per_proof: usize, result: *mut u64, offsets_out: *mut u64, proofs: *mut *mut Bn254sProof) -> c_int;
+    /// g2_msm (the g1_msm circuit with the G2 gadgets): offsets_out[0..=n] = R, R + s_0 x_0, ... ((n + 1) x 16 words, unreduced
+    /// 256-bit scalars), result = offsets_out[n] - R
+    pub fn bn254s_g2_msm_chain(ctx: *mut Bn254sCtx, scalars: *const u64, x: *const u64, offset: *const u64, n: usize,
+                               offsets_out: *mut u64, result: *mut u64) -> c_int;
+    /// the chain plus ceil(n / per_proof) G2 proofs of its jobs (s_i, x_i, offset_i); offsets_out may be null
+    pub fn bn254s_g2_msm(ctx: *mut Bn254sCtx, params: *const Bn254sParams, scalars: *const u64, x: *const u64, offset: *const u64,
+                         n: usize, per_proof: usize, result: *mut u64, offsets_out: *mut u64, proofs: *mut *mut Bn254sProof) -> c_int;
     pub fn bn254s_hash_to_fq2(input: *const u64, len: usize, out: *mut u64) -> c_int;
 }

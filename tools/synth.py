@@ -267,6 +267,97 @@ def g2_from_words(w):
     return ((words_to_int(w[0:4]), words_to_int(w[4:8])), (words_to_int(w[8:12]), words_to_int(w[12:16])))
 
 
+# ---- g2_msm: the g1_msm circuit (src/utils/g1_msm.rs:22-36) with the G2 gadgets --------------------------------------------
+def _f2j_double(p):
+    """2 p in Jacobian coordinates over Fq2 (the formulas of _jac_double); (1, 1, 0) = infinity."""
+    x, y, z = p
+    if z == (0, 0) or y == (0, 0):
+        return ((1, 0), (1, 0), (0, 0))
+    a = f2_mul(x, x)
+    b = f2_mul(y, y)
+    c = f2_mul(b, b)
+    xb = f2_add(x, b)
+    d = f2_sub(f2_sub(f2_mul(xb, xb), a), c)
+    d = f2_add(d, d)
+    e = f2_add(f2_add(a, a), a)
+    x3 = f2_sub(f2_mul(e, e), f2_add(d, d))
+    c8 = ((8 * c[0]) % P, (8 * c[1]) % P)
+    y3 = f2_sub(f2_mul(e, f2_sub(d, x3)), c8)
+    z3 = f2_mul(f2_add(y, y), z)
+    return (x3, y3, z3)
+
+
+def _f2j_add_affine(p, q):
+    """p (Jacobian over Fq2) + q (affine, not infinity), complete: doubles equal points, gives infinity for opposite ones."""
+    x1, y1, z1 = p
+    x2, y2 = q
+    if z1 == (0, 0):
+        return (x2, y2, (1, 0))
+    z1z1 = f2_mul(z1, z1)
+    u2 = f2_mul(x2, z1z1)
+    s2 = f2_mul(y2, f2_mul(z1, z1z1))
+    if u2 == x1:
+        if s2 == y1:
+            return _f2j_double(p)
+        return ((1, 0), (1, 0), (0, 0))
+    h = f2_sub(u2, x1)
+    hh = f2_mul(h, h)
+    hhh = f2_mul(h, hh)
+    r = f2_sub(s2, y1)
+    v = f2_mul(x1, hh)
+    x3 = f2_sub(f2_sub(f2_mul(r, r), hhh), f2_add(v, v))
+    y3 = f2_sub(f2_mul(r, f2_sub(v, x3)), f2_mul(y1, hhh))
+    z3 = f2_mul(z1, h)
+    return (x3, y3, z3)
+
+
+def _f2j_affine(j):
+    x, y, z = j
+    if z == (0, 0):
+        return None
+    zi = f2_inv(z)
+    zi2 = f2_mul(zi, zi)
+    return (f2_mul(x, zi2), f2_mul(y, f2_mul(zi2, zi)))
+
+
+def g2_mul_unreduced(k: int, pt):
+    """k * pt by Jacobian double-and-add over every bit of k, NOT reduced mod r (pt may lie outside the r-torsion subgroup, where
+    k pt != (k mod r) pt); affine result, None for infinity."""
+    acc = ((1, 0), (1, 0), (0, 0))
+    for bit in bin(k)[2:] if k else "":
+        acc = _f2j_double(acc)
+        if bit == "1":
+            acc = _f2j_add_affine(acc, pt)
+    return _f2j_affine(acc)
+
+
+def g2_msm_chain(scalars, xs, R):
+    """The g2_msm fold offset_0 = R, offset_{i+1} = s_i x_i + offset_i, msm = offset_n - R (the G2 twin of g1_msm_chain), with a
+    Jacobian Fq2 accumulator so that infinite partial sums pass through and the products over the unreduced 256-bit s_i, as the
+    G2 trace computes them.  scalars [n,4] (or ints) / xs [n,16] / R [16] in ABI words (or ((x0, x1), (y0, y1)) points).
+    Returns (offsets: n + 1 affine points, None for infinity; msm: affine point, None for infinity)."""
+    def pt(p):
+        return g2_from_words(p) if len(p) == 16 else ((int(p[0][0]), int(p[0][1])), (int(p[1][0]), int(p[1][1])))
+
+    r = pt(R)
+    acc = (r[0], r[1], (1, 0))
+    offsets = [r]
+    for s, x in zip(scalars, xs):
+        k = words_to_int(s) if not isinstance(s, int) else s
+        prod = g2_mul_unreduced(k, pt(x))
+        if prod is not None:
+            acc = _f2j_add_affine(acc, prod)
+        offsets.append(_f2j_affine(acc))
+    msm = _f2j_affine(_f2j_add_affine(acc, (r[0], ((-r[1][0]) % P, (-r[1][1]) % P))))
+    return offsets, msm
+
+
+def g2_points_to_words(pts):
+    """Affine ((x0, x1), (y0, y1)) points -> uint64 [len, 16] ABI words (x.c0, x.c1, y.c0, y.c1)."""
+    return np.array([_to_words(p[0][0]) + _to_words(p[0][1]) + _to_words(p[1][0]) + _to_words(p[1][1]) for p in pts],
+                    dtype=np.uint64).reshape(-1, 16)
+
+
 def fq_inputs(n: int, seed: int = 0x706C6F6E6B7932 + 5):
     """(scalars[n,4], x[n,4]) for the Fq exponentiation STARK: x uniform in [0,p), s any 256-bit value."""
     rng = Xoshiro256ss(seed)
