@@ -222,7 +222,7 @@ int bn254s_hash_to_fq2_batch(bn254s_ctx* ctx, const uint64_t* inputs, size_t n, 
  * offset_{i+1} = s_i x_i + offset_i with one G1 scalar-mul job per link, proves the n jobs (s_i, x_i, offset_i) in one G1
  * STARK (hook.rs:63-71) and returns msm = offset_n - R (G1Target::add: never infinity, a doubling is allowed).
  * bn254s_g1_msm_chain computes the witness chain on the device as a parallel prefix sum (products s_i x_i, a scan of the points,
- * one batched inversion; csrc/g1_msm.hip): offsets_out[0..n] = R, R + s_0 x_0, ..., R + sum s_j x_j ((n + 1) x 8 words) and
+ * one batched inversion; csrc/msm.hip): offsets_out[0..n] = R, R + s_0 x_0, ..., R + sum s_j x_j ((n + 1) x 8 words) and
  * result = offsets_out[n] - R (8 words).  Device front-end only, no proof.  BN254S_E_INVALID_POINT if some offset_i (i >= 1) is
  * the point at infinity (bn254s_last_error names the first such i) or if offset_n == R (the result would be infinity). */
 int bn254s_g1_msm_chain(bn254s_ctx* ctx, const uint64_t* scalars /* n x 4 */, const uint64_t* x /* n x 8 */,
@@ -239,7 +239,7 @@ int bn254s_g1_msm(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* 
  * (set_random_g2 for R, g2_scalar_mul per link, G2Target::neg / add, curves/g2.rs:93-150): offset_0 = R (non-infinity),
  * offset_{i+1} = s_i x_i + offset_i, msm = offset_n - R.  Points are 16 words (x.c0, x.c1, y.c0, y.c1).  Scalars are used as
  * the full 256-bit values, as the G2 trace computes them: for x_i outside the r-torsion subgroup s x_i != (s mod r) x_i.
- * bn254s_g2_msm_chain (csrc/g2_msm.hip): offsets_out[0..n] ((n + 1) x 16 words) and result = offsets_out[n] - R (16 words) on the
+ * bn254s_g2_msm_chain (csrc/msm.hip): offsets_out[0..n] ((n + 1) x 16 words) and result = offsets_out[n] - R (16 words) on the
  * device, no proof.  BN254S_E_INVALID_POINT if some offset_i (i >= 1) is the point at infinity (bn254s_last_error names the
  * first such i) or if offset_n == R; offset_n == -R doubles. */
 int bn254s_g2_msm_chain(bn254s_ctx* ctx, const uint64_t* scalars /* n x 4 */, const uint64_t* x /* n x 16 */,

@@ -542,6 +542,55 @@ __device__ __forceinline__ fq2 fq2_inv_from_norm_inv(const fq2& a, const fq& nin
   r.c1 = fq_neg(fq_mul(a.c1, ninv));
   return r;
 }
+__device__ __forceinline__ fq2 fq2_inv(const fq2& a) { return fq2_inv_from_norm_inv(a, fq_inv(fq2_norm(a))); }  // a != 0
+__device__ __forceinline__ fq2 fq2_neg(const fq2& a) {
+  fq2 r;
+  r.c0 = fq_neg(a.c0);
+  r.c1 = fq_neg(a.c1);
+  return r;
+}
+// eight canonical (non-Montgomery) words, c0 first
+__device__ __forceinline__ fq2 fq2_from_canonical(const u64* w) {
+  fq2 r;
+  r.c0 = fq_from_canonical(w);
+  r.c1 = fq_from_canonical(w + 4);
+  return r;
+}
+__device__ __forceinline__ void fq2_store_canonical(u64* w, const fq2& a) {
+  const fqw c0 = fq_to_canonical(a.c0), c1 = fq_to_canonical(a.c1);
+#pragma unroll
+  for (int l = 0; l < 4; l++) {
+    w[l] = c0.l[l];
+    w[4 + l] = c1.l[l];
+  }
+}
+
+// ---- the coordinate field of a curve, Fq (G1) or Fq2 (G2), by overloading: for code that is written once for both ------------
+__device__ __forceinline__ fq fe_add(const fq& a, const fq& b) { return fq_add(a, b); }
+__device__ __forceinline__ fq2 fe_add(const fq2& a, const fq2& b) { return fq2_add(a, b); }
+__device__ __forceinline__ fq fe_sub(const fq& a, const fq& b) { return fq_sub(a, b); }
+__device__ __forceinline__ fq2 fe_sub(const fq2& a, const fq2& b) { return fq2_sub(a, b); }
+__device__ __forceinline__ fq fe_mul(const fq& a, const fq& b) { return fq_mul(a, b); }
+__device__ __forceinline__ fq2 fe_mul(const fq2& a, const fq2& b) { return fq2_mul(a, b); }
+__device__ __forceinline__ fq fe_sqr(const fq& a) { return fq_sqr(a); }
+__device__ __forceinline__ fq2 fe_sqr(const fq2& a) { return fq2_sqr(a); }
+__device__ __forceinline__ fq fe_neg(const fq& a) { return fq_neg(a); }
+__device__ __forceinline__ fq2 fe_neg(const fq2& a) { return fq2_neg(a); }
+__device__ __forceinline__ fq fe_inv(const fq& a) { return fq_inv(a); }
+__device__ __forceinline__ fq2 fe_inv(const fq2& a) { return fq2_inv(a); }
+__device__ __forceinline__ bool fe_is_zero(const fq& a) { return fq_is_zero(a); }
+__device__ __forceinline__ bool fe_is_zero(const fq2& a) { return fq2_is_zero(a); }
+__device__ __forceinline__ void fe_one(fq& r) { r = fq_one(); }
+__device__ __forceinline__ void fe_one(fq2& r) { r = fq2_one(); }
+// canonical words (four or eight) <-> Montgomery registers
+__device__ __forceinline__ void fe_from_canonical(const u64* w, fq& r) { r = fq_from_canonical(w); }
+__device__ __forceinline__ void fe_from_canonical(const u64* w, fq2& r) { r = fq2_from_canonical(w); }
+__device__ __forceinline__ void fe_store_canonical(u64* w, const fq& a) {
+  const fqw c = fq_to_canonical(a);
+#pragma unroll
+  for (int l = 0; l < 4; l++) w[l] = c.l[l];
+}
+__device__ __forceinline__ void fe_store_canonical(u64* w, const fq2& a) { fq2_store_canonical(w, a); }
 
 struct g2j {
   fq2 x, y, z;

@@ -37,26 +37,6 @@ M2GConsts host_consts() {
   return c;
 }
 
-__device__ __forceinline__ fq2 f2_from(const u64* w) {
-  fq2 r;
-  r.c0 = fq_from_canonical(w);
-  r.c1 = fq_from_canonical(w + 4);
-  return r;
-}
-__device__ __forceinline__ void f2_store_canonical(u64* w, const fq2& a) {
-  const fqw c0 = fq_to_canonical(a.c0), c1 = fq_to_canonical(a.c1);
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    w[i] = c0.l[i];
-    w[4 + i] = c1.l[i];
-  }
-}
-__device__ __forceinline__ fq2 f2_neg(const fq2& a) {
-  fq2 r;
-  r.c0 = fq_neg(a.c0);
-  r.c1 = fq_neg(a.c1);
-  return r;
-}
 __device__ __noinline__ fq fq_pow_words(const fq& a, const u64* e) {  // a^e, e < 2^256
   fq r = fq_one();
   for (int i = 255; i >= 0; i--) {
@@ -65,7 +45,6 @@ __device__ __noinline__ fq fq_pow_words(const fq& a, const u64* e) {  // a^e, e 
   }
   return r;
 }
-__device__ __forceinline__ fq2 f2_inv(const fq2& a) { return fq2_inv_from_norm_inv(a, fq_inv(fq2_norm(a))); }
 __device__ __forceinline__ fq2 g_rhs(const fq2& x, const fq2& b2) { return fq2_add(fq2_mul(fq2_sqr(x), x), b2); }
 __device__ __forceinline__ bool fq_is_square(const fq& a, const M2GConsts& C) {
   return fq_is_zero(a) || fq_eq(fq_pow_words(a, C.leg), fq_one());
@@ -104,20 +83,20 @@ __global__ __launch_bounds__(64) void k_m2g_candidates(const u64* __restrict__ u
                                                        u64* __restrict__ fq_s, u64* __restrict__ fq_x) {
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
-  const fq2 uu = f2_from(u + 8 * k), gz = f2_from(C.gz), b2 = f2_from(C.b2);
+  const fq2 uu = fq2_from_canonical(u + 8 * k), gz = fq2_from_canonical(C.gz), b2 = fq2_from_canonical(C.b2);
   fq2 tv1 = fq2_mul(fq2_sqr(uu), gz);
   const fq2 tv2 = fq2_add(fq2_one(), tv1);
   tv1 = fq2_sub(fq2_one(), tv1);
-  const fq2 tv3 = f2_inv(fq2_mul(tv1, tv2));
-  const fq2 tv5 = fq2_mul(fq2_mul(fq2_mul(uu, tv1), tv3), f2_from(C.tv4));
-  const fq2 nz2 = f2_from(C.nz2);
+  const fq2 tv3 = fq2_inv(fq2_mul(tv1, tv2));
+  const fq2 tv5 = fq2_mul(fq2_mul(fq2_mul(uu, tv1), tv3), fq2_from_canonical(C.tv4));
+  const fq2 nz2 = fq2_from_canonical(C.nz2);
   fq2 x[3];
   x[0] = fq2_sub(nz2, tv5);
   x[1] = fq2_add(nz2, tv5);
   const fq2 t = fq2_mul(fq2_sqr(tv2), tv3);
-  x[2] = fq2_add(fq2_one(), fq2_mul(f2_from(C.tv6), fq2_sqr(t)));
+  x[2] = fq2_add(fq2_one(), fq2_mul(fq2_from_canonical(C.tv6), fq2_sqr(t)));
 #pragma unroll 1
-  for (int i = 0; i < 3; i++) f2_store_canonical(cand + (3 * k + i) * 8, x[i]);
+  for (int i = 0; i < 3; i++) fq2_store_canonical(cand + (3 * k + i) * 8, x[i]);
 #pragma unroll 1
   for (int i = 0; i < 2; i++) {
     const fqw nrm = fq_to_canonical(fq2_norm(g_rhs(x[i], b2)));
@@ -136,13 +115,13 @@ __global__ __launch_bounds__(64) void k_m2g_select(const u64* __restrict__ u, co
   if (k >= n) return;
   auto is_one = [&](const u64* w) { return w[0] == 1 && (w[1] | w[2] | w[3]) == 0; };
   const int pick = is_one(legendre + (2 * k) * 4) ? 0 : is_one(legendre + (2 * k + 1) * 4) ? 1 : 2;
-  const fq2 x = f2_from(cand + (3 * k + pick) * 8);
+  const fq2 x = fq2_from_canonical(cand + (3 * k + pick) * 8);
   bool ok;
-  fq2 y = f2_sqrt(g_rhs(x, f2_from(C.b2)), C, &ok);
+  fq2 y = f2_sqrt(g_rhs(x, fq2_from_canonical(C.b2)), C, &ok);
   if (!ok) atomicCAS(err, 0, BN254S_E_INTERNAL);  // g(x) is not a square: inconsistent Legendre results
-  if (f2_sgn(f2_from(u + 8 * k)) != f2_sgn(y)) y = f2_neg(y);
+  if (f2_sgn(fq2_from_canonical(u + 8 * k)) != f2_sgn(y)) y = fq2_neg(y);
   for (int w = 0; w < 8; w++) g2_x[16 * k + w] = cand[(3 * k + pick) * 8 + w];
-  f2_store_canonical(g2_x + 16 * k + 8, y);
+  fq2_store_canonical(g2_x + 16 * k + 8, y);
   for (int w = 0; w < 4; w++) g2_s[4 * k + w] = C.cof[w];
 }
 
@@ -151,18 +130,18 @@ __global__ __launch_bounds__(64) void k_m2g_finish(const u64* __restrict__ o, co
                                                    int* __restrict__ err) {
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
-  const fq2 x1 = f2_from(o + 16 * k), y1 = f2_from(o + 16 * k + 8);
-  const fq2 x2 = f2_from(off + 16 * k), y2 = f2_neg(f2_from(off + 16 * k + 8));
+  const fq2 x1 = fq2_from_canonical(o + 16 * k), y1 = fq2_from_canonical(o + 16 * k + 8);
+  const fq2 x2 = fq2_from_canonical(off + 16 * k), y2 = fq2_neg(fq2_from_canonical(off + 16 * k + 8));
   const fq2 dx = fq2_sub(x2, x1);
   if (fq2_is_zero(dx)) {
     atomicCAS(err, 0, BN254S_E_INVALID_POINT);
     return;
   }
-  const fq2 lam = fq2_mul(fq2_sub(y2, y1), f2_inv(dx));
+  const fq2 lam = fq2_mul(fq2_sub(y2, y1), fq2_inv(dx));
   const fq2 x3 = fq2_sub(fq2_sub(fq2_sqr(lam), x1), x2);
   const fq2 y3 = fq2_sub(fq2_mul(lam, fq2_sub(x1, x3)), y1);
-  f2_store_canonical(out + 16 * k, x3);
-  f2_store_canonical(out + 16 * k + 8, y3);
+  fq2_store_canonical(out + 16 * k, x3);
+  fq2_store_canonical(out + 16 * k + 8, y3);
 }
 
 // hash_to_fq2 for n inputs of `len` Goldilocks elements each, one lane per input (hash_to_g2.rs:76-87): the challenger absorbs the

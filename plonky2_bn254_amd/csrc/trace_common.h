@@ -20,6 +20,17 @@ __device__ __forceinline__ void st_fq(u64* base, size_t count, size_t e, const f
 #pragma unroll
   for (int l = 0; l < 4; l++) base[l * count + e] = w.l[l];
 }
+// the same for a coordinate of either curve (fe_*, fq_dev.h): an Fq2 element is two Fq vectors in a row, c1 at base + 4 count
+__device__ __forceinline__ void fe_ld(const u64* base, size_t count, size_t e, fq& r) { r = ld_fq(base, count, e); }
+__device__ __forceinline__ void fe_ld(const u64* base, size_t count, size_t e, fq2& r) {
+  r.c0 = ld_fq(base, count, e);
+  r.c1 = ld_fq(base + 4 * count, count, e);
+}
+__device__ __forceinline__ void fe_st(u64* base, size_t count, size_t e, const fq& v) { st_fq(base, count, e, v); }
+__device__ __forceinline__ void fe_st(u64* base, size_t count, size_t e, const fq2& v) {
+  st_fq(base, count, e, v.c0);
+  st_fq(base + 4 * count, count, e, v.c1);
+}
 
 // index of the highest set bit of s below position k, or -1
 __device__ __forceinline__ int last_set_below(const u64 s[4], int k) {

@@ -29,5 +29,5 @@ void launch_range_columns(u64* trace, size_t N, int rc_begin, int rc_end, int fr
                           hipStream_t st);
 void launch_fq_inv_selftest(const u64* in, u64* out, size_t n, hipStream_t st);
 // the cooperative doubling chain of phase A alone: D_k = 2^k x_i (k = 0..256, Jacobian, Montgomery) at point index 257 + k of the
-// SoA arrays px / py / pz (4 * NPTS * n words each, element (257 + k) * n + i); g1_msm.hip uses it for the products s_i x_i
+// SoA arrays px / py / pz (4 * NPTS * n words each, element (257 + k) * n + i); msm.hip uses it for the products s_i x_i
 void launch_g1_dbl_chain(const u64* d_x, int n, u64* px, u64* py, u64* pz, hipStream_t st);

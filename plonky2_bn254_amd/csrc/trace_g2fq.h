@@ -11,5 +11,5 @@ int fq_generate_trace_device(const u64* d_scalars, const u64* d_x, size_t n, u64
                              u64* d_outputs, int* d_err, hipStream_t st, bool with_range = true);
 // the cooperative doubling chain of phase A alone: D_k = 2^k x_i (k = 0..256, Jacobian, Montgomery) at point index 257 + k.  pts
 // holds six SoA Fq vectors of 4 * NPTS * n words each, X.c0, X.c1, Y.c0, Y.c1, Z.c0, Z.c1 one after the other (element
-// (257 + k) * n + i), znorm one more (the norms of Z); g2_msm.hip uses it for the products s_i x_i
+// (257 + k) * n + i), znorm one more (the norms of Z); msm.hip uses it for the products s_i x_i
 void launch_g2_dbl_chain(const u64* d_x, int n, u64* pts, u64* znorm, hipStream_t st);

@@ -27,12 +27,6 @@ __device__ __forceinline__ void st_fq2(const Soa2& v, size_t cnt, size_t e, cons
   st_fq(v.c0, cnt, e, x.c0);
   st_fq(v.c1, cnt, e, x.c1);
 }
-__device__ __forceinline__ fq2 fq2_from_canonical(const u64* w) {
-  fq2 r;
-  r.c0 = fq_from_canonical(w);
-  r.c1 = fq_from_canonical(w + 4);
-  return r;
-}
 
 // phase A as in trace_g1.hip: sequential doubling chain, then the running sums by a parallel scan (chain_scan.h)
 __global__ __launch_bounds__(64) void k_g2_dbl_chain(const u64* __restrict__ xs, int n, Soa2 px, Soa2 py, Soa2 pz,

@@ -1,4 +1,4 @@
-"""g2_msm on the GPU (the g1_msm circuit, src/utils/g1_msm.rs:22-36, with the G2 gadgets): the device chain (csrc/g2_msm.hip)
+"""g2_msm on the GPU (the g1_msm circuit, src/utils/g1_msm.rs:22-36, with the G2 gadgets): the device chain (csrc/msm.hip)
 against the Python fold (tools/synth.py g2_msm_chain), the chained G2 proofs checked with verify_g2_msm, and the error cases."""
 import numpy as np
 import pytest

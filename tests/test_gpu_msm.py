@@ -1,4 +1,4 @@
-"""g1_msm on the GPU (reference src/utils/g1_msm.rs:22-36): the device chain (csrc/g1_msm.hip) against the Python fold
+"""g1_msm on the GPU (reference src/utils/g1_msm.rs:22-36): the device chain (csrc/msm.hip) against the Python fold
 (tools/synth.py g1_msm_chain), the chained proofs checked with verify_g1_msm, and the error cases."""
 import numpy as np
 import pytest
