@@ -99,7 +99,9 @@ __device__ __forceinline__ void accw_init(AccW& a) {
   acc3_init(a.a0);
   acc3_init(a.a1);
 }
-__device__ __forceinline__ void accw_mad(AccW& a, u64 x, const u32* __restrict__ w) {  // x canonical
+// (WP: const u32* or its constant-address-space form, QCONST in quotient_sched.h)
+template <class WP>
+__device__ __forceinline__ void accw_mad(AccW& a, u64 x, WP w) {  // x canonical
   const u32 v0 = (u32)x & M22, v1 = (u32)(x >> 22) & M22, v2 = (u32)(x >> 44);
   acc3_mad(a.a0, v0, v1, v2, w[0], w[1], w[2]);
   acc3_mad(a.a1, v0, v1, v2, w[4], w[5], w[6]);

@@ -20,22 +20,15 @@ static constexpr int G1_K_AIR = 1111;
 static constexpr int G1_MZ_E0[5] = {0, 50, 83, 132, 165};
 
 // Parts 0..4: the five eval_modulus_zero blocks of eval_g1_add (each with the small groups emitted next to it);
-// part 5: the schedule.  One lane per LDE point and part, one launch per part.
-__global__ __launch_bounds__(256, 2) void k_quotient_g1_sched(QArgs A) {
-  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= A.count) return;
-  schedule_part<G1L, false>(A, j, q_next(A, j), 198, 5);
-}
-
+// part 5: the schedule.  One lane per LDE point and part; the parts write independent partial sums, so one launch covers
+// them all: blockIdx.y selects the part (k_quotient_g1_parts below).
 template <int part>
-__global__ __launch_bounds__(256, 2) void k_quotient_g1_add(QArgs A) {
+__device__ __forceinline__ void g1_add_part(const QArgs& A, size_t j) {
   const size_t M2 = A.stride;
-  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= A.count) return;
   const u64* __restrict__ tl = A.tl;
-  const u64* __restrict__ W0 = A.W;
-  const u64* __restrict__ W1 = A.W + A.K;
-  const u32* __restrict__ W3 = (const u32*)(A.W + 2 * (size_t)A.K);  // cut weights (accw_mad)
+  const qc64 W0 = QCONST(u64, A.W);
+  const qc64 W1 = QCONST(u64, A.W + A.K);
+  const qc32 W3 = QCONST(u32, A.W + 2 * (size_t)A.K);  // cut weights (accw_mad)
   u64 tot0 = 0, tot1 = 0;
   int e = 0;
   const int AUX = G1_COL_AUX;
@@ -71,11 +64,13 @@ __global__ __launch_bounds__(256, 2) void k_quotient_g1_add(QArgs A) {
     for (int i = 0; i < 16; i++) u16[i] = gl_sub(u16[i], ax[i]);  // delta_x
     ld16(tl, M2, j, G1_COL_B + 16, t16);                          // b.y
     ld16(tl, M2, j, G1_COL_A + 16, ax);                           // a.y (a.x no longer needed)
+#pragma unroll
+    for (int i = 0; i < 16; i++) t16[i] = gl_sub(t16[i], ax[i]);  // b.y - a.y, formed here: three arrays live in the block, not four
     mz_block<true>(tl, M2, j, AUX + G1_AUX_LAMBDA_AUX, A, G1_MZ_E0[1], 1,
              gl_sub(filter, is_x_eq_filter),
              [&](int i) __attribute__((always_inline)) {
                u64 v = conv16<true>(lam, u16, i);
-               return i < 16 ? gl_sub(v, gl_sub(t16[i < 16 ? i : 0], ax[i < 16 ? i : 0])) : v;
+               return i < 16 ? gl_sub(v, t16[i < 16 ? i : 0]) : v;
              },
              tot0, tot1);
   } else if constexpr (part == 2) {
@@ -102,10 +97,12 @@ __global__ __launch_bounds__(256, 2) void k_quotient_g1_add(QArgs A) {
     ld16(tl, M2, j, AUX + G1_AUX_LAMBDA, lam);
     ld16(tl, M2, j, G1_COL_B, t16);
     ld16(tl, M2, j, G1_COL_C, u16);
+#pragma unroll
+    for (int i = 0; i < 16; i++) ax[i] = gl_add(gl_add(ax[i], t16[i]), u16[i]);  // a.x + b.x + c.x: two arrays live in the block
     mz_block<true>(tl, M2, j, AUX + G1_AUX_X_AUX, A, G1_MZ_E0[3], 3, filter,
              [&](int i) __attribute__((always_inline)) {
                u64 v = conv16<true>(lam, lam, i);
-               return i < 16 ? gl_sub(v, gl_add(gl_add(ax[i < 16 ? i : 0], t16[i < 16 ? i : 0]), u16[i < 16 ? i : 0])) : v;
+               return i < 16 ? gl_sub(v, ax[i < 16 ? i : 0]) : v;
              },
              tot0, tot1);
   } else {
@@ -116,14 +113,32 @@ __global__ __launch_bounds__(256, 2) void k_quotient_g1_add(QArgs A) {
     for (int i = 0; i < 16; i++) u16[i] = gl_sub(u16[i], ax[i]);  // c.x - a.x
     ld16(tl, M2, j, G1_COL_C + 16, t16);                          // c.y
     ld16(tl, M2, j, G1_COL_A + 16, ax);                           // a.y
+#pragma unroll
+    for (int i = 0; i < 16; i++) t16[i] = gl_add(t16[i], ax[i]);  // c.y + a.y
     mz_block<true>(tl, M2, j, AUX + G1_AUX_Y_AUX, A, G1_MZ_E0[4], 4, filter,
              [&](int i) __attribute__((always_inline)) {
                u64 v = conv16<true>(lam, u16, i);
-               return i < 16 ? gl_add(v, gl_add(t16[i < 16 ? i : 0], ax[i < 16 ? i : 0])) : v;
+               return i < 16 ? gl_add(v, t16[i < 16 ? i : 0]) : v;
              },
              tot0, tot1);
   }
   store_part(A, part, j, tot0, tot1);
+}
+
+// All six parts of a proof in one grid: 6 x 2N lanes of independent work per launch instead of 2N lanes six times over, so
+// a SIMD always has a next wave to start when one retires (no drain between parts).  The schedule (the longest part) takes
+// blockIdx.y = 0: workgroups are dispatched x first, then y, so it starts first and does not form the tail.
+__global__ __launch_bounds__(256, 2) void k_quotient_g1_parts(QArgs A) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= A.count) return;
+  switch (blockIdx.y) {
+    case 0: schedule_part<G1L, false>(A, j, q_next(A, j), 198, 5); break;
+    case 1: g1_add_part<0>(A, j); break;
+    case 2: g1_add_part<1>(A, j); break;
+    case 3: g1_add_part<2>(A, j); break;
+    case 4: g1_add_part<3>(A, j); break;
+    default: g1_add_part<4>(A, j); break;
+  }
 }
 
 __global__ __launch_bounds__(256) void k_quotient_finish(QArgs A, StarkShape sh) {
@@ -269,12 +284,7 @@ void g1_quotient_launch(const QArgs& A0, const StarkShape& sh, hipStream_t st) {
   QArgs A = A0;
   A.n_parts = 6;
   const unsigned g = (unsigned)((A.count + 255) / 256);
-  k_quotient_g1_add<0><<<g, 256, 0, st>>>(A);
-  k_quotient_g1_add<1><<<g, 256, 0, st>>>(A);
-  k_quotient_g1_add<2><<<g, 256, 0, st>>>(A);
-  k_quotient_g1_add<3><<<g, 256, 0, st>>>(A);
-  k_quotient_g1_add<4><<<g, 256, 0, st>>>(A);
-  k_quotient_g1_sched<<<g, 256, 0, st>>>(A);
+  k_quotient_g1_parts<<<dim3(g, 6), 256, 0, st>>>(A);
   quotient_finish_launch(A, sh, st);
 }
 

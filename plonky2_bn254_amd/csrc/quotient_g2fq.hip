@@ -37,9 +37,9 @@ __global__ __launch_bounds__(256, 2) void k_quotient_g2_add(QArgs A) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= A.count) return;
   const u64* __restrict__ tl = A.tl;
-  const u64* __restrict__ W0 = A.W;
-  const u64* __restrict__ W1 = A.W + A.K;
-  const u32* __restrict__ W3 = (const u32*)(A.W + 2 * (size_t)A.K);  // cut weights (accw_mad)
+  const qc64 W0 = QCONST(u64, A.W);
+  const qc64 W1 = QCONST(u64, A.W + A.K);
+  const qc32 W3 = QCONST(u32, A.W + 2 * (size_t)A.K);  // cut weights (accw_mad)
   u64 tot0 = 0, tot1 = 0;
   int e = 0;
   const u64 filter = TL(L::FILTER);
@@ -164,8 +164,8 @@ __global__ __launch_bounds__(256) void k_quotient_fq_mul(QArgs A) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= A.count) return;
   const u64* __restrict__ tl = A.tl;
-  const u64* __restrict__ W0 = A.W;
-  const u64* __restrict__ W1 = A.W + A.K;
+  const qc64 W0 = QCONST(u64, A.W);
+  const qc64 W1 = QCONST(u64, A.W + A.K);
   u64 tot0 = 0, tot1 = 0;
   const u64 filter = TL(L::FILTER);
   u64 a[16], b[16], c[16];

@@ -39,6 +39,14 @@ static constexpr size_t QUOTIENT_MZT3_OFF = 10 * 2 * 80, QUOTIENT_MZT_WORDS = 10
 static inline size_t QUOTIENT_W_WORDS(int K) { return 6 * (size_t)K; }
 __device__ __forceinline__ size_t q_next(const QArgs& A, size_t j) { return A.natural ? j + 1 : next_position(j, A.log_n); }
 
+// The weight and modulus-zero tables are written before the stage starts and by no quotient kernel.  They are read through
+// the constant address space, which makes every load with a uniform address a scalar load by construction.  Through a plain
+// pointer that depends on the compiler proving that no store of the kernel can reach the load, and it gives that up in a
+// kernel as large as the merged part grids: the tables then come through vector loads, two registers per weight.
+#define QCONST(T, p) ((const __attribute__((address_space(4))) T*)(p))
+typedef const __attribute__((address_space(4))) u64* qc64;
+typedef const __attribute__((address_space(4))) u32* qc32;
+
 #define TL(c) tl[(size_t)(c)*M2 + j]
 #define TN(c) tl[(size_t)(c)*M2 + jn]
 
@@ -75,12 +83,12 @@ __device__ __forceinline__ u64 conv16(const u64* A, const u64* B, int i) {
 template <bool FULL = false, class InFn>
 __device__ __forceinline__ void mz_block(const u64* __restrict__ tl, size_t M2, size_t j, int auxcol, const QArgs& A, int e0, int blk,
                                          u64 filter, InFn in, u64& tot0, u64& tot1, const Acc2* seed = nullptr) {
-  const u64* __restrict__ w0 = A.W + e0;
-  const u64* __restrict__ w1 = A.W + A.K + e0;
-  const u64* __restrict__ T0 = A.mzt + (size_t)blk * 160;
-  const u64* __restrict__ T1 = T0 + 80;
-  const u32* __restrict__ w3 = (const u32*)(A.W + 2 * (size_t)A.K) + 8 * (size_t)e0;                   // cut weights (accw_mad)
-  const u32* __restrict__ T3 = (const u32*)(A.mzt + QUOTIENT_MZT3_OFF) + 8 * (size_t)(blk * 80);
+  const qc64 w0 = QCONST(u64, A.W + e0);
+  const qc64 w1 = QCONST(u64, A.W + A.K + e0);
+  const qc64 T0 = QCONST(u64, A.mzt + (size_t)blk * 160);
+  const qc64 T1 = T0 + 80;
+  const qc32 w3 = QCONST(u32, A.W + 2 * (size_t)A.K) + 8 * (size_t)e0;                   // cut weights (accw_mad)
+  const qc32 T3 = QCONST(u32, A.mzt + QUOTIENT_MZT3_OFF) + 8 * (size_t)(blk * 80);
   // The input polynomial first (its limb products need the most registers), reduced to two field elements before the witness
   // columns of the block are summed.  `seed`: the weighted sum of a part of the input polynomial that the caller accumulated
   // beforehand (the block is linear in its input: terms that need other trace columns than the limb products are summed
@@ -93,7 +101,13 @@ __device__ __forceinline__ void mz_block(const u64* __restrict__ tl, size_t M2, 
     else acc2_init(neg);
     if constexpr (FULL) {
 #pragma clang loop unroll(full)
-      for (int i = 0; i < 31; i++) acc2_mad(neg, in(i), w0[1 + i], w1[1 + i]);
+      for (int i = 0; i < 31; i++) {
+        acc2_mad(neg, in(i), w0[1 + i], w1[1 + i]);
+        if (i % 8 == 7) {  // groups of eight coefficients: pinned and fenced, or the compiler sinks them all below the loops
+          asm volatile("" : "+v"(neg.a0.lo), "+v"(neg.a0.hi), "+v"(neg.a0.ov), "+v"(neg.a1.lo), "+v"(neg.a1.hi), "+v"(neg.a1.ov));
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < 31; i++) {
@@ -103,6 +117,7 @@ __device__ __forceinline__ void mz_block(const u64* __restrict__ tl, size_t M2, 
     }
     n0 = acc_red(neg.a0);
     n1 = acc_red(neg.a1);
+    asm volatile("" : "+v"(n0), "+v"(n1));
   }
   __builtin_amdgcn_sched_barrier(0);
   // the witness columns of the block, weights cut in limbs (accw_mad); one accumulator pair live at a time
@@ -183,9 +198,9 @@ __device__ __forceinline__ void schedule_part(const QArgs& A, size_t j, size_t j
   u64 tot0 = 0, tot1 = 0;
   const size_t M2 = A.stride;
   const u64* __restrict__ tl = A.tl;
-  const u64* __restrict__ W0 = A.W;
-  const u64* __restrict__ W1 = A.W + A.K;
-  const u32* __restrict__ W3 = (const u32*)(A.W + 2 * (size_t)A.K);  // cut weights (accw_mad), 8 u32 per constraint
+  const qc64 W0 = QCONST(u64, A.W);
+  const qc64 W1 = QCONST(u64, A.W + A.K);
+  const qc32 W3 = QCONST(u32, A.W + 2 * (size_t)A.K);  // cut weights (accw_mad), 8 u32 per constraint
   const u64 filter = TL(L::FILTER);
   // ---- eval_packed_generic body (scalar_mul_stark.rs:257-339) ------------------------------------------
   const u64 is_first = TL(L::FLAGS + 0), is_last = TL(L::FLAGS + 1);
