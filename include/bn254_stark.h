@@ -32,10 +32,11 @@
  * Threading: one call at a time per context (one host thread enters the context at a time); any number of contexts (one per
  * GPU / per host thread).  A batch opened with bn254s_prove_batch_begin stays in flight after _begin returns: until its _end
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
- * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm) queues behind the open batches on the same worker pool and runs
- * on a free slot (stream + workspace) of its own, so it can never share device state with a proof of the open batch;
- * bn254s_verify, _commit_values, _generate_trace and the _bench_* calls use the context's own stream and buffers and are
- * independent of open batches.
+ * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x) queues behind the open batches on the
+ * same worker pool and runs on a free slot (stream + workspace) of its own, so it can never share device state with a proof of
+ * the open batch; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device front-ends
+ * (bn254s_g1_recover_from_x_batch and the front-end half of bn254s_g1_recover_from_x, like those of bn254s_map_to_g2 and the
+ * msm chains) use the context's own stream and pooled buffers under keys of their own and are independent of open batches.
  */
 #ifndef BN254_STARK_H
 #define BN254_STARK_H
@@ -250,6 +251,26 @@ int bn254s_g2_msm_chain(bn254s_ctx* ctx, const uint64_t* scalars /* n x 4 */, co
 int bn254s_g2_msm(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
                   const uint64_t* offset, size_t n, size_t per_proof, uint64_t* result, uint64_t* offsets_out,
                   bn254s_proof** proofs);
+
+/* G1 point recovery from x: the witness side of G1Target::is_recoverable_from_x / recover_from_x (src/curves/g1.rs:76-95; native
+ * form src/fields/recover.rs; is_square src/fields/fq.rs:283-295, sqrt_with_sgn src/fields/fq.rs:266-281).  For every x_i
+ * (4 words, canonical: some x_i >= p is BN254S_E_INVALID_ARG, found on the host before any device work, and bn254s_last_error
+ * names the first such i) the device computes g_i = x_i^3 + 3 and one exponentiation c = g_i^((p+1)/4) (csrc/g1_recover.hip):
+ *   flags_out[i]  = 1 iff g_i is a square in Fq (g_i is never zero: -3 is not a cube modulo p);
+ *   points_out[i] = (x_i, y_i) with y_i^2 = g_i, y_i < p and y_i even ("sgn false") where the flag is 1, (x_i, 0) where it is 0;
+ *   fq_jobs[i]    = (p-1)/2 | g_i (8 words; may be NULL): the Fq-exp job whose output is the Legendre symbol of g_i.
+ * bn254s_g1_recover_from_x_batch: device front-end only, no proof. */
+int bn254s_g1_recover_from_x_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 4, canonical < p */, size_t n,
+                                   uint64_t* points_out /* n x 8 */, uint8_t* flags_out /* n */,
+                                   uint64_t* fq_jobs /* may be NULL: n x 8 = scalar (p-1)/2 | g */);
+/* The front-end plus the Fq-exp proofs of the n Legendre jobs, cut into ceil(n / per_proof) proofs exactly as
+ * bn254s_prove_batch (kind 2) cuts them.  The outputs of the proofs are checked word for word against the flags: job i must
+ * give 1 where flags_out[i] is 1 and p - 1 where it is 0; a mismatch is BN254S_E_INTERNAL.  On any error every proof of the call
+ * is freed and its slot in fq_proofs is NULL.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work (invalid
+ * arguments are reported first). */
+int bn254s_g1_recover_from_x(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* xs, size_t n, size_t per_proof,
+                             uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs /* may be NULL */,
+                             bn254s_proof** fq_proofs);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

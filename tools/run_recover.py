@@ -1,0 +1,76 @@
+"""G1 point recovery from x on ONE GPU (reference src/curves/g1.rs:76-95): the device front-end alone
+(bn254s_g1_recover_from_x_batch) and the front-end plus the Fq-exp proofs of its Legendre jobs (bn254s_g1_recover_from_x)
+against bn254s_prove_batch of the same jobs; and, in the same process, bn254s_g1_msm_chain at the same sizes: the chain folds
+the points that recovery produces, so it is the yardstick for the front-end.
+usage: python tools/run_recover.py [reps=5]
+Inputs: uniform x below p (about half of them recoverable); for the chain 4096 distinct random points tiled and random 256-bit
+scalars, as tools/run_msm.py.  Every figure is synchronised (the calls return after their device work and the copies of their
+results to the host) and taken warm; the median of `reps` runs is reported, the largest shape fewer times."""
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
+import plonky2_bn254_amd as pk
+from tools import synth
+
+reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+SIZES = (128, 16384, 1 << 20)
+ctx = pk.Context(0)
+rng = np.random.default_rng(7)
+_, base_x, base_r = synth.g1_inputs(4096, seed=0x6D736D)
+P_WORDS = np.array(synth._to_words(synth.P), np.uint64)
+
+
+def xs_below_p(n):
+    """n x 4 words, uniform below p: 256-bit values with the top word reduced below p's top word."""
+    x = rng.integers(0, 2**63, size=(n, 4), dtype=np.uint64) * 2 + rng.integers(0, 2, size=(n, 4), dtype=np.uint64)
+    x[:, 3] %= P_WORDS[3]
+    return x
+
+
+def chain_jobs(n):
+    s = rng.integers(0, 2**63, size=(n, 4), dtype=np.uint64) * 2 + rng.integers(0, 2, size=(n, 4), dtype=np.uint64)
+    return s, np.tile(base_x, ((n + 4095) // 4096, 1))[:n].copy(), np.ascontiguousarray(base_r[0])
+
+
+def median_ms(fn, k):
+    fn()  # warm: buffers, code objects
+    ts = []
+    for _ in range(k):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts), min(ts), max(ts)
+
+
+front = {}
+print("front-end only (bn254s_g1_recover_from_x_batch: g = x^3 + 3, g^((p+1)/4), flags, points, jobs), ms", flush=True)
+for n in SIZES:
+    xs = xs_below_p(n)
+    med, lo, hi = median_ms(lambda: ctx.g1_recover_from_x_batch(xs), reps if n < (1 << 20) else 3)
+    front[n] = med
+    _, flags, _ = ctx.g1_recover_from_x_batch(xs)
+    print(f"  n = {n:8d}: {med:9.2f} ms  (min {lo:.2f}, max {hi:.2f}; {n / med * 1e3:,.0f} inputs/s; {int(flags.sum())} recoverable)",
+          flush=True)
+
+print("chain only (bn254s_g1_msm_chain) at the same sizes, ms", flush=True)
+for n in SIZES:
+    s, x, R = chain_jobs(n)
+    med, lo, hi = median_ms(lambda: ctx.g1_msm_chain(s, x, R), reps if n < (1 << 20) else 3)
+    print(f"  n = {n:8d}: {med:9.2f} ms  (min {lo:.2f}, max {hi:.2f}): the recover front-end takes {front[n] / med:.2f} of it", flush=True)
+
+print("g1_recover_from_x (front-end + Fq-exp proofs + linkage check) vs prove_batch of the same jobs, ms", flush=True)
+n, per_proof = 16384, 128
+xs = xs_below_p(n)
+_, _, jobs = ctx.g1_recover_from_x_batch(xs)
+js, jx = np.ascontiguousarray(jobs[:, :4]), np.ascontiguousarray(jobs[:, 4:])
+r_med, r_lo, _ = median_ms(lambda: ctx.g1_recover_from_x(xs, per_proof=per_proof), 2)
+b_med, b_lo, _ = median_ms(lambda: ctx.prove_batch(2, js, jx, None, per_proof=per_proof), 2)
+print(f"  n = {n:6d}, per_proof {per_proof:5d}: g1_recover_from_x {r_med:9.1f} ms (min {r_lo:.1f}), prove_batch {b_med:9.1f} ms "
+      f"(min {b_lo:.1f}): the front-end adds {r_med - b_med:+.1f} ms; {n / r_med * 1e3:,.0f} proven recoveries/s", flush=True)
+ms, mhz, mhz_min = ctx.bench_ntt_clock(781 + 456, 5)  # the G1 proof's columns (W + A), as bench.py
+print(f"shader clock right after, under the NTT/LDE stage: {mhz:.0f} MHz mean, {mhz_min:.0f} MHz slowest 10 us", flush=True)
+ctx.close()

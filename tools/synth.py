@@ -367,3 +367,25 @@ def fq_inputs(n: int, seed: int = 0x706C6F6E6B7932 + 5):
         scalars[i] = _to_words(rng.next_u256())
         xs[i] = _to_words(rng.next_u256() % P)
     return scalars, xs
+
+
+# ---- G1 point recovery from x (reference src/fields/recover.rs, src/curves/g1.rs:76-95) ----------------------------------
+def g1_recover_from_x(x: int):
+    """(x, y) with y^2 = x^3 + 3 and y even ("sgn false", recover_from_x), or None when x^3 + 3 is not a square
+    (is_recoverable_from_x).  p = 3 (mod 4): the root of a square g is g^((p+1)/4)."""
+    g = (x * x * x + 3) % P
+    y = pow(g, (P + 1) // 4, P)
+    if y * y % P != g:
+        return None
+    return (x, P - y if y & 1 else y)
+
+
+def g1_recover_inputs(n: int, seed: int):
+    """xs[n,4] for G1 point recovery: the edge cases 0, 1, 2, 4, p - 1, p - 2 and the x of three g1_inputs points first, then
+    uniform values below p."""
+    _, pts, _ = g1_inputs(3, seed)
+    vals = [0, 1, 2, 4, P - 1, P - 2] + [words_to_int(p[:4]) for p in pts]
+    rng = Xoshiro256ss(seed)
+    while len(vals) < n:
+        vals.append(rng.next_u256() % P)
+    return np.array([_to_words(v) for v in vals[:n]], dtype=np.uint64).reshape(-1, 4)
