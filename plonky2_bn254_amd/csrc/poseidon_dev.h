@@ -161,7 +161,8 @@ __device__ __forceinline__ void poseidon_permute_plain(u64 s[12]) {
 // BN254S_POSEIDON_PLAIN (compile time) selects the compiler's code everywhere (A/B measurements, tools/ubench).
 #include "poseidon_asm.inc"
 #endif
-static __constant__ __attribute__((aligned(64))) u32 POSEIDON_INIT_DEV[31 * 48] = {
+// 30 rounds, the padding row of the prefetch, and the last round's row of the sponge statement (round 0's constants of lanes 8..11)
+static __constant__ __attribute__((aligned(64))) u32 POSEIDON_INIT_DEV[32 * 48] = {
 #include "poseidon_init.inc"
 };
 // records of the merged partial-round blocks (three rounds per linear layer, tools/gen_poseidon_asm.py: block_tables)

@@ -19,12 +19,16 @@ script emits the permutation as ONE inline-asm statement with its own register a
 
 Two statements are generated from the same round code: POSEIDON_ASM_PERMUTE (one permutation of twelve 64-bit operands, round
 0's constants already added) and POSEIDON_ASM_SPONGE (the whole hash_no_pad loop of the Merkle leaf kernel: loads of the
-next eight columns, round 0's constants, permutation; the state never leaves the register block).
+next eight columns, round 0's constants, permutation; the state never leaves the register block).  hash_no_pad overwrites
+lanes 0..7 with the next chunk and reads lanes 0..3 at the end, so the sponge statement's last MDS layer computes, folds and
+range-checks only the four lanes that are read (8..11 before a full chunk, 0..3 after the last chunk, all twelve before a ragged
+chunk, which keeps some of lanes 0..7), and starts lanes 8..11 from round 0's constants of the next permutation.
 
 The instruction lists are first executed by the interpreter below (one lane, Python integers) on the known-answer vectors
 and random inputs and compared with the textbook permutation; then printed.
 usage: python tools/gen_poseidon_asm.py [out_dir = plonky2_bn254_amd/csrc]
 """
+import multiprocessing
 import os
 import random
 import sys
@@ -61,12 +65,14 @@ S_PTR = 96         # s[96:97]: running pointer into the table
 S_CNT = 98
 S_HALF = 99
 ROUND_BYTES = 192
+CARRY_ROW_BYTES = 2 * ROUND_BYTES    # from INIT[29] to the row after the padding: zero, but round 0's constants in lanes 8..11
 
 
 def init_table(rc):
     """INIT[r][j]: what the MDS layer of round r adds to output j = the constants of round r's own partial-round lanes pushed
     through the layer + the pre-S-box constant of round r + 1 (all 12 lanes before a full round, lane 0 before a partial
-    one).  Round 0's own pre-S-box constants are added up front.  One extra all-zero round pads the prefetch."""
+    one).  Round 0's own pre-S-box constants are added up front.  One extra all-zero round pads the prefetch; the row after it
+    is INIT[29] with round 0's constants of lanes 8..11, which the sponge carries into its next permutation."""
     full = lambda r: r < 4 or r >= 26
     tab = []
     for r in range(30):
@@ -81,6 +87,7 @@ def init_table(rc):
             row.append(k % P)
         tab.append(row)
     tab.append([0] * 12)
+    tab.append([0] * 8 + [rc[j] for j in range(8, 12)])     # INIT[29] before another chunk of the sponge (full_round: trim)
     return tab
 
 
@@ -278,8 +285,16 @@ def prefetch_next(p):
 EXPERIMENT = os.environ.get("POSEIDON_GEN_EXPERIMENT", "")     # timing experiments only (tools/ubench): wrong results
 
 
-def full_round(p):
-    """A -> S-boxes -> S -> MDS -> A."""
+def mds_tail(p, g):
+    """Round 29's layer for output group g alone (the sponge statement: the only group the next absorb or the digest reads)."""
+    interleave(p, mds_group_tasks(S, g, False))
+    fold_group(p, A, g)
+    p.emit("poison", [i for i in range(12) if i // 4 != g])
+
+
+def full_round(p, trim=None):
+    """A -> S-boxes -> S -> MDS -> A.  trim (sponge statement): the labels of round 29's short tails, (next chunk full, final
+    chunk): an overwrite sponge reads lanes 8..11 only before a full chunk and lanes 0..3 only after the last one."""
     rezero_stream_temps(p, range(N_STREAMS))
     if "nosbox" not in EXPERIMENT:
         for k in range(0, 12, N_STREAMS):
@@ -288,6 +303,16 @@ def full_round(p):
     if "nomds" in EXPERIMENT:
         prefetch_next(p)
         return
+    if trim:
+        carry, final, every = trim
+        p.emit("s_branch_if_ne", S_HALF, 1, every)
+        p.emit("s_branch_if_ne", S_CNT, 1, every)
+        p.emit("s_branch_if_idx_ge_len", 8, final)             # the last chunk: the digest
+        # a chunk follows: outputs 8..11 start from round 0's constants of the lanes it carries over (INIT[29] itself is zero)
+        p.emit("s_load16", SB_CONST + 32, CARRY_ROW_BYTES + 128)
+        p.emit("s_waitcnt")
+        p.emit("s_branch_if_idx_le_len", 16, carry)            # a full chunk: it overwrites lanes 0..7
+        p.emit("label", every)                                 # a ragged chunk keeps lanes rem..7: all twelve outputs
     for g in range(3):
         interleave(p, mds_group_tasks(S, g, False))
         if g == 2:
@@ -502,15 +527,17 @@ def partial_block(p, src, dst, ratio=2):
     p.emit("s_add_blk", BLK_BYTES)
 
 
-def permutation_body(p, tag=""):
-    """30 rounds on bank A (round 0's constants already added); the table pointer S_PTR must point at INIT[0]."""
+def permutation_body(p, tag="", trim=False):
+    """30 rounds on bank A (round 0's constants already added); the table pointer S_PTR must point at INIT[0].
+    trim: the last round computes only the outputs the sponge reads (full_round) and leaves lanes 8..11 with round 0's
+    constants added whenever another chunk follows."""
     p.emit("s_mov", S_HALF, 0)
     for k in range(3):
         p.emit("s_load16", SB_CONST + 16 * k, 64 * k)
     p.emit("label", "half" + tag)
     p.emit("s_mov", S_CNT, 4)
     p.emit("label", "full" + tag)
-    full_round(p)
+    full_round(p, ("carry" + tag, "final" + tag, "every" + tag) if trim else None)
     p.emit("loop", S_CNT, "full" + tag)
     p.emit("s_branch_if_ne0", S_HALF, "done" + tag)
     rezero_stream_temps(p, [N_STREAMS - 1])
@@ -536,6 +563,12 @@ def permutation_body(p, tag=""):
         p.emit("loop", S_CNT, "part" + tag)
     p.emit("s_mov", S_HALF, 1)
     p.emit("s_branch", "half" + tag)
+    if trim:
+        p.emit("label", "carry" + tag)
+        mds_tail(p, 2)
+        p.emit("s_branch", "done" + tag)
+        p.emit("label", "final" + tag)
+        mds_tail(p, 0)
     p.emit("label", "done" + tag)
     p.emit("s_waitcnt")                    # the last prefetch (padding round) must land before the registers are reused
 
@@ -573,30 +606,42 @@ def build_sponge(store=False):
     """hash_no_pad over leaf_len elements (leaf_len > 0) from the all-zero state: per chunk of <= 8 elements overwrite lanes
     0.., add round 0's constants (lazily: any representative), permute.  The loads of chunk c + 1 are issued before the
     permutation of chunk c into staging registers; the input of every permutation is parked in LDS for the (rare) exact
-    repeat."""
+    repeat.  Lanes 8..11 never see an addition of their round-0 constants: the first chunk starts them from the constants, and
+    the last layer of every permutation that another chunk follows starts their digit sums from them (permutation_body: trim)."""
     p = Prog()
-    p.emit("zero_in")
+    p.emit("zero_in", 8)
     p.emit("sponge_init")                  # s[24:25] = column pointer, s[26:27] = stride, s28 = 0, s29 = leaf_len
     p.emit("s_rem")
     for i in range(8):
         p.emit("gload", vp(LD0 + 2 * i), i, 0)     # if (i < len) LD[i] = *(col + lane offset); col += stride
+    p.emit("s_ptr", "rc")
+    p.emit("s_load8", SB_CONST + 16, 64)
+    p.emit("s_waitcnt")
+    for i in range(8, 12):
+        p.emit("mov64", vp(A[i][0]), sp(SB_CONST + 2 * i))
     p.emit("label", "chunk")
+    p.emit("s_ptr", "rc")
+    for k in range(2):
+        p.emit("s_load8", SB_CONST + 8 * k, 32 * k)
     p.emit("s_rem")                        # S_CNT = len - idx
     p.emit("s_waitcnt_all")
+    # s = a + rc, a = the staged load of a lane the chunk overwrites (a full chunk: all eight, no test per lane), the lane itself
+    # where a ragged chunk keeps it
+    p.emit("s_branch_if_lt", S_CNT, 8, "ragged")
+    for i in range(8):
+        p.emit("add64", vp(A[i][0]), vp(LD0 + 2 * i), sp(SB_CONST + 2 * i))
+    p.emit("s_branch", "staged")
+    p.emit("label", "ragged")
     for i in range(8):
         p.emit("take", vp(A[i][0]), vp(LD0 + 2 * i), i)   # if (idx + i < len) A[i] = LD[i]
     for i in range(8):
+        p.emit("add64", vp(A[i][0]), vp(A[i][0]), sp(SB_CONST + 2 * i))
+    p.emit("label", "staged")
+    for i in range(8):
         p.emit("gload", vp(LD0 + 2 * i), i, 8)     # if (idx + 8 + i < len) LD[i] = next element
-    p.emit("s_ptr", "rc")
-    for k in range(3):
-        p.emit("s_load8", SB_CONST + 8 * k, 32 * k)
     p.emit("e_zero")
-    p.emit("s_waitcnt")
-    # lazy addition of round 0's constants: s = a + rc; wrapped iff s < rc; then + (2^32 - 1)
-    for base in range(0, 12, 2):
-        for k in (0, 1):
-            i = base + k
-            p.emit("add64", vp(A[i][0]), vp(A[i][0]), sp(SB_CONST + 2 * i))
+    # lazy addition of round 0's constants: s wrapped iff s < rc; then + (2^32 - 1)
+    for base in range(0, 8, 2):
         for k in (0, 1):
             i = base + k
             p.emit("cmplt64", sp(SB_CARRY + 2 * k), vp(A[i][0]), sp(SB_CONST + 2 * i))
@@ -611,13 +656,13 @@ def build_sponge(store=False):
     p.emit("s_ptr", "tab")
     p.emit("s_ptr_blk")
     MODE["fast"] = True
-    permutation_body(p)
+    permutation_body(p, trim=True)
     p.emit("flagcheck", "next")
     p.emit("lds_restore")
     p.emit("e_zero")
     p.emit("s_ptr", "tab")
     MODE["fast"] = False
-    permutation_body(p, tag="x")
+    permutation_body(p, tag="x", trim=True)
     MODE["fast"] = True
     p.emit("label", "next")
     p.emit("chunk_loop", "chunk")          # idx += 8; if (idx < len) goto chunk
@@ -647,7 +692,10 @@ def pad_hazards(ins):
     last_write = {}
     n = 0
     for t in ins:
-        if t[0] in ("label", "loop", "s_branch", "s_branch_if_ne0", "chunk_loop", "flagcheck"):
+        if t[0] == "poison":         # (an annotation for the interpreter, no instruction)
+            out.append(t)
+            continue
+        if t[0] in ("label", "loop", "s_branch", "s_branch_if_ne0", "chunk_loop", "flagcheck") or t[0].startswith("s_branch_if_"):
             last_write.clear()       # nothing is assumed across control flow: every target starts with instructions that
             #                          read no VALU-written SGPR within two slots (checked by assert_targets_safe)
         if t[0] in VALU:
@@ -691,6 +739,8 @@ class Machine:
         if isinstance(a, int):
             return a & M64 if a >= 0 else a & M32     # inline constants: -1 is 0xFFFFFFFF as a 32-bit source
         k, i = a
+        if k in ("v", "vp"):
+            assert i in self.v and (k == "v" or i + 1 in self.v), "read of an undefined register: v%d" % i
         if k == "v":
             return self.v[i]
         if k == "vp":
@@ -715,7 +765,9 @@ class Machine:
 
 def run(ins, mem, state, leaf=None, stats=None):
     """mem: {"tab": dwords, "rc": dwords}; state: 12 lanes copied in; leaf: the lane's elements (sponge statement);
-    stats: counts the flag checks and exact repeats ("force": always repeat)."""
+    stats: counts the flag checks and exact repeats ("force": always repeat; "force_at": repeat at these flag checks, counted
+    from 0) and, with "ops", the executed instructions per opcode and the vector-ALU instructions among them ("valu").
+    Lanes of bank A that a trimmed last round did not compute are undefined: reading one asserts, and they come back as None."""
     stats = {} if stats is None else stats
     saved = None
     m = Machine()
@@ -731,14 +783,40 @@ def run(ins, mem, state, leaf=None, stats=None):
         steps += 1
         if "ops" in stats:
             stats["ops"][op] = stats["ops"].get(op, 0) + 1
-        if op == "copy_in":
+            n_valu = PSEUDO_VALU.get(op, 1 if op in UNIT else 0)
+            if op == "take" and not m.s[S_CNT] > t[3]:
+                n_valu = 0
+            stats["valu"] = stats.get("valu", 0) + n_valu
+        if op == "mad":          # (the most frequent ones first: the chain is the interpreter's inner loop)
+            _, d, c, x, y, z = t
+            a, b = m.rd(x), m.rd(y)
+            assert a <= M32 and b <= M32
+            r = a * b + (m.rd(z) if z != 0 else 0)
+            m.wr(d, r & M64)
+            assert (r >> 64) <= 1
+            if c != "vcc":
+                m.wr(c, r >> 64)      # the lane's bit of the carry mask
+            else:
+                assert r >> 64 == 0, "carry into the scratch destination would be lost"
+        elif op in ("mov", "mov64"):
+            m.wr(t[1], m.rd(t[2]))
+        elif op == "cnd":
+            m.wr(t[1], m.rd(t[3]) if m.rd(t[4]) & 1 else m.rd(t[2]))
+        elif op == "add64":
+            m.wr(t[1], (m.rd(t[2]) + m.rd(t[3])) & M64)
+        elif op == "subbco":
+            a, b, c = m.rd(t[3]), m.rd(t[4]), m.rd(t[5]) & 1
+            m.wr(t[1], (a - b - c) & M32)
+            m.wr(t[2], 1 if a < b + c else 0)
+        elif op == "copy_in":
             for i, x in enumerate(state):
                 m.wr(vp(A[i][0]), x)
         elif op == "e_zero":
             m.v[E0 + 1] = m.v[E0 + 3] = 0
         elif op == "flagcheck":
+            forced = stats.get("force") or stats.get("checks", 0) in stats.get("force_at", ())
             stats["checks"] = stats.get("checks", 0) + 1
-            if not (m.v[MN_A] < 1024 or m.v[MX_A] > 0xFFFFFBFF or (m.s[S_FLAG] | m.s[S_FLAG + 1]) != 0 or stats.get("force")):
+            if not (m.v[MN_A] < 1024 or m.v[MX_A] > 0xFFFFFBFF or (m.s[S_FLAG] | m.s[S_FLAG + 1]) != 0 or forced):
                 pc = labels[t[1]]
             else:
                 stats["repeats"] = stats.get("repeats", 0) + 1
@@ -750,8 +828,12 @@ def run(ins, mem, state, leaf=None, stats=None):
         elif op == "copy_out":
             break
         elif op == "zero_in":
-            for i in range(12):
+            for i in range(t[1]):
                 m.wr(vp(A[i][0]), 0)
+        elif op == "poison":
+            for i in t[1]:
+                m.v.pop(A[i][0], None)
+                m.v.pop(A[i][1], None)
         elif op in ("digest_out", "digest_store"):
             break
         elif op == "sponge_init":
@@ -769,17 +851,6 @@ def run(ins, mem, state, leaf=None, stats=None):
             m.s[SB_LOOP + 4] += 8
             if m.s[SB_LOOP + 4] < m.s[SB_LOOP + 5]:
                 pc = labels[t[1]]
-        elif op == "mad":
-            _, d, c, x, y, z = t
-            a, b = m.rd(x), m.rd(y)
-            assert a <= M32 and b <= M32
-            r = a * b + (m.rd(z) if z != 0 else 0)
-            m.wr(d, r & M64)
-            assert (r >> 64) <= 1
-            if c != "vcc":
-                m.wr(c, r >> 64)      # the lane's bit of the carry mask
-            else:
-                assert r >> 64 == 0, "carry into the scratch destination would be lost"
         elif op == "addco":
             r = m.rd(t[3]) + m.rd(t[4])
             m.wr(t[1], r & M32)
@@ -788,10 +859,6 @@ def run(ins, mem, state, leaf=None, stats=None):
             a, b = m.rd(t[3]), m.rd(t[4])
             m.wr(t[1], (a - b) & M32)
             m.wr(t[2], 1 if a < b else 0)
-        elif op == "subbco":
-            a, b, c = m.rd(t[3]), m.rd(t[4]), m.rd(t[5]) & 1
-            m.wr(t[1], (a - b - c) & M32)
-            m.wr(t[2], 1 if a < b + c else 0)
         elif op == "s_xor":
             m.wr(t[1], m.rd(t[2]) ^ m.rd(t[3]))
         elif op == "s_and":
@@ -800,10 +867,6 @@ def run(ins, mem, state, leaf=None, stats=None):
             m.wr(t[1], m.rd(t[2]) | m.rd(t[3]))
         elif op == "cmplt64":
             m.wr(t[1], 1 if m.rd(t[2]) < m.rd(t[3]) else 0)
-        elif op in ("mov", "mov64"):
-            m.wr(t[1], m.rd(t[2]))
-        elif op == "cnd":
-            m.wr(t[1], m.rd(t[3]) if m.rd(t[4]) & 1 else m.rd(t[2]))
         elif op == "sub":
             m.wr(t[1], (m.rd(t[2]) - m.rd(t[3])) & M32)
         elif op == "add3":
@@ -814,8 +877,6 @@ def run(ins, mem, state, leaf=None, stats=None):
             m.wr(t[1], min(m.rd(t[2]), m.rd(t[3]), m.rd(t[4])))
         elif op == "max3":
             m.wr(t[1], max(m.rd(t[2]), m.rd(t[3]), m.rd(t[4])))
-        elif op == "add64":
-            m.wr(t[1], (m.rd(t[2]) + m.rd(t[3])) & M64)
         elif op == "s_mov":
             m.s[t[1]] = t[2]
         elif op == "s_ptr":
@@ -850,9 +911,19 @@ def run(ins, mem, state, leaf=None, stats=None):
         elif op == "s_branch_if_ne0":
             if m.s[t[1]] != 0:
                 pc = labels[t[2]]
+        elif op == "s_branch_if_ne":
+            if m.s[t[1]] != t[2]:
+                pc = labels[t[3]]
+        elif op == "s_branch_if_lt":
+            if m.s[t[1]] < t[2]:
+                pc = labels[t[3]]
+        elif op in ("s_branch_if_idx_ge_len", "s_branch_if_idx_le_len"):
+            m.s[SB_CARRY] = m.s[SB_LOOP + 4] + t[1]
+            if (m.s[SB_CARRY] >= m.s[SB_LOOP + 5]) if op == "s_branch_if_idx_ge_len" else (m.s[SB_CARRY] <= m.s[SB_LOOP + 5]):
+                pc = labels[t[2]]
         else:
             raise ValueError(op)
-    out = [m.rd(vp(A[i][0])) for i in range(12)]
+    out = [m.rd(vp(A[i][0])) if A[i][0] in m.v and A[i][1] in m.v else None for i in range(12)]
     return out, False, steps
 
 
@@ -899,8 +970,10 @@ def text(ins):
             L.append("s_mov_b32 s%d, 0" % (SB_LOOP + 4))
             L.append("s_mov_b32 s%d, %%[len]" % (SB_LOOP + 5))
         elif op == "zero_in":
-            for i in range(12):
+            for i in range(t[1]):
                 L.append("v_mov_b64 v[%d:%d], 0" % (A[i][0], A[i][1]))
+        elif op == "poison":
+            pass
         elif op == "digest_out":
             for i in range(4):
                 L.append("v_mov_b64 %%[o%d], v[%d:%d]" % (i, A[i][0], A[i][1]))
@@ -1009,6 +1082,13 @@ def text(ins):
         elif op == "s_branch_if_ne0":
             L.append("s_cmp_lg_u32 s%d, 0" % t[1])
             L.append("s_cbranch_scc1 Lpos_%s_%%=" % t[2])
+        elif op in ("s_branch_if_ne", "s_branch_if_lt"):
+            L.append("s_cmp_%s_u32 s%d, %d" % (op[-2:].replace("ne", "lg"), t[1], t[2]))
+            L.append("s_cbranch_scc1 Lpos_%s_%%=" % t[3])
+        elif op in ("s_branch_if_idx_ge_len", "s_branch_if_idx_le_len"):     # element index + k against the leaf length
+            L.append("s_add_u32 s%d, s%d, %d" % (SB_CARRY, SB_LOOP + 4, t[1]))
+            L.append("s_cmp_%s_u32 s%d, s%d" % (op[-6:-4], SB_CARRY, SB_LOOP + 5))
+            L.append("s_cbranch_scc1 Lpos_%s_%%=" % t[2])
         else:
             raise ValueError(op)
     return L
@@ -1020,6 +1100,8 @@ HALF = {"mov64": 4.15, "mad": 4.15, "cnd": 4.15, "add64": 4.15, "addco": 4.15, "
         "min3": 4.15, "max3": 4.15}
 FULL = {"mov": 2.1, "sub": 2.1, "min": 2.1}
 UNIT = dict(HALF, **FULL)
+# vector-ALU instructions behind the interpreter's compound operations (text()); "take" counts when its move runs
+PSEUDO_VALU = {"copy_in": 12, "copy_out": 12, "e_zero": 2, "flagcheck": 2, "zero_in": 8, "take": 1, "digest_out": 4, "digest_store": 16}
 
 
 def dynamic_counts(ins):
@@ -1044,6 +1126,41 @@ def write_macro(f, name, lines):
     for ln in lines:
         f.write('  "%s\\n" \\\n' % ln)
     f.write('  ""\n')
+
+
+def full_rate_share():
+    """Share of full-rate instructions (v_mov_b32, v_sub_u32) among the VALU instructions of one fast-code permutation, as
+    main() prints it (tools/make_profiles.py: bench.py weighs the counted instructions with it)."""
+    rc = round_constants()
+    tab = init_table(rc)
+    mem = {"tab": table_dwords(tab), "rc": [w for c in rc[:12] for w in (c & M32, c >> 32)], "blk": block_tables(tab)}
+    st = {"ops": {}}
+    run(pad_hazards(build_permute().ins), mem, [(x + rc[i]) % P for i, x in enumerate(KATS[1][0])], stats=st)
+    valu = sum(n for k, n in st["ops"].items() if k in UNIT)
+    return round(sum(n for k, n in st["ops"].items() if k in FULL) / valu, 4)
+
+
+SPONGE_JOB = {}      # the statements and tables of sponge_job (set by main before the worker processes are forked)
+
+
+def sponge_job(job):
+    """One leaf through the sponge statement in one repeat mode, against the textbook hash_no_pad."""
+    leaf, mode = job
+    sponge, mem, rc = SPONGE_JOB["sponge"], SPONGE_JOB["mem"], SPONGE_JOB["rc"]
+    n, chunks = len(leaf), (len(leaf) + 7) // 8
+    st = [0] * 12
+    for c in range(0, n, 8):
+        st[:len(leaf[c:c + 8])] = leaf[c:c + 8]
+        st = permute(st, rc)
+    stats = dict(mode)
+    got, _, _ = run(sponge, mem, None, leaf, stats=stats)
+    assert got[4:] == [None] * 8, "the final variant computes the digest lanes only"
+    assert [g % P for g in got[:4]] == st[:4], (n, mode)
+    assert stats["checks"] == chunks and stats.get("repeats", 0) >= (chunks if "force" in mode else len(mode)), (n, mode, stats)
+    if n <= 25:
+        got2, _, _ = run(SPONGE_JOB["sponge_store"], mem, None, leaf, stats=dict(mode))
+        assert got2 == got, (n, mode)
+    return 1
 
 
 def main():
@@ -1084,17 +1201,26 @@ def main():
             st = [rnd.choice([0, 1, P - 1, (1 << 32) - 1, 1 << 32, rnd.randrange(1 << 16)]) for _ in range(12)]
         b, steps = check(st)
         n_bad += b
-    # sponge: hash_no_pad of ragged leaves from non-canonical-looking state words
-    for n in (1, 5, 8, 9, 16, 21):
-        leaf = [rnd.randrange(P) if rnd.random() < 0.7 else rnd.choice([0, P - 1, 1]) for _ in range(n)]
-        got, bad, _ = run(sponge, mem, None, leaf, stats={"force": n % 2})
-        got2, _, _ = run(sponge_store, mem, None, leaf, stats={"force": n % 2})
-        assert got2 == got
-        st = [0] * 12
-        for c in range(0, n, 8):
-            st[:len(leaf[c:c + 8])] = leaf[c:c + 8]
-            st = permute(st, rc)
-        assert [g % P for g in got[:4]] == st[:4], n
+    # sponge: hash_no_pad of every leaf length around the chunk boundaries and of the two headline widths, each with the fast
+    # code alone, with the exact repeat forced on every chunk and with it forced on exactly one chunk: the first, a middle one,
+    # the one before a ragged chunk, the one before the last, the last (every class of chunk the last round tells apart)
+    assert sponge[:-1] == sponge_store[:-1] and sponge[-1] == ("digest_out",) and sponge_store[-1] == ("digest_store",)
+    jobs = []
+    for n in list(range(1, 26)) + [456, 781]:
+        leaf = [rnd.randrange(P) if rnd.random() < 0.7 else rnd.choice([0, 1, P - 1, (1 << 32) - 1, 1 << 32]) for _ in range(n)]
+        chunks = (n + 7) // 8
+        single = sorted({0, chunks // 2, max(chunks - 2, 0), chunks - 1})
+        jobs += [(leaf, mode) for mode in [{}, {"force": 1}] + [{"force_at": (c,)} for c in single]]
+    SPONGE_JOB.update(sponge=sponge, sponge_store=sponge_store, mem=mem, rc=rc)
+    with multiprocessing.get_context("fork").Pool(min(8, os.cpu_count() or 1)) as pool:
+        n_runs = sum(pool.map(sponge_job, sorted(jobs, key=lambda j: -len(j[0])), chunksize=1))
+    sponge_valu = {}
+    for n in (781, 456):
+        leaf = [rnd.randrange(P) for _ in range(n)]
+        st_n = {"ops": {}}
+        run(sponge_store, mem, None, leaf, stats=st_n)
+        assert not st_n.get("repeats")
+        sponge_valu[n] = (st_n["valu"], st_n["checks"])
     st1 = {"ops": {}}
     run(perm, mem, [(x + rc[i]) % P for i, x in enumerate(KATS[1][0])], stats=st1)
     valu = sum(n for k, n in st1["ops"].items() if k in UNIT)
@@ -1104,6 +1230,11 @@ def main():
           (steps, stats.get("repeats", 0), stats.get("checks", 0)))
     print("fast code: %d VALU instructions per permutation, %d of them half-rate -> about %.0f cycles per wave and SIMD; "
           "VGPRs v%d..v%d" % (valu, half, cycles, VB, V_END - 1))
+    print("sponge statement ok (%d leaves hashed)" % n_runs)
+    for n, (total, perms) in sponge_valu.items():
+        print("sponge statement, len = %d, fast path: %d VALU instructions per lane in %d permutations = %.1f per permutation" %
+              (n, total, perms, total / perms))
+    print("full-rate share of the fast code's VALU instructions: %.4f" % ((valu - half) / valu))
 
     with open(os.path.join(out_dir, "poseidon_asm.inc"), "w") as f:
         f.write("// Generated by tools/gen_poseidon_asm.py - do not edit.  Hand-scheduled Poseidon-Goldilocks for gfx950; see the\n"
@@ -1126,7 +1257,8 @@ def main():
         f.write("#define POSEIDON_ASM_CLOBBERS " + ", ".join(clob) + "\n")
     with open(os.path.join(out_dir, "poseidon_init.inc"), "w") as f:
         f.write("/* Initial digit sums of the MDS layer of every round (tools/gen_poseidon_asm.py: init_table): per round and output\n"
-                "   lane four dwords (low 32 bits, 0, high 32 bits, 0) of the constant the layer adds; 31 rounds (the last is padding). */\n")
+                "   lane four dwords (low 32 bits, 0, high 32 bits, 0) of the constant the layer adds; 30 rounds, one row of padding, and the\n"
+                "   last round's row of the sponge statement before another chunk (round 0's constants in lanes 8..11). */\n")
         d = mem["tab"]
         for i in range(0, len(d), 8):
             f.write("  " + ", ".join("0x%08xu" % x for x in d[i:i + 8]) + ",\n")

@@ -9,6 +9,9 @@ import re
 import shutil
 import sys
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from gen_poseidon_asm import full_rate_share  # noqa: E402
+
 R = sys.argv[1] if len(sys.argv) > 1 else "r02"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "gpurun_out", "profiles_" + R)
@@ -50,7 +53,7 @@ def main():
     per_perm = valu_per_wave / 98
     alu = {"leaf_hash_valu_wave_insts_per_launch_781x2e17": 2048 * valu_per_wave, "valu_insts_per_permutation": round(per_perm, 1),
            "salu_insts_per_permutation": round(salu_per_wave / 98, 1),
-           "full_rate_share": 0.1323,   # tools/gen_poseidon_asm.py: 1576 of the 11908 instructions are v_mov_b32 / v_sub_u32
+           "full_rate_share": full_rate_share(),   # v_mov_b32 / v_sub_u32 among the fast code's instructions, from the generator
            "valu_peak_wave_insts_per_s": peak, "peak_definition": "1024 SIMDs x 2.4 GHz / %.2f cycles: issue cost of v_mad_u64_u32 (and of "
            "every other half-rate instruction) measured with 8 waves per SIMD, tools/ubench/sgpr_ops.hip" % mad8,
            "source": "profiles/%s_valu_insts.md" % R}
