@@ -294,6 +294,18 @@ int bn254s_poseidon_permute(bn254s_ctx* ctx, uint64_t* states, size_t n);
 /* debug: the hand-written Goldilocks sequences of the NTT kernels (csrc/gl_asm.h) on n operand pairs; out[n][17] =
  * a+b, a-b, b-a, a*b, a*2^{12,24,32,36,48,60,64,1,31}, a*2^-{12,24,1,31} (all mod p) */
 int bn254s_selftest_field(bn254s_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
+/* Debug: one implementation of the Poseidon permutation on `n` 12-word states in place (host buffer).  variant 0: the
+ * hand-scheduled statement (the kernel of bn254s_poseidon_permute), 1: the compiler's code (poseidon_permute_plain), 2: the
+ * cooperative code, 16 lanes per state (poseidon_permute_coop).  Other variants: BN254S_E_INVALID_ARG. */
+int bn254s_selftest_poseidon(bn254s_ctx* ctx, int variant, uint64_t* states, size_t n);
+/* Debug: the leaf-hash kernels on caller data.  data: column-major [ncols][2^log_leaves] (host), digests: 2^log_leaves x 4 words
+ * (host).  kernel 0: what merkle_leaves picks in latency mode (any ncols >= 1: leaves of <= 4 elements are copied); 1: k_leaf_hash
+ * (ncols > 4, at least 256 leaves); 2: k_leaf_hash_coop (ncols > 4, 2^log_leaves * ceil(ncols / 8) <= 65536, the shapes the
+ * latency mode gives it); 3: k_leaf_absorb, fed chunk_cols columns per call (a positive multiple of 8; ncols > 4) with the sponge
+ * states carried between calls as the streaming prover does.  chunk_cols is ignored by kernels 0..2.  Shapes a kernel never sees
+ * in the prover are not launched: BN254S_E_INVALID_ARG. */
+int bn254s_selftest_leaf_hash(bn254s_ctx* ctx, const uint64_t* data, size_t ncols, int log_leaves, int kernel, int chunk_cols,
+                              uint64_t* digests);
 /* Debug: BN254 Fq inversion as trace generation uses it (ark-ff `inverse()` at add.rs:66,80): x[n][4] canonical little-endian
  * words -> out[n][8] = x^-1 mod p twice, by the divstep inversion of the product path and by Fermat's little theorem. */
 int bn254s_selftest_fq_inv(bn254s_ctx* ctx, const uint64_t* x, size_t n, uint64_t* out);

@@ -426,6 +426,79 @@ int bn254s_selftest_field(bn254s_ctx* c, const uint64_t* a, const uint64_t* b, s
   return BN254S_OK;
 }
 
+// Debug: the compiler's permutation on caller states (the code k_merkle_level<false> runs), one state per lane.
+__global__ __launch_bounds__(256) void k_poseidon_states_plain(u64* st, size_t n) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u64 s[12];
+  for (int k = 0; k < 12; k++) s[k] = st[12 * i + k];
+#if defined(__HIP_DEVICE_COMPILE__)
+  poseidon_permute_plain(s);
+#endif
+  for (int k = 0; k < 12; k++) st[12 * i + k] = s[k];
+}
+// Debug: the cooperative permutation on caller states, 16 lanes per state; like k_merkle_level_coop every lane of every wave
+// runs the permutation, whole 16-lane groups are live or not.
+__global__ __launch_bounds__(256) void k_poseidon_states_coop(u64* st, size_t n) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = t >> 4;
+  const int l = (int)(t & 15);
+  const bool live = i < n;
+  u64 s = (live && l < 12) ? st[12 * i + l] : 0;
+  s = poseidon_permute_coop(s, l);
+  if (live && l < 12) st[12 * i + l] = s;
+}
+
+int bn254s_selftest_poseidon(bn254s_ctx* c, int variant, uint64_t* states, size_t n) {
+  if (!c || !states || variant < 0 || variant > 2) return BN254S_E_INVALID_ARG;
+  if (n == 0) return BN254S_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  u64* d = c->words("pp.states", 12 * n);
+  if (!d) return BN254S_E_OOM;
+  HIP_TRY(c, hipMemcpyAsync(d, states, 96 * n, hipMemcpyHostToDevice, c->stream));
+  if (variant == 0) k_poseidon_states<<<(unsigned)((n + 63) / 64), 64, 0, c->stream>>>(d, n);
+  else if (variant == 1) k_poseidon_states_plain<<<(unsigned)((n + 63) / 64), 64, 0, c->stream>>>(d, n);
+  else k_poseidon_states_coop<<<(unsigned)((16 * n + 255) / 256), 256, 0, c->stream>>>(d, n);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(states, d, 96 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BN254S_OK;
+}
+
+// Debug: the leaf-hash kernels on caller data, through the launchers of merkle.h (see bn254_stark.h for the kernels and shapes).
+int bn254s_selftest_leaf_hash(bn254s_ctx* c, const uint64_t* data, size_t ncols, int log_leaves, int kernel, int chunk_cols,
+                              uint64_t* digests) {
+  if (!c || !data || !digests || ncols == 0 || ncols > 4096 || log_leaves < 0 || log_leaves > 20 || kernel < 0 || kernel > 3)
+    return BN254S_E_INVALID_ARG;
+  const size_t n = (size_t)1 << log_leaves;
+  const size_t chunks = (ncols + 7) / 8;
+  if (kernel == 1 && (ncols <= 4 || n < 256)) return BN254S_E_INVALID_ARG;
+  if (kernel == 2 && (ncols <= 4 || n * chunks > 4 * 16384)) return BN254S_E_INVALID_ARG;
+  if (kernel == 3 && (ncols <= 4 || chunk_cols <= 0 || chunk_cols % 8 != 0)) return BN254S_E_INVALID_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  u64* d = c->words("ls.data", ncols * n);
+  u64* t = c->words("ls.tree", 4 * n);
+  u64* sponge = kernel == 3 ? c->words("ls.sponge", 12 * n) : nullptr;
+  if (!d || !t || (kernel == 3 && !sponge)) return BN254S_E_OOM;
+  HIP_TRY(c, hipMemcpyAsync(d, data, 8 * ncols * n, hipMemcpyHostToDevice, c->stream));
+  if (kernel == 0) {
+    merkle_leaves(d, 1, n, (int)ncols, log_leaves, t, c->stream, MERKLE_LATENCY);
+  } else if (kernel == 1) {
+    merkle_leaves_range(d, 1, n, (int)ncols, 0, n, t, c->stream);
+  } else if (kernel == 2) {
+    merkle_leaves_coop(d, 1, n, (int)ncols, log_leaves, t, c->stream);
+  } else {
+    for (size_t c0 = 0; c0 < ncols; c0 += (size_t)chunk_cols) {
+      const size_t cn = std::min((size_t)chunk_cols, ncols - c0);
+      merkle_absorb(d + c0 * n, n, (int)cn, log_leaves, sponge, c0 == 0, c0 + cn == ncols ? t : nullptr, c->stream);
+    }
+  }
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(digests, t, 32 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BN254S_OK;
+}
+
 // Debug: BN254 Fq inversion on the device, x[n][4] canonical words -> out[n][8] = x^-1 by divsteps (the product's fq_inv) and by
 // Fermat's little theorem (0 -> 0).
 int bn254s_selftest_fq_inv(bn254s_ctx* c, const uint64_t* x, size_t n, uint64_t* out) {

@@ -156,6 +156,12 @@ void merkle_leaves(const u64* data, size_t leaf_stride, size_t elem_stride, int 
   }
 }
 
+// the cooperative leaf kernel on its own (debug entry point: merkle_leaves reaches it only through the process-wide thresholds)
+void merkle_leaves_coop(const u64* data, size_t leaf_stride, size_t elem_stride, int leaf_len, int log_leaves, u64* tree, hipStream_t s) {
+  const size_t n = (size_t)1 << log_leaves;
+  k_leaf_hash_coop<<<(unsigned)((16 * n + 255) / 256), 256, 0, s>>>(data, leaf_stride, elem_stride, leaf_len, n, tree);
+}
+
 // ---- streaming commitment (prover.hip "stream": the LDE of a commitment never exists as a whole) --------------------------------
 // hash_no_pad over the columns of a leaf, a chunk of columns at a time: the sponge states of all leaves stay resident between
 // chunks (state lane l of leaf j at state[l * n_leaves + j]); a chunk brings `ncols` columns (a multiple of the rate 8, except for

@@ -89,6 +89,8 @@ def load_library():
     lib.bn254s_bench_issue.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.bn254s_poseidon_permute.argtypes = [vp, vp, C.c_size_t]
     lib.bn254s_selftest_field.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    lib.bn254s_selftest_poseidon.argtypes = [vp, C.c_int, vp, C.c_size_t]
+    lib.bn254s_selftest_leaf_hash.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp]
     lib.bn254s_selftest_fq_inv.argtypes = [vp, vp, C.c_size_t, vp]
     lib.bn254s_bench_copy.argtypes = [vp, C.c_size_t, C.c_int]
     lib.bn254s_bench_leafhash.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]
@@ -423,6 +425,25 @@ class Context:
         b = np.ascontiguousarray(b, dtype=np.uint64)
         out = np.zeros((a.shape[0], 17), np.uint64)
         self._check(self._lib.bn254s_selftest_field(self._h, _ptr(a), _ptr(b), a.shape[0], _ptr(out)), "bn254s_selftest_field")
+        return out
+
+    def selftest_poseidon(self, variant: int, states: np.ndarray) -> np.ndarray:
+        """Debug: states[n][12] through one implementation of the permutation: 0 the hand-scheduled statement, 1 the compiler's
+        code, 2 the cooperative code (bn254s_selftest_poseidon)."""
+        st = np.ascontiguousarray(states, dtype=np.uint64).copy()
+        assert st.ndim == 2 and st.shape[1] == 12
+        self._check(self._lib.bn254s_selftest_poseidon(self._h, variant, _ptr(st), st.shape[0]), "bn254s_selftest_poseidon")
+        return st
+
+    def selftest_leaf_hash(self, data: np.ndarray, kernel: int, chunk_cols: int = 0) -> np.ndarray:
+        """Debug: leaf digests [2^k][4] of column-major data[ncols][2^k] by one leaf-hash kernel: 0 what the latency mode picks,
+        1 k_leaf_hash, 2 k_leaf_hash_coop, 3 k_leaf_absorb fed chunk_cols columns per call (bn254s_selftest_leaf_hash)."""
+        data = np.ascontiguousarray(data, dtype=np.uint64)
+        ncols, n = data.shape
+        assert n > 0 and n & (n - 1) == 0, "the number of leaves must be a power of two"
+        out = np.zeros((n, 4), np.uint64)
+        self._check(self._lib.bn254s_selftest_leaf_hash(self._h, _ptr(data), ncols, n.bit_length() - 1, kernel, chunk_cols, _ptr(out)),
+                    "bn254s_selftest_leaf_hash")
         return out
 
     def selftest_fq_inv(self, x: np.ndarray) -> np.ndarray:

@@ -15,7 +15,10 @@ script emits the permutation as ONE inline-asm statement with its own register a
     with carry-out, one select and one 64-bit add;
   * the S-boxes of a full round run three at a time, the S-box of a partial round is interleaved with the 176
     multiply-adds of the layer that do not depend on it;
-  * every value inside the statement is "any representative below 2^64"; nothing is approximate and there is no fall-back.
+  * every value inside the statement is "any representative below 2^64".  The statements run a FAST code first whose short forms
+    (mul_task, fold_group) do not cover every digit pattern; running min / max registers and a sticky scalar flag detect those
+    patterns, and the whole wave then repeats the permutation with the exact code (build_permute, build_sponge), so the result
+    is exact for every input.  tools/gen_poseidon_adversarial.py constructs inputs that truly take those repeats.
 
 Two statements are generated from the same round code: POSEIDON_ASM_PERMUTE (one permutation of twelve 64-bit operands, round
 0's constants already added) and POSEIDON_ASM_SPONGE (the whole hash_no_pad loop of the Merkle leaf kernel: loads of the
@@ -766,7 +769,9 @@ class Machine:
 def run(ins, mem, state, leaf=None, stats=None):
     """mem: {"tab": dwords, "rc": dwords}; state: 12 lanes copied in; leaf: the lane's elements (sponge statement);
     stats: counts the flag checks and exact repeats ("force": always repeat; "force_at": repeat at these flag checks, counted
-    from 0) and, with "ops", the executed instructions per opcode and the vector-ALU instructions among them ("valu").
+    from 0; "never": never repeat, i.e. the fast code alone) and, with "ops", the executed instructions per opcode and the
+    vector-ALU instructions among them ("valu").  It also records "flag_sites", the (flag check, instruction index) of every
+    product that raised the sticky flag, and "fold_in_range", per flag check whether the running min / max stayed in range.
     Lanes of bank A that a trimmed last round did not compute are undefined: reading one asserts, and they come back as None."""
     stats = {} if stats is None else stats
     saved = None
@@ -816,8 +821,10 @@ def run(ins, mem, state, leaf=None, stats=None):
         elif op == "flagcheck":
             forced = stats.get("force") or stats.get("checks", 0) in stats.get("force_at", ())
             stats["checks"] = stats.get("checks", 0) + 1
-            if not (m.v[MN_A] < 1024 or m.v[MX_A] > 0xFFFFFBFF or (m.s[S_FLAG] | m.s[S_FLAG + 1]) != 0 or forced):
-                pc = labels[t[1]]
+            fold_ok = not (m.v[MN_A] < 1024 or m.v[MX_A] > 0xFFFFFBFF)
+            stats.setdefault("fold_in_range", []).append(fold_ok)      # per flag check: were MN_A / MX_A inside their range?
+            if stats.get("never") or not (not fold_ok or (m.s[S_FLAG] | m.s[S_FLAG + 1]) != 0 or forced):
+                pc = labels[t[1]]                                      # ("never": the fast code alone, whatever the flags say)
             else:
                 stats["repeats"] = stats.get("repeats", 0) + 1
         elif op == "lds_save":
@@ -864,6 +871,8 @@ def run(ins, mem, state, leaf=None, stats=None):
         elif op == "s_and":
             m.wr(t[1], m.rd(t[2]) & m.rd(t[3]))
         elif op == "s_or":
+            if t[1] == sp(S_FLAG) and m.rd(t[3]) != 0:     # a product raised the sticky flag: (flag check it counts for, instruction)
+                stats.setdefault("flag_sites", []).append((stats.get("checks", 0), pc - 1))
             m.wr(t[1], m.rd(t[2]) | m.rd(t[3]))
         elif op == "cmplt64":
             m.wr(t[1], 1 if m.rd(t[2]) < m.rd(t[3]) else 0)
