@@ -32,11 +32,12 @@
  * Threading: one call at a time per context (one host thread enters the context at a time); any number of contexts (one per
  * GPU / per host thread).  A batch opened with bn254s_prove_batch_begin stays in flight after _begin returns: until its _end
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
- * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x) queues behind the open batches on the
- * same worker pool and runs on a free slot (stream + workspace) of its own, so it can never share device state with a proof of
- * the open batch; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device front-ends
- * (bn254s_g1_recover_from_x_batch and the front-end half of bn254s_g1_recover_from_x, like those of bn254s_map_to_g2 and the
- * msm chains) use the context's own stream and pooled buffers under keys of their own and are independent of open batches.
+ * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x) queues
+ * behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its own, so it can never share
+ * device state with a proof of the open batch; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
+ * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch and the front-end halves of
+ * bn254s_g1_recover_from_x and bn254s_g2_recover_from_x, like those of bn254s_map_to_g2 and the msm chains) use the context's
+ * own stream and pooled buffers under keys of their own and are independent of open batches.
  */
 #ifndef BN254_STARK_H
 #define BN254_STARK_H
@@ -270,6 +271,32 @@ int bn254s_g1_recover_from_x_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 4,
  * arguments are reported first). */
 int bn254s_g1_recover_from_x(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* xs, size_t n, size_t per_proof,
                              uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs /* may be NULL */,
+                             bn254s_proof** fq_proofs);
+/* G2 point recovery from x: the witness side of G2Target::g_circuit (src/curves/g2.rs:42-54), Fq2Target::is_square
+ * (src/fields/fq2.rs:228-241) and Fq2Target::sqrt_with_sgn (fq2.rs:209-226; sign rule src/fields/sgn.rs:20-27).  For every x_i
+ * (8 words: x.c0, x.c1, each canonical) and wanted sign sgns[i] (0 or 1; sgns == NULL: all 0) the device computes
+ * g_i = x_i^3 + b' in Fq2 (b' = 3/(9+u), the twist coefficient), its norm N_i = g_i.c0^2 + g_i.c1^2 and the root by two
+ * exponentiations with (p+1)/4 and one inversion (csrc/g2_recover.hip):
+ *   flags_out[i]  = 1 iff g_i is a square in Fq2, that is iff N_i is a square in Fq: x_i is the x of a point ON THE TWIST CURVE.
+ *                   Membership in the r-torsion subgroup is NOT checked (the reference's gadgets do not check it either).
+ *                   g_i and N_i are never zero: the twist has odd order, so no point has y = 0;
+ *   points_out[i] = (x_i, y_i) (16 words) with y_i^2 = g_i, both coordinates of y_i below p and sgn(y_i) == sgns[i] (the parity
+ *                   of y.c0, or of y.c1 when y.c0 is zero) where the flag is 1, (x_i, 0) where it is 0;
+ *   fq_jobs[i]    = (p-1)/2 | N_i (8 words; may be NULL): the Fq-exp job whose output is the Legendre symbol of N_i.
+ * A coordinate >= p or an sgns[i] above 1 is BN254S_E_INVALID_ARG, found on the host before any device work and before any
+ * output is written; bn254s_last_error names the first such i.
+ * bn254s_g2_recover_from_x_batch: device front-end only, no proof. */
+int bn254s_g2_recover_from_x_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 8: x.c0, x.c1, each < p */,
+                                   const uint8_t* sgns /* n bytes, 0 or 1; NULL = all 0 */, size_t n,
+                                   uint64_t* points_out /* n x 16 */, uint8_t* flags_out /* n */,
+                                   uint64_t* fq_jobs /* may be NULL: n x 8 = (p-1)/2 | norm(g) */);
+/* The front-end plus the Fq-exp proofs of the n Legendre jobs, cut into ceil(n / per_proof) proofs exactly as
+ * bn254s_prove_batch (kind 2) cuts them.  The outputs of the proofs are checked word for word against the flags: job i must
+ * give 1 where flags_out[i] is 1 and p - 1 where it is 0; a mismatch is BN254S_E_INTERNAL.  On any error every proof of the call
+ * is freed and its slot in fq_proofs is NULL.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work (invalid
+ * arguments are reported first).  points_out is the `x` argument of bn254s_g2_msm as it stands. */
+int bn254s_g2_recover_from_x(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* xs, const uint8_t* sgns, size_t n,
+                             size_t per_proof, uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs /* may be NULL */,
                              bn254s_proof** fq_proofs);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)

@@ -10,30 +10,10 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include "ctx.h"
-#include "fq_dev.h"
-#include "../../include/bn254_stark.h"
-#include "g1_recover_constants.inc"
+#include "recover_host.h"
+#include "sqrt_ladder.h"
 
 namespace {
-
-constexpr size_t G1R_PER_PROOF_MAX = 16384;  // 2^23 rows: the largest Fq-exp proof (bn254s_prove_batch)
-constexpr int G1R_LANES = 64, G1R_ENTRIES = (1 << G1R_WINDOW) - 1;  // g^1 .. g^15 (a zero digit multiplies by nothing)
-
-// g^((p+1)/4) by a fixed-window ladder over the compile-time digits of the exponent: 4 x 62 squarings and one product per non-zero
-// digit, against 256 squarings and 109 products of a bit-at-a-time ladder.  The lane's powers g^1 .. g^15 (150 words: too many to
-// keep in registers beside a product's working set) live in LDS as tab[entry][limb][lane]: a wave's 64 lanes read 64 consecutive
-// words, one per bank, whatever the entry.  A lane only ever reads what it wrote itself: no barrier.
-__device__ __forceinline__ void tab_store(u32 (*tab)[FQ_NL][G1R_LANES], int e, const fq& a) {
-#pragma unroll
-  for (int j = 0; j < FQ_NL; j++) tab[e][j][threadIdx.x] = a.l[j];
-}
-__device__ __forceinline__ fq tab_load(const u32 (*tab)[FQ_NL][G1R_LANES], int e) {
-  fq r;
-#pragma unroll
-  for (int j = 0; j < FQ_NL; j++) r.l[j] = tab[e][j][threadIdx.x];
-  return r;
-}
 
 // points: n x 8 words (x, y); flags: n bytes; jobs: n x 8 words (scalar (p-1)/2 | g)
 __global__ __launch_bounds__(G1R_LANES) void k_g1_recover(const u64* __restrict__ xs, size_t n, u64* __restrict__ points,
@@ -45,20 +25,7 @@ __global__ __launch_bounds__(G1R_LANES) void k_g1_recover(const u64* __restrict_
   const fq x = fq_from_canonical(xs + 4 * k);
   const fq one = fq_one();
   const fq g = fq_add(fq_mul(fq_sqr(x), x), fq_add(fq_dbl(one), one));
-  fq t = g;
-#pragma unroll 1
-  for (int e = 0; e < G1R_ENTRIES; e++) {
-    tab_store(tab, e, t);
-    if (e + 1 < G1R_ENTRIES) t = fq_mul(t, g);
-  }
-  fq c = tab_load(tab, G1R_SQRT_DIGITS[0] - 1);
-#pragma unroll 1
-  for (int i = 1; i < G1R_NDIGITS; i++) {
-#pragma unroll 1
-    for (int s = 0; s < G1R_WINDOW; s++) c = fq_sqr(c);
-    const int d = G1R_SQRT_DIGITS[i];  // the same in every lane; 32-bit entries, so that it is a scalar load
-    if (d) c = fq_mul(c, tab_load(tab, d - 1));
-  }
+  const fq c = sqrt_ladder(tab, g);  // sqrt_ladder.h
   const fq c2 = fq_sqr(c);
   const bool square = fq_eq(c2, g);
   if (!square && !fq_eq(c2, fq_neg(g))) atomicCAS(err, 0, BN254S_E_INTERNAL);  // neither root nor non-residue: the ladder is wrong
@@ -78,15 +45,7 @@ __global__ __launch_bounds__(G1R_LANES) void k_g1_recover(const u64* __restrict_
 // index of the first x_i >= p, or n
 size_t first_unreduced(const uint64_t* xs, size_t n) {
   for (size_t i = 0; i < n; i++) {
-    const uint64_t* w = xs + 4 * i;
-    bool below = false;
-    for (int j = 3; j >= 0; j--) {
-      if (w[j] != G1R_P[j]) {
-        below = w[j] < G1R_P[j];
-        break;
-      }
-    }
-    if (!below) return i;
+    if (!recover_below_p(xs + 4 * i)) return i;
   }
   return n;
 }
@@ -154,44 +113,8 @@ extern "C" int bn254s_g1_recover_from_x(bn254s_ctx* c, const bn254s_params* para
   std::vector<u64> jobs(8 * n);
   int rc = recover_front(c, xs, n, points_out, flags_out, jobs.data());
   if (rc != BN254S_OK) return rc;
-  std::vector<u64> s(4 * n), g(4 * n);
-  for (size_t i = 0; i < n; i++) {
-    memcpy(s.data() + 4 * i, jobs.data() + 8 * i, 32);
-    memcpy(g.data() + 4 * i, jobs.data() + 8 * i + 4, 32);
-  }
-  rc = bn254s_prove_batch(c, 2, params, s.data(), g.data(), nullptr, n, per_proof, fq_proofs);
-  if (rc != BN254S_OK) return rc;  // (the batch has freed its proofs)
-  // linkage: the trace generator computes g_i^((p-1)/2) on its own; it must be 1 where the flag is set and p - 1 where it is not
-  u64 pm1[4];
-  memcpy(pm1, G1R_P, 32);
-  pm1[0] -= 1;
-  static const u64 ONE[4] = {1, 0, 0, 0};
-  size_t pos = 0;
-  for (size_t i = 0; i < n_proofs && rc == BN254S_OK; i++) {
-    const uint64_t* o;
-    size_t len = 0;
-    const size_t cnt = n - pos < per_proof ? n - pos : per_proof;
-    if (bn254s_proof_outputs(fq_proofs[i], &o, &len) != BN254S_OK || len != 4 * cnt) {
-      c->set_err("g1_recover_from_x: proof " + std::to_string(i) + " has " + std::to_string(len / 4) + " outputs, expected " +
-                 std::to_string(cnt));
-      rc = BN254S_E_INTERNAL;
-    }
-    for (size_t j = 0; j < cnt && rc == BN254S_OK; j++) {
-      if (memcmp(o + 4 * j, flags_out[pos + j] ? ONE : pm1, 32) != 0) {
-        c->set_err("g1_recover_from_x: the proven Legendre symbol of input " + std::to_string(pos + j) + " is not " +
-                   (flags_out[pos + j] ? "1, but its flag is set" : "p - 1, but its flag is clear"));
-        rc = BN254S_E_INTERNAL;
-      }
-    }
-    pos += cnt;
-  }
-  if (rc != BN254S_OK) {
-    for (size_t i = 0; i < n_proofs; i++) {
-      bn254s_proof_free(fq_proofs[i]);
-      fq_proofs[i] = nullptr;
-    }
-    return rc;
-  }
+  rc = recover_prove_legendre(c, "g1_recover_from_x", params, jobs, flags_out, n, per_proof, fq_proofs);
+  if (rc != BN254S_OK) return rc;
   if (fq_jobs) memcpy(fq_jobs, jobs.data(), jobs.size() * 8);
   return BN254S_OK;
 }

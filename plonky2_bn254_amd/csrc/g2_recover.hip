@@ -1,0 +1,181 @@
+// G2 point recovery from x on the device: the witness arithmetic of the reference's G2Target::g_circuit (src/curves/g2.rs:42-54),
+// Fq2Target::is_square (src/fields/fq2.rs:228-241) and Fq2Target::sqrt_with_sgn (fq2.rs:209-226; sign rule src/fields/sgn.rs:20-27)
+// around their one STARK job kind:
+//   k_g2_recover: g = x^3 + b' in Fq2, the Legendre job norm(g)^((p-1)/2), the flag "g is a square" and y = sqrt(g) with the
+//                 wanted sign
+//   [n fq_exp proofs of the Legendre symbols]
+// An Fq2 square root in two Fq exponentiations, both with the exponent (p+1)/4 of sqrt_ladder.h (p = 3 mod 4):
+//   1. N = g.c0^2 + g.c1^2, alpha = N^((p+1)/4): alpha^2 == N says that N, and with it g, is a square; alpha^2 == -N that it is none.
+//   2. delta = (alpha + g.c0)/2 satisfies delta (delta - alpha) = -g.c1^2/4.  t = delta^((p+1)/4) has t^2 = +-delta:
+//        t^2 ==  delta: y = (t, g.c1/(2t)),   since (g.c1/(2t))^2 = alpha - delta and t^2 - (alpha - delta) = g.c0;
+//        t^2 == -delta: y = (g.c1/(2t), t),   since (g.c1/(2t))^2 = delta - alpha and (delta - alpha) - t^2 = g.c0.
+//      For g.c1 == 0 delta could vanish (alpha = -g.c0), so delta = g.c0 there: the same two formulas give (t, 0) and (0, t).
+// g is never zero (the twist has odd order: no point with y = 0; equivalently -b' is not a cube in Fq2), and -1 is a non-residue
+// of Fq, so N is never zero either: "N is a square" and "the Legendre symbol of N is 1" agree, and delta, t are never zero.
+#include "recover_host.h"
+#include "sqrt_ladder.h"
+#include "g2_recover_constants.inc"
+
+namespace {
+
+__device__ __forceinline__ fq fq_from_limbs(const u32 (&l)[FQ_NL]) {
+  fq r;
+#pragma unroll
+  for (int j = 0; j < FQ_NL; j++) r.l[j] = l[j];
+  return r;
+}
+// c ? a : b limb by limb (a select of whole structs goes through their addresses, and with them through scratch memory)
+__device__ __forceinline__ fq fq_select(bool c, const fq& a, const fq& b) {
+  const u32 m = 0u - (u32)c;
+  fq r;
+#pragma unroll
+  for (int j = 0; j < FQ_NL; j++) r.l[j] = (a.l[j] & m) | (b.l[j] & ~m);
+  return r;
+}
+// src/fields/sgn.rs:20-27 on canonical words: the parity of c0, or of c1 when c0 is zero
+__device__ __forceinline__ bool sgn_words(const fqw& c0, const fqw& c1) {
+  const bool zero0 = (c0.l[0] | c0.l[1] | c0.l[2] | c0.l[3]) == 0;
+  return (c0.l[0] & 1) || (zero0 && (c1.l[0] & 1));
+}
+
+// xs: n x 8 words (x.c0, x.c1); sgns: n bytes; points: n x 16 words (x, y); flags: n bytes; jobs: n x 8 words ((p-1)/2 | norm(g))
+__global__ __launch_bounds__(G1R_LANES) void k_g2_recover(const u64* __restrict__ xs, const unsigned char* __restrict__ sgns, size_t n,
+                                                          u64* __restrict__ points, unsigned char* __restrict__ flags,
+                                                          u64* __restrict__ jobs, int* __restrict__ err) {
+  __shared__ u32 tab[G1R_ENTRIES][FQ_NL][G1R_LANES];
+  const size_t k = (size_t)blockIdx.x * G1R_LANES + threadIdx.x;
+  if (k >= n) return;
+  const fq2 x = fq2_from_canonical(xs + 8 * k);
+  fq2 b;
+  b.c0 = fq_from_limbs(G2R_B_C0);
+  b.c1 = fq_from_limbs(G2R_B_C1);
+  const fq2 g = fq2_add(fq2_mul(fq2_sqr(x), x), b);
+  const fq nrm = fq2_norm(g);
+  const fq alpha = sqrt_ladder(tab, nrm);
+  const fq a2 = fq_sqr(alpha);
+  const bool square = fq_eq(a2, nrm);
+  bool bad = !square && !fq_eq(a2, fq_neg(nrm));  // neither root nor non-residue: the ladder is wrong
+  // Every lane runs the second ladder, so that a wave stays together: where g is no square it works on delta = 1 (t = 1, an
+  // inverse of 2) and its y is masked below.
+  fq delta = fq_select(fq_is_zero(g.c1), g.c0, fq_mul(fq_add(alpha, g.c0), fq_from_limbs(G2R_HALF)));
+  delta = fq_select(square, delta, fq_one());
+  const fq t = sqrt_ladder(tab, delta);  // overwrites the lane's own table entries: no barrier
+  const fq t2 = fq_sqr(t);
+  const bool plus = fq_eq(t2, delta);
+  bad |= !plus && !fq_eq(t2, fq_neg(delta));
+  const fq o = fq_mul(g.c1, fq_inv(fq_dbl(t)));
+  fq2 y;
+  y.c0 = fq_select(plus, t, o);
+  y.c1 = fq_select(plus, o, t);
+  bad |= square && !fq2_eq(fq2_sqr(y), g);
+  if (bad) atomicCAS(err, 0, BN254S_E_INTERNAL);
+  fqw y0 = fq_to_canonical(y.c0), y1 = fq_to_canonical(y.c1);
+  if (sgn_words(y0, y1) != (sgns[k] != 0)) {  // -y: p - c for a non-zero coordinate, which flips its parity as p is odd
+    y0 = fq_to_canonical(fq_neg(y.c0));
+    y1 = fq_to_canonical(fq_neg(y.c1));
+  }
+  const fqw nc = fq_to_canonical(nrm);
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    points[16 * k + w] = xs[8 * k + w];
+    points[16 * k + 4 + w] = xs[8 * k + 4 + w];
+    points[16 * k + 8 + w] = square ? y0.l[w] : 0;
+    points[16 * k + 12 + w] = square ? y1.l[w] : 0;
+    jobs[8 * k + w] = G1R_LEGENDRE_EXP[w];
+    jobs[8 * k + 4 + w] = nc.l[w];
+  }
+  flags[k] = square ? 1 : 0;
+}
+
+// The first input with a coordinate that is not below p or a sign byte above 1 puts its message into *what; true if all are fine.
+bool inputs_ok(const uint64_t* xs, const uint8_t* sgns, size_t n, std::string* what) {
+  for (size_t i = 0; i < n; i++) {
+    for (int c = 0; c < 2; c++) {
+      if (!recover_below_p(xs + 8 * i + 4 * c)) {
+        *what = "g2_recover_from_x: x_" + std::to_string(i) + " has c" + std::to_string(c) + " not below p";
+        return false;
+      }
+    }
+    if (sgns && sgns[i] > 1) {
+      *what = "g2_recover_from_x: sgn_" + std::to_string(i) + " is " + std::to_string(sgns[i]) + ", neither 0 nor 1";
+      return false;
+    }
+  }
+  return true;
+}
+
+// the arguments that both entry points share, other than the context
+bool recover_args_ok(const uint64_t* xs, size_t n, const uint64_t* points_out, const uint8_t* flags_out) {
+  return xs && points_out && flags_out && n > 0 && n < ((size_t)1 << 32);
+}
+
+// The front-end into host memory: points[n x 16], flags[n], jobs[n x 8] (jobs may be NULL).  Nothing is written on an error.
+int recover_front(bn254s_ctx* c, const uint64_t* xs, const uint8_t* sgns, size_t n, uint64_t* points, uint8_t* flags, uint64_t* jobs) {
+  std::string what;
+  if (!inputs_ok(xs, sgns, n, &what)) {
+    c->set_err(what);
+    return BN254S_E_INVALID_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  const size_t nb = (n + 7) / 8;  // words that hold n bytes
+  u64* d = c->words("g2rec", 8 * n /* xs */ + 16 * n /* points */ + 8 * n /* jobs */ + 1 /* err */ + nb /* flags */ + nb /* sgns */);
+  if (!d) return BN254S_E_OOM;
+  u64* d_xs = d;
+  u64* d_pts = d_xs + 8 * n;
+  u64* d_jobs = d_pts + 16 * n;
+  int* d_err = (int*)(d_jobs + 8 * n);
+  unsigned char* d_flags = (unsigned char*)(d_jobs + 8 * n + 1);
+  unsigned char* d_sgns = d_flags + 8 * nb;
+  HIP_TRY(c, hipMemsetAsync(d_err, 0, 8, st));
+  HIP_TRY(c, hipMemcpyAsync(d_xs, xs, n * 64, hipMemcpyHostToDevice, st));
+  if (sgns)
+    HIP_TRY(c, hipMemcpyAsync(d_sgns, sgns, n, hipMemcpyHostToDevice, st));
+  else
+    HIP_TRY(c, hipMemsetAsync(d_sgns, 0, n, st));
+  k_g2_recover<<<(unsigned)((n + G1R_LANES - 1) / G1R_LANES), G1R_LANES, 0, st>>>(d_xs, d_sgns, n, d_pts, d_flags, d_jobs, d_err);
+  HIP_TRY(c, hipGetLastError());
+  int h_err = 0;
+  HIP_TRY(c, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (h_err) {
+    c->set_err("g2_recover_from_x: a square root does not square back (device self-check)");
+    return h_err;
+  }
+  HIP_TRY(c, hipMemcpyAsync(points, d_pts, n * 128, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(flags, d_flags, n, hipMemcpyDeviceToHost, st));
+  if (jobs) HIP_TRY(c, hipMemcpyAsync(jobs, d_jobs, n * 64, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return BN254S_OK;
+}
+
+}  // namespace
+
+extern "C" int bn254s_g2_recover_from_x_batch(bn254s_ctx* c, const uint64_t* xs, const uint8_t* sgns, size_t n, uint64_t* points_out,
+                                              uint8_t* flags_out, uint64_t* fq_jobs) {
+  if (!c || !recover_args_ok(xs, n, points_out, flags_out)) return BN254S_E_INVALID_ARG;
+  return recover_front(c, xs, sgns, n, points_out, flags_out, fq_jobs);
+}
+
+extern "C" int bn254s_g2_recover_from_x(bn254s_ctx* c, const bn254s_params* params, const uint64_t* xs, const uint8_t* sgns, size_t n,
+                                        size_t per_proof, uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs,
+                                        bn254s_proof** fq_proofs) {
+  // every check before device work; the context last, so that the shape checks can be exercised without one
+  if (!recover_args_ok(xs, n, points_out, flags_out) || !params || !fq_proofs || per_proof == 0 ||
+      params->struct_size != sizeof(bn254s_params))
+    return BN254S_E_INVALID_ARG;
+  const size_t n_proofs = (n + per_proof - 1) / per_proof;
+  for (size_t i = 0; i < n_proofs; i++) fq_proofs[i] = nullptr;
+  if (per_proof > G1R_PER_PROOF_MAX) {
+    if (c) c->set_err("g2_recover_from_x: per_proof above 16384 (2^23 rows, the largest Fq-exp proof)");
+    return BN254S_E_UNSUPPORTED;
+  }
+  if (!c) return BN254S_E_INVALID_ARG;
+  std::vector<u64> jobs(8 * n);
+  int rc = recover_front(c, xs, sgns, n, points_out, flags_out, jobs.data());
+  if (rc != BN254S_OK) return rc;
+  rc = recover_prove_legendre(c, "g2_recover_from_x", params, jobs, flags_out, n, per_proof, fq_proofs);
+  if (rc != BN254S_OK) return rc;
+  if (fq_jobs) memcpy(fq_jobs, jobs.data(), jobs.size() * 8);
+  return BN254S_OK;
+}

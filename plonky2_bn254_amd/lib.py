@@ -81,6 +81,8 @@ def load_library():
     lib.bn254s_g2_msm.argtypes = [vp, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(vp)]
     lib.bn254s_g1_recover_from_x_batch.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     lib.bn254s_g1_recover_from_x.argtypes = [vp, C.POINTER(Params), vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
+    lib.bn254s_g2_recover_from_x_batch.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
+    lib.bn254s_g2_recover_from_x.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
     lib.bn254s_hash_to_fq2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bn254s_ctl_values.argtypes = [C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_commit_values.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
@@ -364,6 +366,43 @@ class Context:
                                                        flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_g1_recover_from_x")
         return pts, flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
 
+    @staticmethod
+    def _sgns(sgns, n):
+        """sgns (None: all 0) as n contiguous bytes, kept as the caller gave them so that the library sees a value above 1."""
+        if sgns is None:
+            return None, None
+        sgns = np.ascontiguousarray(sgns, dtype=np.uint8).reshape(-1)
+        if sgns.shape[0] != n:
+            raise ValueError(f"{sgns.shape[0]} sgns for {n} xs")
+        return sgns, sgns.ctypes.data_as(C.c_void_p)
+
+    def g2_recover_from_x_batch(self, xs, sgns=None):
+        """xs [n,8] (x.c0, x.c1, canonical, below p), sgns [n] in {0, 1} (None: all 0) -> (points [n,16], flags [n] uint8,
+        fq_jobs [n,8]): with g = x_i^3 + b' on the twist, flags[i] = 1 iff g is a square in Fq2, points[i] = (x_i, y_i) with
+        y_i^2 = g and sgn(y_i) == sgns[i] where it is and (x_i, 0) where it is not, fq_jobs[i] = (p-1)/2 | norm(g): the witness
+        side of g_circuit / is_square / sqrt_with_sgn on the device, no proof (bn254s_g2_recover_from_x_batch)."""
+        xs = np.ascontiguousarray(xs, dtype=np.uint64)
+        n = xs.shape[0]
+        sgns, sp = self._sgns(sgns, n)
+        pts, flags, jobs = np.zeros((n, 16), np.uint64), np.zeros(n, np.uint8), np.zeros((n, 8), np.uint64)
+        self._check(self._lib.bn254s_g2_recover_from_x_batch(self._h, _ptr(xs), sp, n, _ptr(pts), flags.ctypes.data_as(C.c_void_p),
+                                                             _ptr(jobs)), "bn254s_g2_recover_from_x_batch")
+        return pts, flags, jobs
+
+    def g2_recover_from_x(self, xs, sgns=None, per_proof=128, params: Optional[Params] = None):
+        """-> (points [n,16], flags [n], fq_jobs [n,8], proofs): the front-end plus the Fq-exp proofs of the n Legendre jobs, cut
+        into ceil(n / per_proof) proofs like prove_batch(2, ...) (bn254s_g2_recover_from_x).  Check it with verify_g2_recover."""
+        params = params or default_params()
+        xs = np.ascontiguousarray(xs, dtype=np.uint64)
+        n = xs.shape[0]
+        sgns, sp = self._sgns(sgns, n)
+        k = (n + per_proof - 1) // per_proof
+        pts, flags, jobs = np.zeros((n, 16), np.uint64), np.zeros(n, np.uint8), np.zeros((n, 8), np.uint64)
+        outs = (C.c_void_p * k)()
+        self._check(self._lib.bn254s_g2_recover_from_x(self._h, C.byref(params), _ptr(xs), sp, n, per_proof, _ptr(pts),
+                                                       flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_g2_recover_from_x")
+        return pts, flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+
     def hash_to_fq2_batch(self, inputs: np.ndarray) -> np.ndarray:
         """inputs [n, len] Goldilocks elements -> u [n, 8]: hash_to_fq2 (hash_to_g2.rs:76-87) of every row, on the device."""
         inputs = np.ascontiguousarray(inputs, dtype=np.uint64)
@@ -614,6 +653,70 @@ def verify_g1_recover(xs, points, flags, fq_jobs, proofs, per_proof, ctx: Option
             if py >= p or py & 1 or py * py % p != g[i]:
                 raise VerifyError(f"{tag}: y of point {i} is not the even root of x_{i}^3 + 3 below p")
         elif py != 0:
+            raise VerifyError(f"{tag}: point {i} is not (x_{i}, 0) although its flag is clear")
+
+
+def verify_g2_recover(xs, sgns, points, flags, fq_jobs, proofs, per_proof, ctx: Optional[Context] = None,
+                      params: Optional[Params] = None):
+    """Checks a g2_recover_from_x: job i is ((p-1)/2, norm(x_i^3 + b')) in Python integer arithmetic (tools/synth.py), every Fq-exp
+    proof verifies against its jobs (Context.verify with a context, else verify_host), the proven Legendre symbol of job i is 1 or
+    p - 1 and agrees with flags[i], and points[i] is (x_i, y_i) with both coordinates of y_i below p, y_i^2 = x_i^3 + b' and
+    sgn(y_i) == sgns[i] (src/fields/sgn.rs:20-27; sgns None: all 0) where the flag is set and (x_i, 0) where it is not.  `proofs`:
+    objects with `words`, `degree_bits` and `outputs`, such as Proof.  Returns None or raises VerifyError naming the first input
+    or proof that fails."""
+    from tools import synth
+
+    tag, p = "g2_recover", synth.P
+    xs, points, fq_jobs = (np.ascontiguousarray(a, dtype=np.uint64) for a in (xs, points, fq_jobs))
+    flags = np.asarray(flags).reshape(-1)
+    n = xs.shape[0]
+    sgns = np.zeros(n, np.uint8) if sgns is None else np.asarray(sgns).reshape(-1)
+    if xs.shape != (n, 8) or points.shape != (n, 16) or fq_jobs.shape != (n, 8) or flags.shape != (n,) or sgns.shape != (n,):
+        raise VerifyError(f"{tag}: shapes: xs {xs.shape}, sgns {sgns.shape}, points {points.shape}, flags {flags.shape}, "
+                          f"fq_jobs {fq_jobs.shape}")
+    if len(proofs) != (n + per_proof - 1) // per_proof:
+        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    g = []
+    for i in range(n):
+        x = (synth.words_to_int(xs[i, :4]), synth.words_to_int(xs[i, 4:]))
+        if x[0] >= p or x[1] >= p:
+            raise VerifyError(f"{tag}: x_{i} is not below p")
+        if int(sgns[i]) not in (0, 1):
+            raise VerifyError(f"{tag}: sign {i} is {int(sgns[i])}, neither 0 nor 1")
+        g.append(synth.g2_rhs(x))
+        if synth.words_to_int(fq_jobs[i, :4]) != (p - 1) // 2:
+            raise VerifyError(f"{tag}: scalar of job {i} != (p - 1)/2")
+        if synth.words_to_int(fq_jobs[i, 4:]) != (g[i][0] * g[i][0] + g[i][1] * g[i][1]) % p:
+            raise VerifyError(f"{tag}: x of job {i} != norm(x_{i}^3 + b')")
+    for k, pr in enumerate(proofs):
+        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
+        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 4)
+        if outs.shape[0] != hi - lo:
+            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+        s_, x_ = np.ascontiguousarray(fq_jobs[lo:hi, :4]), np.ascontiguousarray(fq_jobs[lo:hi, 4:])
+        try:
+            if ctx is not None:
+                ctx.verify(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
+            else:
+                verify_host(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
+        except VerifyError as e:
+            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+        for i in range(lo, hi):
+            leg = synth.words_to_int(outs[i - lo])
+            if leg not in (1, p - 1):
+                raise VerifyError(f"{tag}: output {i} of proof {k} is neither 1 nor p - 1")
+            if (leg == 1) != bool(flags[i]):
+                raise VerifyError(f"{tag}: flag {i} is {int(flags[i])}, the proven Legendre symbol of job {i} is {'1' if leg == 1 else 'p - 1'}")
+    for i in range(n):
+        if not np.array_equal(points[i, :8], xs[i]):
+            raise VerifyError(f"{tag}: point {i} does not carry x_{i}")
+        y = (synth.words_to_int(points[i, 8:12]), synth.words_to_int(points[i, 12:]))
+        if flags[i]:
+            if y[0] >= p or y[1] >= p or synth.f2_mul(y, y) != g[i]:
+                raise VerifyError(f"{tag}: y of point {i} is not a root of x_{i}^3 + b' below p")
+            if synth.f2_sgn(y) != bool(sgns[i]):
+                raise VerifyError(f"{tag}: sign {i} is {int(sgns[i])}, y of point {i} has the other one")
+        elif y != (0, 0):
             raise VerifyError(f"{tag}: point {i} is not (x_{i}, 0) although its flag is clear")
 
 

@@ -2,10 +2,14 @@
 (bn254s_g1_recover_from_x_batch) and the front-end plus the Fq-exp proofs of its Legendre jobs (bn254s_g1_recover_from_x)
 against bn254s_prove_batch of the same jobs; and, in the same process, bn254s_g1_msm_chain at the same sizes: the chain folds
 the points that recovery produces, so it is the yardstick for the front-end.
-usage: python tools/run_recover.py [reps=5]
-Inputs: uniform x below p (about half of them recoverable); for the chain 4096 distinct random points tiled and random 256-bit
-scalars, as tools/run_msm.py.  Every figure is synchronised (the calls return after their device work and the copies of their
-results to the host) and taken warm; the median of `reps` runs is reported, the largest shape fewer times."""
+With --g2 the G2 twin (reference src/curves/g2.rs:42-54, src/fields/fq2.rs:209-241): the front-end times of
+bn254s_g2_recover_from_x_batch beside the G1 ones and beside bn254s_g2_msm_chain at the same sizes, then bn254s_g2_recover_from_x
+against bn254s_prove_batch of its jobs.
+usage: python tools/run_recover.py [--g2] [reps=5]
+Inputs: uniform x below p (about half of them recoverable), for G2 two such coordinates and a random sign; for the chain 4096
+distinct points tiled (G1: random; G2: an arithmetic progression) and random 256-bit scalars, as tools/run_msm.py.  Every figure
+is synchronised (the calls return after their device work and the copies of their results to the host) and taken warm; the
+median of `reps` runs is reported, the largest shape fewer times."""
 import statistics
 import sys
 import time
@@ -16,11 +20,21 @@ sys.path.insert(0, __file__.rsplit("/tools/", 1)[0])
 import plonky2_bn254_amd as pk
 from tools import synth
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+g2 = "--g2" in sys.argv[1:]
+reps = int(args[0]) if args else 5
 SIZES = (128, 16384, 1 << 20)
 ctx = pk.Context(0)
 rng = np.random.default_rng(7)
-_, base_x, base_r = synth.g1_inputs(4096, seed=0x6D736D)
+if g2:
+    step, cur = synth.g2_mul(0x9E3779B9, synth.G2_GEN), synth.g2_mul(0x1234567, synth.G2_GEN)
+    pts = []
+    for _ in range(4096):
+        pts.append(cur)
+        cur = synth.g2_add(cur, step)
+    base_x, base_r = synth.g2_points_to_words(pts), synth.g2_points_to_words([synth.g2_mul(0xC0FFEE, synth.G2_GEN)])
+else:
+    _, base_x, base_r = synth.g1_inputs(4096, seed=0x6D736D)
 P_WORDS = np.array(synth._to_words(synth.P), np.uint64)
 
 
@@ -29,6 +43,11 @@ def xs_below_p(n):
     x = rng.integers(0, 2**63, size=(n, 4), dtype=np.uint64) * 2 + rng.integers(0, 2, size=(n, 4), dtype=np.uint64)
     x[:, 3] %= P_WORDS[3]
     return x
+
+
+def xs2_below_p(n):
+    """n x 8 words (x.c0, x.c1 uniform below p) and n sign bytes."""
+    return np.concatenate([xs_below_p(n), xs_below_p(n)], axis=1), rng.integers(0, 2, size=n, dtype=np.uint8)
 
 
 def chain_jobs(n):
@@ -47,7 +66,7 @@ def median_ms(fn, k):
 
 
 front = {}
-print("front-end only (bn254s_g1_recover_from_x_batch: g = x^3 + 3, g^((p+1)/4), flags, points, jobs), ms", flush=True)
+print("G1 front-end only (bn254s_g1_recover_from_x_batch: g = x^3 + 3, g^((p+1)/4), flags, points, jobs), ms", flush=True)
 for n in SIZES:
     xs = xs_below_p(n)
     med, lo, hi = median_ms(lambda: ctx.g1_recover_from_x_batch(xs), reps if n < (1 << 20) else 3)
@@ -56,20 +75,41 @@ for n in SIZES:
     print(f"  n = {n:8d}: {med:9.2f} ms  (min {lo:.2f}, max {hi:.2f}; {n / med * 1e3:,.0f} inputs/s; {int(flags.sum())} recoverable)",
           flush=True)
 
-print("chain only (bn254s_g1_msm_chain) at the same sizes, ms", flush=True)
+if g2:
+    front2 = {}
+    print("G2 front-end only (bn254s_g2_recover_from_x_batch: g = x^3 + b', two exponentiations, one inversion), ms", flush=True)
+    for n in SIZES:
+        xs, sgns = xs2_below_p(n)
+        med, lo, hi = median_ms(lambda: ctx.g2_recover_from_x_batch(xs, sgns), reps if n < (1 << 20) else 3)
+        front2[n] = med
+        _, flags, _ = ctx.g2_recover_from_x_batch(xs, sgns)
+        print(f"  n = {n:8d}: {med:9.2f} ms  (min {lo:.2f}, max {hi:.2f}; {n / med * 1e3:,.0f} inputs/s; {int(flags.sum())} recoverable): "
+              f"{med / front[n]:.2f} of the G1 front-end", flush=True)
+    front, chain, tag = front2, ctx.g2_msm_chain, "g2"
+else:
+    chain, tag = ctx.g1_msm_chain, "g1"
+
+print(f"chain only (bn254s_{tag}_msm_chain) at the same sizes, ms", flush=True)
 for n in SIZES:
     s, x, R = chain_jobs(n)
-    med, lo, hi = median_ms(lambda: ctx.g1_msm_chain(s, x, R), reps if n < (1 << 20) else 3)
-    print(f"  n = {n:8d}: {med:9.2f} ms  (min {lo:.2f}, max {hi:.2f}): the recover front-end takes {front[n] / med:.2f} of it", flush=True)
+    med, lo, hi = median_ms(lambda: chain(s, x, R), reps if n < (1 << 20) else 3)
+    print(f"  n = {n:8d}: {med:9.2f} ms  (min {lo:.2f}, max {hi:.2f}): the {tag} recover front-end takes {front[n] / med:.2f} of it",
+          flush=True)
 
-print("g1_recover_from_x (front-end + Fq-exp proofs + linkage check) vs prove_batch of the same jobs, ms", flush=True)
+print(f"{tag}_recover_from_x (front-end + Fq-exp proofs + linkage check) vs prove_batch of the same jobs, ms", flush=True)
 n, per_proof = 16384, 128
-xs = xs_below_p(n)
-_, _, jobs = ctx.g1_recover_from_x_batch(xs)
+if g2:
+    xs, sgns = xs2_below_p(n)
+    _, _, jobs = ctx.g2_recover_from_x_batch(xs, sgns)
+    full = lambda: ctx.g2_recover_from_x(xs, sgns, per_proof=per_proof)
+else:
+    xs = xs_below_p(n)
+    _, _, jobs = ctx.g1_recover_from_x_batch(xs)
+    full = lambda: ctx.g1_recover_from_x(xs, per_proof=per_proof)
 js, jx = np.ascontiguousarray(jobs[:, :4]), np.ascontiguousarray(jobs[:, 4:])
-r_med, r_lo, _ = median_ms(lambda: ctx.g1_recover_from_x(xs, per_proof=per_proof), 2)
+r_med, r_lo, _ = median_ms(full, 2)
 b_med, b_lo, _ = median_ms(lambda: ctx.prove_batch(2, js, jx, None, per_proof=per_proof), 2)
-print(f"  n = {n:6d}, per_proof {per_proof:5d}: g1_recover_from_x {r_med:9.1f} ms (min {r_lo:.1f}), prove_batch {b_med:9.1f} ms "
+print(f"  n = {n:6d}, per_proof {per_proof:5d}: {tag}_recover_from_x {r_med:9.1f} ms (min {r_lo:.1f}), prove_batch {b_med:9.1f} ms "
       f"(min {b_lo:.1f}): the front-end adds {r_med - b_med:+.1f} ms; {n / r_med * 1e3:,.0f} proven recoveries/s", flush=True)
 ms, mhz, mhz_min = ctx.bench_ntt_clock(781 + 456, 5)  # the G1 proof's columns (W + A), as bench.py
 print(f"shader clock right after, under the NTT/LDE stage: {mhz:.0f} MHz mean, {mhz_min:.0f} MHz slowest 10 us", flush=True)

@@ -389,3 +389,53 @@ def g1_recover_inputs(n: int, seed: int):
     while len(vals) < n:
         vals.append(rng.next_u256() % P)
     return np.array([_to_words(v) for v in vals[:n]], dtype=np.uint64).reshape(-1, 4)
+
+
+# ---- G2 point recovery from x (reference src/curves/g2.rs:42-54, src/fields/fq2.rs:209-241, src/fields/sgn.rs:20-27) -------
+def g2_rhs(x):
+    """x^3 + b' on the twist (G2Target::g_circuit)."""
+    return f2_add(f2_mul(f2_mul(x, x), x), G2_B)
+
+
+def f2_sgn(a) -> bool:
+    """src/fields/sgn.rs:20-27: parity of c0, or of c1 when c0 = 0."""
+    return bool(a[0] & 1) or (a[0] == 0 and bool(a[1] & 1))
+
+
+def g2_recover_from_x(x, sgn):
+    """(x, y) with y^2 = x^3 + b' in Fq2 and f2_sgn(y) == sgn (sqrt_with_sgn), or None when x^3 + b' is not a square
+    (is_square: the Legendre symbol of its norm).  The root is ark-ff's QuadExtField::sqrt (complex method, in ark's order of
+    cases: tools/map_to_g2_ref.py f2_sqrt), negated when its sign is not the wanted one."""
+    from tools import map_to_g2_ref
+
+    y = map_to_g2_ref.f2_sqrt(g2_rhs(x))
+    if y is None:
+        return None
+    if f2_sgn(y) != bool(sgn):
+        y = ((-y[0]) % P, (-y[1]) % P)
+    return (x, y)
+
+
+def _g2_recover_real_g(c: int):
+    """x = (sqrt((c^3 - b'.c1)/(3c)), c): the imaginary part 3 x0^2 c - c^3 + b'.c1 of x^3 + b' vanishes."""
+    s = (c ** 3 - G2_B[1]) * pow(3 * c, -1, P) % P
+    x0 = pow(s, (P + 1) // 4, P)
+    assert x0 * x0 % P == s, "no such x for this c"
+    return (x0, c)
+
+
+def g2_recover_inputs(n: int, seed: int):
+    """(xs[n,8], sgns[n]) for G2 point recovery: the edge cases (0,0), (1,0), (0,1), (p-1,p-1) with sgn 0, the two x with a real
+    x^3 + b' (c = 2: a square of Fq, root (t, 0); c = 7: a non-square, root (0, t)) with sgn 0 and 1, the x of three g2_inputs
+    points with the sign of their y and again with the opposite sign, then uniform (x, sgn) pairs."""
+    _, pts, _ = g2_inputs(3, seed)
+    known = [g2_from_words(w) for w in pts]
+    cases = [((0, 0), 0), ((1, 0), 0), ((0, 1), 0), ((P - 1, P - 1), 0), (_g2_recover_real_g(2), 0), (_g2_recover_real_g(7), 1)]
+    cases += [(x, int(f2_sgn(y))) for x, y in known] + [(x, 1 - int(f2_sgn(y))) for x, y in known]
+    rng = Xoshiro256ss(seed)
+    while len(cases) < n:
+        x = (rng.next_u256() % P, rng.next_u256() % P)
+        cases.append((x, rng.next_u256() & 1))
+    cases = cases[:n]
+    xs = np.array([_to_words(x[0]) + _to_words(x[1]) for x, _ in cases], dtype=np.uint64).reshape(-1, 8)
+    return xs, np.array([s for _, s in cases], dtype=np.uint8)
