@@ -336,6 +336,25 @@ int bn254s_selftest_leaf_hash(bn254s_ctx* ctx, const uint64_t* data, size_t ncol
 /* Debug: BN254 Fq inversion as trace generation uses it (ark-ff `inverse()` at add.rs:66,80): x[n][4] canonical little-endian
  * words -> out[n][8] = x^-1 mod p twice, by the divstep inversion of the product path and by Fermat's little theorem. */
 int bn254s_selftest_fq_inv(bn254s_ctx* ctx, const uint64_t* x, size_t n, uint64_t* out);
+/* Debug: the BN254 Fq / Fq2 device arithmetic (csrc/fq_dev.h) and the cooperative pieces of the doubling chains
+ * (csrc/chain_coop.h) on RAW register contents, one GPU lane per row.  An operand is four little-endian words of an integer below
+ * p that is loaded as it is (the registers hold Montgomery residues x 2^260 mod p: no conversion is made, the caller chooses the
+ * limbs the multiplier sees); a result is the raw residue, four words, canonical if the code is right.  With Ri = 2^-260 mod p a
+ * product form returns formula * Ri mod p and a linear form formula mod p.  in[n][W_in], out[n][W_out] words by group:
+ *  0 (16 -> 68)  a b c d -> a+b, a-b, -a, 2a, ab, a^2, ab+cd, fq_from_canonical(a) = a 2^260, fq_to_canonical(a) = a Ri, then the
+ *                loose forms (a+b)^2, (3a)^2, (3a)b, (a+b)(c-d+2p), (a+b+c+d)(a+b-c-d+4p), (3a+3b)(3a-3b+6p), (3a)b+(3c)(2p-d),
+ *                (3a)(3b)+(3c)(6p-3d)
+ *  1 (16 -> 60)  x = (a, b) != 0, y = (c, d) -> fq2_mul(x, y), fq2_mul(3x loose, y), fq2_sqr<2>(x), fq2_sqr<4>(x + y lazy),
+ *                fq2_sqr<6>(3x lazy) (two results each), fq2_norm(x), fq2_neg(x) (two), fq2_inv(x) (two)
+ *  2 (32 -> 92)  e0 .. e7, stored in LDS slots -> g1coop::product(e0, e1; e2, e3) at the five (fa, ga, fb, gb) of the G1 chain
+ *                (1,0,1,0) (2,0,1,0) (1,1,1,1) (3,0,3,0) (3,0,1,0); g2coop::product of the Fq2 slots (e0,e1) (e2,e3); (e4,e5) (e6,e7)
+ *                at the same five tuples, each as c = 0, c = 1 and plain; chain_coop::combine of e0 .. e3 with the coefficient
+ *                sets (1,4,4,-4; 4 p), (-1,-6,-6,6; 13 p) and (1,-8,0,0; 8 p)
+ *  3 (72 -> 74)  Jacobian G1 P, Q (X Y Z each) and G2 P, Q (X.c0 X.c1 Y.c0 Y.c1 Z.c0 Z.c1 each) -> g1_double(P), g1_add(P, Q),
+ *                g2_double(P), g2_add(P, Q) as raw X Y Z, then the return codes of g1_add and g2_add (one word each)
+ * BN254S_E_INVALID_ARG: a NULL argument, an unknown group, an operand of p or more, x = 0 in group 1, a Z = 0 in group 3
+ * (the curve code has no point at infinity); nothing is launched then. */
+int bn254s_selftest_fq(bn254s_ctx* ctx, int group, const uint64_t* in, size_t n, uint64_t* out);
 /* Trace generation only: column-major trace[W][rows] copied to the host buffer.
  * kind: 0 = G1 scalar mul (W 781), 1 = G2 scalar mul (W 1295), 2 = Fq exp (W 427; offset ignored). */
 int bn254s_generate_trace(bn254s_ctx* ctx, int kind, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset,

@@ -5,6 +5,7 @@
 #include "ctx.h"
 #include "merkle.h"
 #include "trace_g1.h"
+#include "fq_selftest.h"
 #include "poseidon_dev.h"
 
 // one per translation unit: loads its code object (defined at the end of each .hip file)
@@ -511,6 +512,42 @@ int bn254s_selftest_fq_inv(bn254s_ctx* c, const uint64_t* x, size_t n, uint64_t*
   launch_fq_inv_selftest(d, d + 4 * n, n, c->stream);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(out, d + 4 * n, 64 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BN254S_OK;
+}
+
+// Debug: the BN254 Fq / Fq2 device arithmetic and the cooperative pieces of the doubling chains on RAW residues (fq_selftest.hip).
+// Unreduced limbs never reach the kernels: every operand is checked to be below p here, and so is what a group cannot represent.
+static bool selftest_fq_below_p(const uint64_t* w) {
+  static const uint64_t P[4] = {0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
+  for (int j = 3; j >= 0; j--)
+    if (w[j] != P[j]) return w[j] < P[j];
+  return false;
+}
+int bn254s_selftest_fq(bn254s_ctx* c, int group, const uint64_t* in, size_t n, uint64_t* out) {
+  if (!c || !in || !out || group < 0 || group >= FQ_SELFTEST_GROUPS) return BN254S_E_INVALID_ARG;
+  if (n == 0) return BN254S_OK;
+  const size_t wi = (size_t)FQ_SELFTEST_IN[group], wo = (size_t)FQ_SELFTEST_OUT[group];
+  auto is_zero = [](const uint64_t* w, int words) {
+    uint64_t o = 0;
+    for (int k = 0; k < words; k++) o |= w[k];
+    return o == 0;
+  };
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t* r = in + wi * i;
+    for (size_t k = 0; k < wi; k += 4)
+      if (!selftest_fq_below_p(r + k)) return BN254S_E_INVALID_ARG;
+    if (group == 1 && is_zero(r, 8)) return BN254S_E_INVALID_ARG;  // fq2_inv(x): x != 0
+    if (group == 3 && (is_zero(r + 8, 4) || is_zero(r + 20, 4) || is_zero(r + 40, 8) || is_zero(r + 64, 8)))
+      return BN254S_E_INVALID_ARG;  // Z = 0: the Jacobian code has no point at infinity
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  u64* d = c->words("fqs.io", (wi + wo) * n);
+  if (!d) return BN254S_E_OOM;
+  HIP_TRY(c, hipMemcpyAsync(d, in, 8 * wi * n, hipMemcpyHostToDevice, c->stream));
+  launch_fq_selftest(group, d, d + wi * n, n, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(out, d + wi * n, 8 * wo * n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return BN254S_OK;
 }

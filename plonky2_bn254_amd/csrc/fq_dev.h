@@ -168,11 +168,19 @@ __device__ __forceinline__ fq fq_sqr(const fq& a) {
 }
 
 // ---- loose operands ---------------------------------------------------------------------------------------------
-// fq_mul / fq_sqr / fq_mul2 accept "loose" operands: limbs up to 2^28.5 (a column sum of twenty limb products still fits 64
-// bits) and any values whose products add up to at most 64 p^2 (R = 2^260 > 84 p: the Montgomery result stays below 2p and
-// the final conditional subtraction makes it canonical).  Sums and differences that only feed a product therefore need no
-// carry chain and no reduction - ten instructions instead of the eighty of fq_add / fq_sub.  Every function still RETURNS
-// canonical values, so results are the same field elements bit for bit.
+// fq_mul / fq_sqr / fq_mul2 accept "loose" operands: un-reduced limb vectors.  What the code relies on is
+//  (1) every limb fits 32 bits and no 64-bit column sum wraps.  A column collects at most ten limb products per operand pair
+//      (twenty in fq_mul2), ten m p_j below 2^52 and a carry, so the bound is on the PRODUCT of the two sides' limb sizes, not on
+//      each side: with limbs <= La, Lb it needs 10 La Lb (20 for fq_mul2) + 2^56 < 2^64.  The widest pairing in use is a lazy
+//      sum of six canonical values (limbs <= 6 (2^26 - 1)) against fq_sub_lazy<6> of a 3x operand (limbs just below 7 * 2^26,
+//      about 2^28.8): 10 * 42 * 2^52 < 2^61.  In fq_mul2 the widest is 3x against that same difference (g2coop::product);
+//  (2) the products add up to at most 64 p^2 (R = 2^260 > 84 p: the Montgomery result stays below 2p, its top limb fits a
+//      signed register, and the final conditional subtraction makes it canonical).  The widest in use is 54 p^2 (fq2_sqr<6>).
+// Measured by the limb model (tools/fq_limb_model.py; tests/test_fq_limb_model_cpu.py replays the extreme residues of
+// tools/fq_operands.py - p - 1, all-ones limbs, 3x on both sides - and tests/test_gpu_fq_arith.py runs them through this code
+// on the GPU): largest column sum 60 bits (0.87 * 2^60), largest limb 29 bits (6.99 * 2^26).
+// Sums and differences that only feed a product therefore need no carry chain and no reduction - ten instructions instead of the
+// eighty of fq_add / fq_sub.  Every function still RETURNS canonical values, so results are the same field elements bit for bit.
 __device__ __forceinline__ fq fq_add_lazy(const fq& a, const fq& b) {  // a + b, limb-wise
   fq r;
 #pragma unroll
@@ -188,7 +196,8 @@ __device__ __forceinline__ fq fq_tpl_lazy(const fq& a) {  // 3a
 }
 // a - b + M p (M = 2, 4, 6), limb-wise and non-negative in every limb for b = a lazy sum of at most M/2 canonical values
 // (limbs <= (M/2)(2^26 - 1), value < (M/2) p): M p is written with every limb below the top raised by (M/2) 2^26, borrowed
-// from the limb above.  Result: value in (a, a + M p), limbs below a's + (M/2) 2^26 + 2^26.
+// from the limb above.  Result: value in (a, a + M p), limbs below a's + (M/2) 2^26 + 2^26 (M = 6 on a = 3x: up to 7 * 2^26).
+// b MUST respect its M: fq_sub_lazy<4> of a 3x operand would wrap a limb below zero.
 template <int M>
 struct FqSubConst {
   u32 k[FQ_NL];

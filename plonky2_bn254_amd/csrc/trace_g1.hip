@@ -187,17 +187,7 @@ namespace g1coop {
 using namespace chain_coop;
 enum { SX, SY, SZ, SA, SB, SC, SS, SF, SWW, SM, NSLOT };
 constexpr int INST_W = NSLOT * SLOT_W;
-// (fa S1 + ga S2) (fb T1 + gb T2): operands below 3p with limbs <= 3 (2^26 - 1)
-__device__ __forceinline__ fq product(const u32* g, int s1, int s2, u32 fa, u32 ga, int t1, int t2, u32 fb, u32 gb) {
-  const fq u = lds_ld(g, s1), v = lds_ld(g, s2), x = lds_ld(g, t1), y = lds_ld(g, t2);
-  fq A, B;
-#pragma unroll
-  for (int j = 0; j < FQ_NL; j++) {
-    A.l[j] = u.l[j] * fa + v.l[j] * ga;
-    B.l[j] = x.l[j] * fb + y.l[j] * gb;
-  }
-  return fq_mul(A, B);
-}
+// (product: chain_coop.h)
 }  // namespace g1coop
 
 __global__ __launch_bounds__(64) void k_g1_dbl_chain_coop(const u64* __restrict__ xs, int n, u64* __restrict__ px,

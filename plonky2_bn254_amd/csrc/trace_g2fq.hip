@@ -65,37 +65,7 @@ namespace g2coop {
 using namespace chain_coop;
 enum { SX, SY, SZ, SA, SB, SC, SS, SF, SWW, SM, NSLOT };
 constexpr int INST_W = NSLOT * 2 * SLOT_W;  // dwords per instance
-
-// component c of (fa S1 + ga S2) (fb T1 + gb T2) over Fq2, or with plain = true the sum of the two component products
-// (the norm).  Operand components stay below 3p with limbs <= 3 (2^26 - 1): c0 = A0 B0 + A1 (6p - B1) <= 27 p^2.
-__device__ __forceinline__ fq product(const u32* g, int c, bool plain, int s1, int s2, u32 fa, u32 ga, int t1, int t2, u32 fb,
-                                      u32 gb) {
-  fq A0, A1, B0, B1;
-  {
-    const fq u0 = lds_ld(g, 2 * s1), u1 = lds_ld(g, 2 * s1 + 1), v0 = lds_ld(g, 2 * s2), v1 = lds_ld(g, 2 * s2 + 1);
-#pragma unroll
-    for (int j = 0; j < FQ_NL; j++) {
-      A0.l[j] = u0.l[j] * fa + v0.l[j] * ga;
-      A1.l[j] = u1.l[j] * fa + v1.l[j] * ga;
-    }
-  }
-  {
-    const fq u0 = lds_ld(g, 2 * t1), u1 = lds_ld(g, 2 * t1 + 1), v0 = lds_ld(g, 2 * t2), v1 = lds_ld(g, 2 * t2 + 1);
-#pragma unroll
-    for (int j = 0; j < FQ_NL; j++) {
-      B0.l[j] = u0.l[j] * fb + v0.l[j] * gb;
-      B1.l[j] = u1.l[j] * fb + v1.l[j] * gb;
-    }
-  }
-  const fq nB1 = fq_sub_lazy<6>(fq_zero(), B1);
-  fq P, Q;
-#pragma unroll
-  for (int j = 0; j < FQ_NL; j++) {
-    P.l[j] = c ? B1.l[j] : B0.l[j];
-    Q.l[j] = c ? B0.l[j] : (plain ? B1.l[j] : nB1.l[j]);
-  }
-  return fq_mul2(A0, P, A1, Q);
-}
+// (product: chain_coop.h)
 }  // namespace g2coop
 
 __global__ __launch_bounds__(64) void k_g2_dbl_chain_coop(const u64* __restrict__ xs, int n, Soa2 px, Soa2 py, Soa2 pz,

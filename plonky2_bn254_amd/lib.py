@@ -94,6 +94,7 @@ def load_library():
     lib.bn254s_selftest_poseidon.argtypes = [vp, C.c_int, vp, C.c_size_t]
     lib.bn254s_selftest_leaf_hash.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp]
     lib.bn254s_selftest_fq_inv.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.bn254s_selftest_fq.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
     lib.bn254s_bench_copy.argtypes = [vp, C.c_size_t, C.c_int]
     lib.bn254s_bench_leafhash.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]
     lib.bn254s_g1_generate_trace.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
@@ -490,6 +491,20 @@ class Context:
         x = np.ascontiguousarray(x, dtype=np.uint64)
         out = np.zeros((x.shape[0], 8), np.uint64)
         self._check(self._lib.bn254s_selftest_fq_inv(self._h, _ptr(x), x.shape[0], _ptr(out)), "bn254s_selftest_fq_inv")
+        return out
+
+    SELFTEST_FQ_WORDS = ((16, 68), (16, 60), (32, 92), (72, 74))   # (in, out) words per row, by group
+
+    def selftest_fq(self, group: int, rows: np.ndarray) -> np.ndarray:
+        """Debug: the Fq / Fq2 device arithmetic on raw residues, rows[n][W_in] words -> out[n][W_out]; group 0 Fq, 1 Fq2,
+        2 the cooperative products and combine, 3 the Jacobian curve code (bn254s_selftest_fq)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        if not 0 <= group < len(self.SELFTEST_FQ_WORDS):
+            raise ValueError(f"selftest_fq: unknown group {group}")
+        wi, wo = self.SELFTEST_FQ_WORDS[group]
+        assert rows.ndim == 2 and rows.shape[1] == wi, (rows.shape, wi)
+        out = np.zeros((rows.shape[0], wo), np.uint64)
+        self._check(self._lib.bn254s_selftest_fq(self._h, group, _ptr(rows), rows.shape[0], _ptr(out)), "bn254s_selftest_fq")
         return out
 
     def poseidon_permute(self, states: np.ndarray) -> np.ndarray:

@@ -31,14 +31,20 @@ def fq_edge_inputs(n=6):
 
 
 def test_fq_arithmetic_limb_boundaries(gpu_ctx, oracle):
-    """Field elements that sit on the carry boundaries of the 26-bit-limb representation of csrc/fq_dev.h (all-ones limbs,
-    p - 1, p - 2^k, 2^(26 j) +- 1, R mod p ...): the whole Fq-exp trace (which squares and multiplies them 256 times) must
-    equal the oracle's, and the outputs Python's pow()."""
+    """Field elements on the carry boundaries of the 26-bit-limb representation of csrc/fq_dev.h (all-ones limbs, p - 1,
+    p - 2^k, 2^(26 j) +- 1, R mod p ...), twice.  First half: the values themselves as CANONICAL inputs - fq_unpack and the first
+    product by R^2 see the boundary limbs, after which the registers hold the Montgomery residues x 2^260 mod p, whose limbs are
+    pseudo-random.  Second half: the same list times 2^-260 mod p, so that the REGISTERS the exponentiation starts from hold the
+    boundary limbs.  The whole Fq-exp trace (which squares and multiplies them 256 times) must equal the oracle's, and the
+    outputs Python's pow().  (Every later step works on products of these, pseudo-random again: the loose forms and combine at
+    their bounds are tests/test_gpu_fq_arith.py.)"""
     P = synth.P
     vals = [P - 1, P - 2, (P - 1) // 2, (P + 1) // 2, (1 << 253) + 12345, (1 << 254) % P, pow(2, 260, P), pow(2, 520, P), P - (1 << 26),
             P - (1 << 52) + 1]
     vals += [(1 << (26 * j)) - 1 for j in range(1, 10)] + [(1 << (26 * j)) + 1 for j in range(1, 10)] + [(1 << (26 * j)) % P for j in (9, 10)]
     vals += [sum(((1 << 26) - 1) << (26 * j) for j in range(9)), sum(0x2AAAAAA << (26 * j) for j in range(9)) % P]
+    ri = pow(pow(2, 260, P), -1, P)
+    vals += [v % P * ri % P for v in vals]   # x with x 2^260 mod p = v: the residue in the registers is v
     n = len(vals)
     s, x = synth.fq_inputs(n, seed=77)
     for i, v in enumerate(vals):
