@@ -32,12 +32,14 @@
  * Threading: one call at a time per context (one host thread enters the context at a time); any number of contexts (one per
  * GPU / per host thread).  A batch opened with bn254s_prove_batch_begin stays in flight after _begin returns: until its _end
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
- * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x) queues
+ * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x /
+ * bn254s_g2_subgroup_check) queues
  * behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its own, so it can never share
  * device state with a proof of the open batch; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
- * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch and the front-end halves of
- * bn254s_g1_recover_from_x and bn254s_g2_recover_from_x, like those of bn254s_map_to_g2 and the msm chains) use the context's
- * own stream and pooled buffers under keys of their own and are independent of open batches.
+ * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch and the front-end
+ * halves of bn254s_g1_recover_from_x, bn254s_g2_recover_from_x and bn254s_g2_subgroup_check, like those of bn254s_map_to_g2 and
+ * the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub" for the subgroup check) and
+ * are independent of open batches.
  */
 #ifndef BN254_STARK_H
 #define BN254_STARK_H
@@ -278,7 +280,8 @@ int bn254s_g1_recover_from_x(bn254s_ctx* ctx, const bn254s_params* params, const
  * g_i = x_i^3 + b' in Fq2 (b' = 3/(9+u), the twist coefficient), its norm N_i = g_i.c0^2 + g_i.c1^2 and the root by two
  * exponentiations with (p+1)/4 and one inversion (csrc/g2_recover.hip):
  *   flags_out[i]  = 1 iff g_i is a square in Fq2, that is iff N_i is a square in Fq: x_i is the x of a point ON THE TWIST CURVE.
- *                   Membership in the r-torsion subgroup is NOT checked (the reference's gadgets do not check it either).
+ *                   Membership in the r-torsion subgroup is NOT checked (the reference's gadgets do not check it either):
+ *                   bn254s_g2_subgroup_check does that.
  *                   g_i and N_i are never zero: the twist has odd order, so no point has y = 0;
  *   points_out[i] = (x_i, y_i) (16 words) with y_i^2 = g_i, both coordinates of y_i below p and sgn(y_i) == sgns[i] (the parity
  *                   of y.c0, or of y.c1 when y.c0 is zero) where the flag is 1, (x_i, 0) where it is 0;
@@ -298,6 +301,35 @@ int bn254s_g2_recover_from_x_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 8:
 int bn254s_g2_recover_from_x(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* xs, const uint8_t* sgns, size_t n,
                              size_t per_proof, uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs /* may be NULL */,
                              bn254s_proof** fq_proofs);
+/* G2 subgroup check: is P_i, a point of the twist curve E'(Fq2), in the r-torsion subgroup, [r] P_i = O?  The twist has the
+ * cofactor 2p - r = 10069 * 5864401 * 1875725156269 * (a 178-bit prime), so bn254s_g2_recover_from_x hands out points that are
+ * no group elements of G2; this is the link between it and bn254s_g2_msm.  The reference has no such gadget: it is the circuit
+ * one writes with G2Target::new_checked, set_random_g2, g2_scalar_mul with the constant scalar r and connect.  Points are
+ * 16 words (x.c0, x.c1, y.c0, y.c1).  The device decides [r] P_i = O with the endomorphism psi = twist^-1 o Frobenius o twist,
+ * [x0 + 1]P + psi([x0]P) + psi^2([x0]P) == psi^3([2 x0]P) for the 63-bit BN parameter x0 (csrc/g2_subgroup.hip; why this holds
+ * for exactly the members, on the whole of E'(Fq2): DESIGN.md "G2 subgroup check"):
+ *   flags_out[i] = 1 iff [r] P_i is the point at infinity.
+ * A coordinate >= p is BN254S_E_INVALID_ARG, found on the host before any device work and before any output is written;
+ * bn254s_last_error names the first such i.  A point that is not on the twist curve (y^2 != x^3 + b') is BN254S_E_INVALID_ARG
+ * too: it is found on the device, reported before any output is copied to the caller, bn254s_last_error names the smallest
+ * such i, and no proof job is made of it (it is no valid G2Target; the trace generator never sees it).
+ * bn254s_g2_subgroup_check_batch: device front-end only, no proof. */
+int bn254s_g2_subgroup_check_batch(bn254s_ctx* ctx, const uint64_t* points /* n x 16, each coordinate < p */, size_t n,
+                                   uint8_t* flags_out /* n */);
+/* The front-end plus the G2 proofs of the n jobs (scalar r, x = P_i, offset = R_i = offsets[i]), cut into ceil(n / per_proof)
+ * proofs exactly as bn254s_prove_batch (kind 1) cuts them.  The G2 trace walks all 256 bits of the scalar and starts its running
+ * sum at the offset, so output i is R_i + [r] P_i: R_i exactly when P_i is a member.  The outputs of the proofs (computed bit by
+ * bit by the trace generator on its own) are checked against the flags of the endomorphism front-end: output i must equal
+ * offsets[i] word for word where flags_out[i] is 1 and differ from it where it is 0; a mismatch is BN254S_E_INTERNAL.
+ * offsets: n x 16 words, random subgroup points as set_random_g2 draws them, every coordinate below p (else
+ * BN254S_E_INVALID_ARG, as for the points).  If the running sum of a job meets the point at infinity (R_i unluckily equal to
+ * -m P_i for a partial scalar m) the error is BN254S_E_INVALID_POINT, exactly as bn254s_prove_g2 reports it: draw another offset.
+ * g2_jobs[i] = r | P_i (20 words; may be NULL).  flags_out and g2_jobs are written on success only.  On any error every proof
+ * of the call is freed and its slot in g2_proofs is NULL.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work
+ * (invalid arguments are reported first; the context is checked last). */
+int bn254s_g2_subgroup_check(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* points /* n x 16 */,
+                             const uint64_t* offsets /* n x 16 */, size_t n, size_t per_proof, uint8_t* flags_out /* n */,
+                             uint64_t* g2_jobs /* may be NULL: n x 20 = r | P_i */, bn254s_proof** g2_proofs);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

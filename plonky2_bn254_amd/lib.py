@@ -83,6 +83,8 @@ def load_library():
     lib.bn254s_g1_recover_from_x.argtypes = [vp, C.POINTER(Params), vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
     lib.bn254s_g2_recover_from_x_batch.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
     lib.bn254s_g2_recover_from_x.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
+    lib.bn254s_g2_subgroup_check_batch.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.bn254s_g2_subgroup_check.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(vp)]
     lib.bn254s_hash_to_fq2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bn254s_ctl_values.argtypes = [C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_commit_values.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
@@ -403,6 +405,34 @@ class Context:
         self._check(self._lib.bn254s_g2_recover_from_x(self._h, C.byref(params), _ptr(xs), sp, n, per_proof, _ptr(pts),
                                                        flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_g2_recover_from_x")
         return pts, flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+
+    def g2_subgroup_check_batch(self, points):
+        """points [n,16] (x.c0, x.c1, y.c0, y.c1, canonical, below p, on the twist curve) -> flags [n] uint8: flags[i] = 1 iff
+        [r] P_i is the point at infinity, by the endomorphism criterion on the device, no proof (bn254s_g2_subgroup_check_batch).
+        A coordinate >= p or a point off the curve raises (-1, the message names the first such point)."""
+        points = np.ascontiguousarray(points, dtype=np.uint64)
+        n = points.shape[0]
+        flags = np.zeros(n, np.uint8)
+        self._check(self._lib.bn254s_g2_subgroup_check_batch(self._h, _ptr(points), n, flags.ctypes.data_as(C.c_void_p)),
+                    "bn254s_g2_subgroup_check_batch")
+        return flags
+
+    def g2_subgroup_check(self, points, offsets, per_proof=128, params: Optional[Params] = None):
+        """points [n,16], offsets [n,16] (R_i: random subgroup points, set_random_g2) -> (flags [n], g2_jobs [n,20] = r | P_i,
+        proofs): the front-end plus the G2 proofs of the n jobs (r, P_i, R_i), cut into ceil(n / per_proof) proofs like
+        prove_batch(1, ...); output i is R_i + [r]P_i, R_i exactly where flags[i] is 1 (bn254s_g2_subgroup_check).  Check it with
+        verify_g2_subgroup."""
+        params = params or default_params()
+        points, offsets = (np.ascontiguousarray(a, dtype=np.uint64) for a in (points, offsets))
+        n = points.shape[0]
+        if offsets.shape != (n, 16):
+            raise ValueError(f"offsets {offsets.shape} for {n} points")
+        k = (n + per_proof - 1) // per_proof
+        flags, jobs = np.zeros(n, np.uint8), np.zeros((n, 20), np.uint64)
+        outs = (C.c_void_p * k)()
+        self._check(self._lib.bn254s_g2_subgroup_check(self._h, C.byref(params), _ptr(points), _ptr(offsets), n, per_proof,
+                                                       flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_g2_subgroup_check")
+        return flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
 
     def hash_to_fq2_batch(self, inputs: np.ndarray) -> np.ndarray:
         """inputs [n, len] Goldilocks elements -> u [n, 8]: hash_to_fq2 (hash_to_g2.rs:76-87) of every row, on the device."""
@@ -733,6 +763,55 @@ def verify_g2_recover(xs, sgns, points, flags, fq_jobs, proofs, per_proof, ctx: 
                 raise VerifyError(f"{tag}: sign {i} is {int(sgns[i])}, y of point {i} has the other one")
         elif y != (0, 0):
             raise VerifyError(f"{tag}: point {i} is not (x_{i}, 0) although its flag is clear")
+
+
+def verify_g2_subgroup(points, offsets, flags, g2_jobs, proofs, per_proof, ctx: Optional[Context] = None,
+                       params: Optional[Params] = None):
+    """Checks a g2_subgroup_check: job i is r | P_i (r from tools/synth.py), every coordinate of P_i is below p and P_i is on
+    the twist curve in Python integer arithmetic, every G2 proof (kind 1) verifies against its jobs (r, P_i, offsets[i])
+    (Context.verify with a context, else verify_host), and the proven output of job i, offsets[i] + [r]P_i, equals offsets[i]
+    word for word iff flags[i].  `proofs`: objects with `words`, `degree_bits` and `outputs`, such as Proof.  Returns None or
+    raises VerifyError naming the first point, job, flag or proof that fails."""
+    from tools import synth
+
+    tag, p = "g2_subgroup", synth.P
+    points, offsets, g2_jobs = (np.ascontiguousarray(a, dtype=np.uint64) for a in (points, offsets, g2_jobs))
+    flags = np.asarray(flags).reshape(-1)
+    n = points.shape[0]
+    if points.shape != (n, 16) or offsets.shape != (n, 16) or g2_jobs.shape != (n, 20) or flags.shape != (n,):
+        raise VerifyError(f"{tag}: shapes: points {points.shape}, offsets {offsets.shape}, flags {flags.shape}, g2_jobs {g2_jobs.shape}")
+    if len(proofs) != (n + per_proof - 1) // per_proof:
+        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    r_words = np.array(synth._to_words(synth.R_ORDER), np.uint64)
+    for i in range(n):
+        pt = synth.g2_from_words(points[i])
+        if max(pt[0] + pt[1]) >= p:
+            raise VerifyError(f"{tag}: point {i} has a coordinate that is not below p")
+        if not synth.g2_on_curve(pt):
+            raise VerifyError(f"{tag}: point {i} is not on the twist curve")
+        if not np.array_equal(g2_jobs[i, :4], r_words):
+            raise VerifyError(f"{tag}: scalar of job {i} != r")
+        if not np.array_equal(g2_jobs[i, 4:], points[i]):
+            raise VerifyError(f"{tag}: x of job {i} != point {i}")
+    scalars = np.ascontiguousarray(g2_jobs[:, :4])
+    for k, pr in enumerate(proofs):
+        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
+        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 16)
+        if outs.shape[0] != hi - lo:
+            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+        s_, x_, o_ = (np.ascontiguousarray(a[lo:hi]) for a in (scalars, points, offsets))
+        try:
+            if ctx is not None:
+                ctx.verify(1, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+            else:
+                verify_host(1, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+        except VerifyError as e:
+            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+        for i in range(lo, hi):
+            back = np.array_equal(outs[i - lo], offsets[i])
+            if back != bool(flags[i]):
+                raise VerifyError(f"{tag}: flag {i} is {int(flags[i])}, the proven offset_{i} + [r] point_{i} "
+                                  f"{'equals' if back else 'differs from'} offset_{i}")
 
 
 class BatchInFlight:

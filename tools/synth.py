@@ -439,3 +439,128 @@ def g2_recover_inputs(n: int, seed: int):
     cases = cases[:n]
     xs = np.array([_to_words(x[0]) + _to_words(x[1]) for x, _ in cases], dtype=np.uint64).reshape(-1, 8)
     return xs, np.array([s for _, s in cases], dtype=np.uint8)
+
+
+# ---- G2 subgroup membership: [r]P = O, and the untwist-Frobenius-twist endomorphism psi ------------------------------------
+X0 = 4965661367192848881                     # the BN parameter: p = 36 x0^4 + 36 x0^3 + 24 x0^2 + 6 x0 + 1
+G2_COFACTOR = 2 * P - R_ORDER                # #E'(Fq2) = r (2p - r)
+G2_COFACTOR_PRIMES = (10069, 5864401, 1875725156269, 197620364512881247228717050342013327560683201906968909)
+XI = (9, 1)                                  # the twist is y^2 = x^3 + 3/xi
+
+
+def f2_conj(a):
+    return (a[0], (-a[1]) % P)
+
+
+def f2_pow(a, e: int):
+    r = (1, 0)
+    for bit in bin(e)[2:] if e else "":
+        r = f2_mul(r, r)
+        if bit == "1":
+            r = f2_mul(r, a)
+    return r
+
+
+PSI_X = f2_pow(XI, (P - 1) // 3)             # psi(x, y) = (conj(x) xi^((p-1)/3), conj(y) xi^((p-1)/2))
+PSI_Y = f2_pow(XI, (P - 1) // 2)
+
+
+def g2_neg(pt):
+    return None if pt is None else (pt[0], ((-pt[1][0]) % P, (-pt[1][1]) % P))
+
+
+def g2_add_complete(a, b):
+    """a + b for affine points of the twist with None as the point at infinity: equal points double, opposite ones give None."""
+    if a is None:
+        return b
+    if b is None:
+        return a
+    return _f2j_affine(_f2j_add_affine((a[0], a[1], (1, 0)), b))
+
+
+def g2_on_curve(pt) -> bool:
+    return f2_mul(pt[1], pt[1]) == g2_rhs(pt[0])
+
+
+def g2_in_subgroup(pt) -> bool:
+    """The definition: [r] pt is the point at infinity (pt on the twist curve, any order)."""
+    return g2_mul_unreduced(R_ORDER, pt) is None
+
+
+def psi(pt):
+    """The endomorphism twist^-1 o Frobenius_p o twist of E'; None (infinity) stays None.  It satisfies psi^2 - t psi + p = 0 with
+    t = 6 x0^2 + 1, and acts on the r-torsion subgroup of E'(Fq2) as multiplication by p."""
+    if pt is None:
+        return None
+    return (f2_mul(f2_conj(pt[0]), PSI_X), f2_mul(f2_conj(pt[1]), PSI_Y))
+
+
+def g2_in_subgroup_psi(pt) -> bool:
+    """The endomorphism criterion (El Housni, Guillevic, Piellard: "Co-factor clearing and subgroup membership testing on
+    pairing-friendly curves"): [x0 + 1]P + psi([x0]P) + psi^2([x0]P) == psi^3([2 x0]P), one 63-bit scalar multiplication."""
+    q = g2_mul_unreduced(X0, pt)
+    lhs = g2_add_complete(g2_add_complete(g2_add_complete(q, pt), psi(q)), psi(psi(q)))
+    return lhs == psi(psi(psi(g2_add_complete(q, q))))
+
+
+def _g2_random_twist_point(rng):
+    """A uniform-looking point of E'(Fq2) (almost never in the r-torsion subgroup): g2_recover_from_x of random x until one is
+    the x of a point."""
+    while True:
+        x = (rng.next_u256() % P, rng.next_u256() % P)
+        pt = g2_recover_from_x(x, rng.next_u64() & 1)
+        if pt is not None:
+            return pt
+
+
+G2_SUBGROUP_CLASSES = ("generator multiple", "random twist point", "cofactor-cleared", "prime order f", "order 10069 * 5864401",
+                       "member + order 10069", "negated member")
+
+
+def g2_subgroup_inputs(n: int, seed: int, with_classes: bool = False):
+    """(points[n,16], flags[n]) for the G2 subgroup check; input i is of class i % 7 of G2_SUBGROUP_CLASSES:
+    k G2_GEN; a random twist point; [h]T; [r h / f]T of prime order f (the four primes of the cofactor h in turn); a point of
+    order 10069 * 5864401; a member plus a point of order 10069; the negation of a member.  Prefix-stable in n.  With
+    with_classes also the list of (class index, order of the cofactor part) per input."""
+    rng = Xoshiro256ss(seed)
+    h, primes = G2_COFACTOR, G2_COFACTOR_PRIMES
+
+    def of_order(d):
+        """A point of exact order d (a divisor of h made of distinct primes of h)."""
+        while True:
+            q = g2_mul_unreduced(R_ORDER * h // d, _g2_random_twist_point(rng))
+            if q is not None and all(g2_mul_unreduced(d // f, q) is not None for f in primes if d % f == 0):
+                return q
+
+    def member():
+        return g2_mul(rng.next_u256() % (R_ORDER - 1) + 1, G2_GEN)
+
+    pts, flags, classes, turn = [], [], [], 0
+    for i in range(n):
+        c, d = i % 7, 1
+        if c == 0:
+            pt = member()
+        elif c == 1:
+            pt = _g2_random_twist_point(rng)
+            d = 0  # (unknown)
+        elif c == 2:
+            pt = None
+            while pt is None:
+                pt = g2_mul_unreduced(h, _g2_random_twist_point(rng))
+        elif c == 3:
+            d = primes[turn % 4]
+            turn += 1
+            pt = of_order(d)
+        elif c == 4:
+            d = primes[0] * primes[1]
+            pt = of_order(d)
+        elif c == 5:
+            d = primes[0]
+            pt = g2_add(member(), of_order(d))
+        else:
+            pt = g2_neg(member())
+        pts.append(pt)
+        flags.append(1 if c in (0, 2, 6) else 0)
+        classes.append((c, d))
+    out = (g2_points_to_words(pts), np.array(flags, dtype=np.uint8))
+    return out + (classes,) if with_classes else out
