@@ -33,13 +33,15 @@
  * GPU / per host thread).  A batch opened with bn254s_prove_batch_begin stays in flight after _begin returns: until its _end
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
  * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x /
- * bn254s_g2_subgroup_check) queues
+ * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor) queues
  * behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its own, so it can never share
  * device state with a proof of the open batch; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
- * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch and the front-end
- * halves of bn254s_g1_recover_from_x, bn254s_g2_recover_from_x and bn254s_g2_subgroup_check, like those of bn254s_map_to_g2 and
- * the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub" for the subgroup check) and
- * are independent of open batches.
+ * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch,
+ * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch and the front-end halves of
+ * bn254s_g1_recover_from_x, bn254s_g2_recover_from_x, bn254s_g2_subgroup_check and bn254s_g2_clear_cofactor, like those of
+ * bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub" for the
+ * subgroup check, "g2cof" and "g2cof.link" for cofactor clearing, "m2g.batch" for the proof-free map) and are independent of
+ * open batches.
  */
 #ifndef BN254_STARK_H
 #define BN254_STARK_H
@@ -330,6 +332,52 @@ int bn254s_g2_subgroup_check_batch(bn254s_ctx* ctx, const uint64_t* points /* n 
 int bn254s_g2_subgroup_check(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* points /* n x 16 */,
                              const uint64_t* offsets /* n x 16 */, size_t n, size_t per_proof, uint8_t* flags_out /* n */,
                              uint64_t* g2_jobs /* may be NULL: n x 20 = r | P_i */, bn254s_proof** g2_proofs);
+/* G2 cofactor clearing: P_i -> [h] P_i for points of the twist curve E'(Fq2), h = 2p - r the cofactor of the r-torsion subgroup
+ * (mul_by_cofactor at the end of the reference's map_to_g2, src/utils/hash_to_g2.rs:113-148; in its circuit g2_scalar_mul with the
+ * constant scalar h).  It turns what bn254s_g2_recover_from_x hands out into points that bn254s_g2_subgroup_check accepts and
+ * bn254s_g2_msm can fold.  Points are 16 words (x.c0, x.c1, y.c0, y.c1).  The device does not walk the 254 bits of h: with
+ * psi = twist^-1 o Frobenius o twist and T = [6 x0^2] P (two chained ladders by the BN parameter, 63 and 65 bits),
+ * [h] P = T + psi(T + P) - psi^2(P), exactly, on the whole of E'(Fq2) (csrc/g2_cofactor.hip; DESIGN.md "G2 cofactor clearing"):
+ *   finite_out[i] = 1 iff [h] P_i is a finite point, 0 iff it is the point at infinity (the order of P_i divides h);
+ *   images_out[i] = [h] P_i, affine, every coordinate below p, where finite_out[i] is 1; 16 zero words where it is 0.
+ * A coordinate >= p is BN254S_E_INVALID_ARG, found on the host before any device work and before any output is written;
+ * bn254s_last_error names the first such i.  A point that is not on the twist curve (y^2 != x^3 + b') is BN254S_E_INVALID_ARG
+ * too: it is found on the device, reported before any output is copied to the caller, bn254s_last_error names the smallest
+ * such i, and no proof job is made of it.
+ * bn254s_g2_clear_cofactor_batch: device front-end only, no proof (one MI355X, copies included: 3.0 ms for 128 points,
+ * 3.2 ms for 16 384, 67 ms for 2^20; profiles/g2_cofactor_times.txt). */
+int bn254s_g2_clear_cofactor_batch(bn254s_ctx* ctx, const uint64_t* points /* n x 16, each coordinate < p */, size_t n,
+                                   uint64_t* images_out /* n x 16 */, uint8_t* finite_out /* n */);
+/* The front-end plus the G2 proofs of the n jobs (scalar h, x = P_i, offset = R_i = offsets[i]), cut into ceil(n / per_proof)
+ * proofs exactly as bn254s_prove_batch (kind 1) cuts them.  Output i of the proofs is R_i + [h] P_i, computed bit by bit by the
+ * trace generator on its own, and is checked against the front-end: it must equal offsets[i] word for word where finite_out[i] is
+ * 0, and output i - R_i (the subtraction bn254s_map_to_g2 ends with) must equal images_out[i] word for word where it is 1; a
+ * mismatch is BN254S_E_INTERNAL and bn254s_last_error names i.  Output i == +-R_i beside a finite image is
+ * BN254S_E_INVALID_POINT, as bn254s_map_to_g2 reports it.  offsets: n x 16 words, random subgroup points as set_random_g2 draws
+ * them, every coordinate below p (else BN254S_E_INVALID_ARG, as for the points).  If the running sum of a job meets the point at
+ * infinity the error is BN254S_E_INVALID_POINT, exactly as bn254s_prove_g2 reports it: draw another offset.
+ * g2_jobs[i] = h | P_i (20 words; may be NULL).  images_out, finite_out and g2_jobs are written on success only.  On any error
+ * every proof of the call is freed and its slot in g2_proofs is NULL.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device
+ * work (invalid arguments are reported first; the context is checked last). */
+int bn254s_g2_clear_cofactor(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* points /* n x 16 */,
+                             const uint64_t* offsets /* n x 16 */, size_t n, size_t per_proof, uint64_t* images_out /* n x 16 */,
+                             uint8_t* finite_out /* n */, uint64_t* g2_jobs /* may be NULL: n x 20 = h | P_i */,
+                             bn254s_proof** g2_proofs);
+/* The reference's native map_to_g2 (src/utils/hash_to_g2.rs:113-148) for n inputs u (8 words: c0, c1, each below p) on the
+ * device, no proof: the candidates of bn254s_map_to_g2, "g(x1) is a square" and "g(x2) is a square" decided from the norm's
+ * exponentiation as bn254s_g2_recover_from_x decides its flag, the choice of x, y = sqrt(g(x)) with sgn(y) = sgn(u), and the
+ * cofactor-clearing kernel on (x, y).  out_points (n x 16 words) are the out_points bn254s_map_to_g2 returns for the same u
+ * (they do not depend on its offsets), without its 2 Fq-exp jobs and 1 G2 job per input (one MI355X: 3.9 ms against 1030 ms
+ * for 4096 inputs; profiles/g2_cofactor_times.txt).
+ * A coordinate of u >= p: BN254S_E_INVALID_ARG, found on the host, bn254s_last_error names the first such i.  g(x) of the chosen
+ * x not a square (a device self-check): BN254S_E_INTERNAL.  An infinite image (a mapped point whose order divides h; never seen
+ * in practice): BN254S_E_INVALID_POINT, bn254s_last_error names the smallest such i.  Nothing is written on an error. */
+int bn254s_map_to_g2_batch(bn254s_ctx* ctx, const uint64_t* u /* n x 8, each coordinate < p */, size_t n,
+                           uint64_t* out_points /* n x 16 */);
+/* hash_to_g2 (src/utils/hash_to_g2.rs:40-43) for n inputs of `len` Goldilocks elements each: bn254s_hash_to_fq2_batch and then
+ * bn254s_map_to_g2_batch, u staying on the device.  Errors as bn254s_map_to_g2_batch (u is below p by construction). */
+int bn254s_hash_to_g2_batch(bn254s_ctx* ctx, const uint64_t* inputs /* n x len */, size_t n, size_t len,
+                            uint64_t* out_points /* n x 16 */);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

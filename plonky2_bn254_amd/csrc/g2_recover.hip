@@ -4,7 +4,8 @@
 //   k_g2_recover: g = x^3 + b' in Fq2, the Legendre job norm(g)^((p-1)/2), the flag "g is a square" and y = sqrt(g) with the
 //                 wanted sign
 //   [n fq_exp proofs of the Legendre symbols]
-// An Fq2 square root in two Fq exponentiations, both with the exponent (p+1)/4 of sqrt_ladder.h (p = 3 mod 4):
+// An Fq2 square root in two Fq exponentiations, both with the exponent (p+1)/4 of sqrt_ladder.h (p = 3 mod 4); the code is
+// fq2_root.h, shared with map_to_g2.hip:
 //   1. N = g.c0^2 + g.c1^2, alpha = N^((p+1)/4): alpha^2 == N says that N, and with it g, is a square; alpha^2 == -N that it is none.
 //   2. delta = (alpha + g.c0)/2 satisfies delta (delta - alpha) = -g.c1^2/4.  t = delta^((p+1)/4) has t^2 = +-delta:
 //        t^2 ==  delta: y = (t, g.c1/(2t)),   since (g.c1/(2t))^2 = alpha - delta and t^2 - (alpha - delta) = g.c0;
@@ -13,25 +14,10 @@
 // g is never zero (the twist has odd order: no point with y = 0; equivalently -b' is not a cube in Fq2), and -1 is a non-residue
 // of Fq, so N is never zero either: "N is a square" and "the Legendre symbol of N is 1" agree, and delta, t are never zero.
 #include "recover_host.h"
-#include "sqrt_ladder.h"
-#include "g2_recover_constants.inc"
+#include "fq2_root.h"
 
 namespace {
 
-__device__ __forceinline__ fq fq_from_limbs(const u32 (&l)[FQ_NL]) {
-  fq r;
-#pragma unroll
-  for (int j = 0; j < FQ_NL; j++) r.l[j] = l[j];
-  return r;
-}
-// c ? a : b limb by limb (a select of whole structs goes through their addresses, and with them through scratch memory)
-__device__ __forceinline__ fq fq_select(bool c, const fq& a, const fq& b) {
-  const u32 m = 0u - (u32)c;
-  fq r;
-#pragma unroll
-  for (int j = 0; j < FQ_NL; j++) r.l[j] = (a.l[j] & m) | (b.l[j] & ~m);
-  return r;
-}
 // src/fields/sgn.rs:20-27 on canonical words: the parity of c0, or of c1 when c0 is zero
 __device__ __forceinline__ bool sgn_words(const fqw& c0, const fqw& c1) {
   const bool zero0 = (c0.l[0] | c0.l[1] | c0.l[2] | c0.l[3]) == 0;
@@ -51,23 +37,8 @@ __global__ __launch_bounds__(G1R_LANES) void k_g2_recover(const u64* __restrict_
   b.c1 = fq_from_limbs(G2R_B_C1);
   const fq2 g = fq2_add(fq2_mul(fq2_sqr(x), x), b);
   const fq nrm = fq2_norm(g);
-  const fq alpha = sqrt_ladder(tab, nrm);
-  const fq a2 = fq_sqr(alpha);
-  const bool square = fq_eq(a2, nrm);
-  bool bad = !square && !fq_eq(a2, fq_neg(nrm));  // neither root nor non-residue: the ladder is wrong
-  // Every lane runs the second ladder, so that a wave stays together: where g is no square it works on delta = 1 (t = 1, an
-  // inverse of 2) and its y is masked below.
-  fq delta = fq_select(fq_is_zero(g.c1), g.c0, fq_mul(fq_add(alpha, g.c0), fq_from_limbs(G2R_HALF)));
-  delta = fq_select(square, delta, fq_one());
-  const fq t = sqrt_ladder(tab, delta);  // overwrites the lane's own table entries: no barrier
-  const fq t2 = fq_sqr(t);
-  const bool plus = fq_eq(t2, delta);
-  bad |= !plus && !fq_eq(t2, fq_neg(delta));
-  const fq o = fq_mul(g.c1, fq_inv(fq_dbl(t)));
-  fq2 y;
-  y.c0 = fq_select(plus, t, o);
-  y.c1 = fq_select(plus, o, t);
-  bad |= square && !fq2_eq(fq2_sqr(y), g);
+  bool square, bad;
+  const fq2 y = fq2_root(tab, g, nrm, square, bad);
   if (bad) atomicCAS(err, 0, BN254S_E_INTERNAL);
   fqw y0 = fq_to_canonical(y.c0), y1 = fq_to_canonical(y.c1);
   if (sgn_words(y0, y1) != (sgns[k] != 0)) {  // -y: p - c for a non-zero coordinate, which flips its parity as p is odd

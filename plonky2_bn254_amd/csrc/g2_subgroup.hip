@@ -28,84 +28,12 @@
 // One lane per point, like k_g2_recover; x0 is a compile-time constant, so every lane of a wave doubles and adds in the same
 // steps.  P stays affine through the ladder (mixed addition, Z2 = 1).
 #include <climits>
-#include "recover_host.h"
-#include "chain_scan.h"
-#include "g2_recover_constants.inc"
-#include "g2_subgroup_constants.inc"
+#include "g2_endo.h"
 
 namespace {
 
 constexpr int G2S_LANES = 64;
 constexpr size_t G2S_PER_PROOF_MAX = 16384;  // 2^23 rows, the largest G2 proof (bn254s_prove_batch)
-
-__device__ __forceinline__ fq g2s_limbs(const u32 (&l)[FQ_NL]) {
-  fq r;
-#pragma unroll
-  for (int j = 0; j < FQ_NL; j++) r.l[j] = l[j];
-  return r;
-}
-__device__ __forceinline__ fq2 fq2_conj(const fq2& a) {
-  fq2 r;
-  r.c0 = a.c0;
-  r.c1 = fq_neg(a.c1);
-  return r;
-}
-// psi on Jacobian coordinates: x = X/Z^2 and y = Y/Z^3 are conjugated by conjugating X, Y and Z.  O (Z = 0) stays O.
-__device__ __forceinline__ g2j g2_psi(const g2j& p) {
-  fq2 gx, gy;
-  gx.c0 = g2s_limbs(G2S_PSI_X_C0);
-  gx.c1 = g2s_limbs(G2S_PSI_X_C1);
-  gy.c0 = g2s_limbs(G2S_PSI_Y_C0);
-  gy.c1 = g2s_limbs(G2S_PSI_Y_C1);
-  g2j r;
-  r.x = fq2_mul(fq2_conj(p.x), gx);
-  r.y = fq2_mul(fq2_conj(p.y), gy);
-  r.z = fq2_conj(p.z);
-  return r;
-}
-// p + (x2, y2) for an affine, finite second operand (Z2 = 1: 8 products and 3 squarings against the 11 and 5 of g2_add),
-// complete: an infinite p gives the affine point, equal points double, opposite points give O.
-__device__ __forceinline__ g2j g2_madd(const g2j& p, const fq2& x2, const fq2& y2) {
-  g2j r;
-  if (pt_inf(p)) {
-    r.x = x2;
-    r.y = y2;
-    r.z = fq2_one();
-    return r;
-  }
-  const fq2 z1z1 = fq2_sqr(p.z);
-  const fq2 h = fq2_sub(fq2_mul(x2, z1z1), p.x), rr = fq2_sub(fq2_mul(fq2_mul(y2, p.z), z1z1), p.y);
-  if (fq2_is_zero(h)) return fq2_is_zero(rr) ? g2_double(p) : pt_infinity((const g2j*)nullptr);
-  const fq2 hh = fq2_sqr(h), hhh = fq2_mul(h, hh), v = fq2_mul(p.x, hh);
-  r.x = fq2_sub(fq2_sub(fq2_sqr(rr), hhh), fq2_dbl(v));
-  r.y = fq2_sub(fq2_mul(rr, fq2_sub(v, r.x)), fq2_mul(p.y, hhh));
-  r.z = fq2_mul(p.z, h);
-  return r;
-}
-// p + q, complete like pt_add_complete (chain_scan.h): either operand may be O, equal points double, opposite points give O.
-// The formulas of g2_add in another order: u2 and s2 are consumed as they are made, so fewer Fq2 values are alive at the widest
-// point - with pt_add_complete in its place the compiler puts 340 bytes per lane into scratch memory, with this form none.
-__device__ __forceinline__ g2j g2_add_lean(const g2j& p, const g2j& q) {
-  if (pt_inf(q)) return p;
-  if (pt_inf(p)) return q;
-  const fq2 z1z1 = fq2_sqr(p.z), z2z2 = fq2_sqr(q.z);
-  const fq2 u1 = fq2_mul(p.x, z2z2), s1 = fq2_mul(fq2_mul(p.y, q.z), z2z2);
-  const fq2 h = fq2_sub(fq2_mul(q.x, z1z1), u1), rr = fq2_sub(fq2_mul(fq2_mul(q.y, p.z), z1z1), s1);
-  if (fq2_is_zero(h)) return fq2_is_zero(rr) ? g2_double(p) : pt_infinity((const g2j*)nullptr);
-  const fq2 hh = fq2_sqr(h), hhh = fq2_mul(h, hh), v = fq2_mul(u1, hh);
-  g2j r;
-  r.x = fq2_sub(fq2_sub(fq2_sqr(rr), hhh), fq2_dbl(v));
-  r.y = fq2_sub(fq2_mul(rr, fq2_sub(v, r.x)), fq2_mul(s1, hhh));
-  r.z = fq2_mul(fq2_mul(p.z, q.z), h);
-  return r;
-}
-// t == -(x, y) for a Jacobian t and an affine, finite (x, y), by cross-multiplication: X == x Z^2 and Y == -y Z^3.  O is not
-// the negative of a finite point.
-__device__ __forceinline__ bool g2_is_neg_of_affine(const g2j& t, const fq2& x, const fq2& y) {
-  if (pt_inf(t)) return false;
-  const fq2 zz = fq2_sqr(t.z);
-  return fq2_eq(t.x, fq2_mul(x, zz)) && fq2_eq(t.y, fq2_neg(fq2_mul(fq2_mul(y, t.z), zz)));
-}
 
 // points: n x 16 canonical words (x.c0, x.c1, y.c0, y.c1), every coordinate below p; flags: n bytes.  A point off the curve
 // writes no flag and lowers *bad_idx to its index.
@@ -114,10 +42,7 @@ __global__ __launch_bounds__(G2S_LANES) void k_g2_subgroup(const u64* __restrict
   const size_t k = (size_t)blockIdx.x * G2S_LANES + threadIdx.x;
   if (k >= n) return;
   fq2 px = fq2_from_canonical(points + 16 * k), py = fq2_from_canonical(points + 16 * k + 8);
-  fq2 b;
-  b.c0 = g2s_limbs(G2R_B_C0);
-  b.c1 = g2s_limbs(G2R_B_C1);
-  if (!fq2_eq(fq2_sqr(py), fq2_add(fq2_mul(fq2_sqr(px), px), b))) {
+  if (!g2_on_twist(px, py)) {
     atomicMin(bad_idx, (unsigned)k);
     return;
   }
@@ -143,18 +68,6 @@ __global__ __launch_bounds__(G2S_LANES) void k_g2_subgroup(const u64* __restrict
   flags[k] = g2_is_neg_of_affine(t, q.x, q.y) ? 1 : 0;
 }
 
-// The first point with a coordinate that is not below p puts its message into *what; true if all are fine.
-bool coords_ok(const char* name, const uint64_t* pts, size_t n, std::string* what) {
-  static const char* const coord[4] = {"x.c0", "x.c1", "y.c0", "y.c1"};
-  for (size_t i = 0; i < n; i++)
-    for (int c = 0; c < 4; c++)
-      if (!recover_below_p(pts + 16 * i + 4 * c)) {
-        *what = std::string("g2_subgroup_check: ") + name + "_" + std::to_string(i) + " has " + coord[c] + " not below p";
-        return false;
-      }
-  return true;
-}
-
 bool front_args_ok(const uint64_t* points, size_t n, const uint8_t* flags_out) {
   return points && flags_out && n > 0 && n < (size_t)UINT_MAX;  // the first bad index travels as a 32-bit word
 }
@@ -162,7 +75,7 @@ bool front_args_ok(const uint64_t* points, size_t n, const uint8_t* flags_out) {
 // The front-end into host memory: flags[n].  Nothing is written on an error.
 int subgroup_front(bn254s_ctx* c, const uint64_t* points, size_t n, uint8_t* flags) {
   std::string what;
-  if (!coords_ok("point", points, n, &what)) {
+  if (!g2_coords_ok("g2_subgroup_check", "point", points, n, &what)) {
     c->set_err(what);
     return BN254S_E_INVALID_ARG;
   }
@@ -211,7 +124,7 @@ extern "C" int bn254s_g2_subgroup_check(bn254s_ctx* c, const bn254s_params* para
   }
   if (!c) return BN254S_E_INVALID_ARG;
   std::string what;
-  if (!coords_ok("offset", offsets, n, &what)) {  // (the trace generator takes canonical words; before any output is written)
+  if (!g2_coords_ok("g2_subgroup_check", "offset", offsets, n, &what)) {  // (the trace generator takes canonical words; before any output is written)
     c->set_err(what);
     return BN254S_E_INVALID_ARG;
   }

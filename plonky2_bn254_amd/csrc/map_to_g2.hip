@@ -9,11 +9,19 @@
 //   k_m2g_finish:     output - offset                                                (hash_to_g2.rs:200-205)
 // Square roots follow ark-ff 0.4 (Fq: a^((p+1)/4); Fq2: the "complex method" of QuadExtField::sqrt), like the Python
 // front-end tools/map_to_g2_ref.py, which is the parity reference of tests/test_map_to_g2.py.
+// The same map without the proofs, the reference's native map_to_g2 / hash_to_g2 (bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch):
+//   [k_hash_to_fq2]
+//   k_m2g_point:          the candidates, the two "is a square" flags and the signed root from the ladders of fq2_root.h
+//   k_g2_clear_cofactor:  [h](x, y) by the endomorphism form (g2_cofactor.hip)
+#include <climits>
 #include <cstring>
 #include <string>
 #include <vector>
 #include "ctx.h"
 #include "fq_dev.h"
+#include "fq2_root.h"
+#include "g2_cofactor.h"
+#include "recover_host.h"
 #include "transcript.h"
 #include "../../include/bn254_stark.h"
 #include "map_to_g2_constants.inc"
@@ -78,23 +86,30 @@ __device__ __noinline__ fq2 f2_sqrt(const fq2& a, const M2GConsts& C, bool* ok) 
   return r;
 }
 
-// cand: 3 x 8 words per input (x1, x2, x3 canonical); fq_s / fq_x: the 2n fq_exp jobs
-__global__ __launch_bounds__(64) void k_m2g_candidates(const u64* __restrict__ u, size_t n, M2GConsts C, u64* __restrict__ cand,
-                                                       u64* __restrict__ fq_s, u64* __restrict__ fq_x) {
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const fq2 uu = fq2_from_canonical(u + 8 * k), gz = fq2_from_canonical(C.gz), b2 = fq2_from_canonical(C.b2);
+// x1, x2, x3 of hash_to_g2.rs:119-127 for one input u: shared by the proven pipeline (k_m2g_candidates) and the proof-free one
+// (k_m2g_point), so that the two cannot diverge - also not where tv1 tv2 = 0, whose inverse both take as fq2_inv gives it.
+__device__ __forceinline__ void m2g_candidates(const fq2& uu, const M2GConsts& C, fq2& x1, fq2& x2, fq2& x3) {
+  const fq2 gz = fq2_from_canonical(C.gz);
   fq2 tv1 = fq2_mul(fq2_sqr(uu), gz);
   const fq2 tv2 = fq2_add(fq2_one(), tv1);
   tv1 = fq2_sub(fq2_one(), tv1);
   const fq2 tv3 = fq2_inv(fq2_mul(tv1, tv2));
   const fq2 tv5 = fq2_mul(fq2_mul(fq2_mul(uu, tv1), tv3), fq2_from_canonical(C.tv4));
   const fq2 nz2 = fq2_from_canonical(C.nz2);
-  fq2 x[3];
-  x[0] = fq2_sub(nz2, tv5);
-  x[1] = fq2_add(nz2, tv5);
+  x1 = fq2_sub(nz2, tv5);
+  x2 = fq2_add(nz2, tv5);
   const fq2 t = fq2_mul(fq2_sqr(tv2), tv3);
-  x[2] = fq2_add(fq2_one(), fq2_mul(fq2_from_canonical(C.tv6), fq2_sqr(t)));
+  x3 = fq2_add(fq2_one(), fq2_mul(fq2_from_canonical(C.tv6), fq2_sqr(t)));
+}
+
+// cand: 3 x 8 words per input (x1, x2, x3 canonical); fq_s / fq_x: the 2n fq_exp jobs
+__global__ __launch_bounds__(64) void k_m2g_candidates(const u64* __restrict__ u, size_t n, M2GConsts C, u64* __restrict__ cand,
+                                                       u64* __restrict__ fq_s, u64* __restrict__ fq_x) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const fq2 b2 = fq2_from_canonical(C.b2);
+  fq2 x[3];
+  m2g_candidates(fq2_from_canonical(u + 8 * k), C, x[0], x[1], x[2]);
 #pragma unroll 1
   for (int i = 0; i < 3; i++) fq2_store_canonical(cand + (3 * k + i) * 8, x[i]);
 #pragma unroll 1
@@ -142,6 +157,44 @@ __global__ __launch_bounds__(64) void k_m2g_finish(const u64* __restrict__ o, co
   const fq2 y3 = fq2_sub(fq2_mul(lam, fq2_sub(x1, x3)), y1);
   fq2_store_canonical(out + 16 * k, x3);
   fq2_store_canonical(out + 16 * k + 8, y3);
+}
+
+// The point (x, y) of hash_to_g2.rs:119-145 without the proven Legendre symbols: the candidates, "g(x1) is a square" and "g(x2) is
+// a square" from the norm's exponentiation as k_g2_recover decides its flag (fq2_root.h), the choice of x, and y = sqrt(g(x)) with
+// sgn(y) = sgn(u).  The two roots +-y have opposite signs under sgn.rs:20-27, so any root followed by the sign fix is the
+// reference's y.  Every lane runs the three norm ladders and one root ladder, so that a wave stays together.
+// points: n x 16 canonical words; *err: BN254S_E_INTERNAL if g of the chosen x is no square or a root does not square back.
+__global__ __launch_bounds__(G1R_LANES) void k_m2g_point(const u64* __restrict__ u, size_t n, M2GConsts C, u64* __restrict__ points,
+                                                         int* __restrict__ err) {
+  __shared__ u32 tab[G1R_ENTRIES][FQ_NL][G1R_LANES];
+  const size_t k = (size_t)blockIdx.x * G1R_LANES + threadIdx.x;
+  if (k >= n) return;
+  const fq2 uu = fq2_from_canonical(u + 8 * k), b2 = fq2_from_canonical(C.b2);
+  fq2 x1, x2, x3;
+  m2g_candidates(uu, C, x1, x2, x3);
+  // from x3 down to x1, so that the first candidate with a square g(x) is the one that stays
+  fq2 x = x3, g = g_rhs(x3, b2);
+  bool square, bad;
+  fq alpha = fq2_norm_root(tab, fq2_norm(g), square, bad);
+  auto prefer = [&](const fq2& xi) {
+    const fq2 gi = g_rhs(xi, b2);
+    bool sq, bd;
+    const fq ai = fq2_norm_root(tab, fq2_norm(gi), sq, bd);
+    bad |= bd;
+    x.c0 = fq_select(sq, xi.c0, x.c0);
+    x.c1 = fq_select(sq, xi.c1, x.c1);
+    g.c0 = fq_select(sq, gi.c0, g.c0);
+    g.c1 = fq_select(sq, gi.c1, g.c1);
+    alpha = fq_select(sq, ai, alpha);
+    square |= sq;
+  };
+  prefer(x2);
+  prefer(x1);
+  fq2 y = fq2_root_from_alpha(tab, g, alpha, square, bad);
+  if (bad || !square) atomicCAS(err, 0, BN254S_E_INTERNAL);
+  if (f2_sgn(uu) != f2_sgn(y)) y = fq2_neg(y);
+  fq2_store_canonical(points + 16 * k, x);
+  fq2_store_canonical(points + 16 * k + 8, y);
 }
 
 // hash_to_fq2 for n inputs of `len` Goldilocks elements each, one lane per input (hash_to_g2.rs:76-87): the challenger absorbs the
@@ -351,4 +404,80 @@ extern "C" int bn254s_map_to_g2(bn254s_ctx* c, const bn254s_params* params, cons
     return h_err;
   }
   return BN254S_OK;
+}
+
+namespace {
+
+// d_u (n x 8 canonical words on the device, in the buffer d of 8n + 16n + 16n + 2 + ceil(n/8) words that starts with it) ->
+// out_points: k_m2g_point, then k_g2_clear_cofactor on its points.  Nothing is written on an error.
+int map_to_g2_on_device(bn254s_ctx* c, const char* tag, u64* d, size_t n, uint64_t* out_points) {
+  hipStream_t st = c->stream;
+  u64* d_u = d;
+  u64* d_pts = d_u + 8 * n;
+  u64* d_img = d_pts + 16 * n;
+  int* d_err = (int*)(d_img + 16 * n);
+  unsigned* d_bad = (unsigned*)(d_img + 16 * n + 1);
+  unsigned char* d_fin = (unsigned char*)(d_img + 16 * n + 2);
+  const std::string who = std::string(tag) + ": ";
+  HIP_TRY(c, hipMemsetAsync(d_err, 0, 8, st));
+  HIP_TRY(c, hipMemsetAsync(d_bad, 0xFF, 8, st));
+  k_m2g_point<<<(unsigned)((n + G1R_LANES - 1) / G1R_LANES), G1R_LANES, 0, st>>>(d_u, n, host_consts(), d_pts, d_err);
+  HIP_TRY(c, hipGetLastError());
+  int rc = bn254s_g2_clear_cofactor_device(c, d_pts, n, d_img, d_fin, d_bad);
+  if (rc != BN254S_OK) return rc;
+  int h_err = 0;
+  unsigned h_bad = UINT_MAX;
+  std::vector<uint8_t> fin(n);
+  HIP_TRY(c, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(fin.data(), d_fin, n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (h_err) {
+    c->set_err(who + "g(x) of the chosen candidate is not a square, or a root does not square back (device self-check)");
+    return h_err;
+  }
+  if (h_bad != UINT_MAX) {
+    c->set_err(who + "the mapped point " + std::to_string(h_bad) + " is not on the twist curve (device self-check)");
+    return BN254S_E_INTERNAL;
+  }
+  for (size_t i = 0; i < n; i++)
+    if (!fin[i]) {
+      c->set_err(who + "the image of input " + std::to_string(i) + " is the point at infinity (the order of its mapped point divides the cofactor)");
+      return BN254S_E_INVALID_POINT;
+    }
+  HIP_TRY(c, hipMemcpyAsync(out_points, d_img, n * 128, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return BN254S_OK;
+}
+size_t m2g_batch_words(size_t n) { return 40 * n + 2 + (n + 7) / 8; }
+
+}  // namespace
+
+// The reference's native map_to_g2 (hash_to_g2.rs:113-148) without proofs: the point bn254s_map_to_g2 reads from its proofs.
+extern "C" int bn254s_map_to_g2_batch(bn254s_ctx* c, const uint64_t* u, size_t n, uint64_t* out_points) {
+  if (!c || !u || !out_points || n == 0 || n >= (size_t)UINT_MAX) return BN254S_E_INVALID_ARG;
+  for (size_t i = 0; i < n; i++)
+    for (int j = 0; j < 2; j++)
+      if (!recover_below_p(u + 8 * i + 4 * j)) {
+        c->set_err("map_to_g2_batch: u_" + std::to_string(i) + " has c" + std::to_string(j) + " not below p");
+        return BN254S_E_INVALID_ARG;
+      }
+  HIP_TRY(c, hipSetDevice(c->device));
+  u64* d = c->words("m2g.batch", m2g_batch_words(n));
+  if (!d) return BN254S_E_OOM;
+  HIP_TRY(c, hipMemcpyAsync(d, u, n * 64, hipMemcpyHostToDevice, c->stream));
+  return map_to_g2_on_device(c, "map_to_g2_batch", d, n, out_points);
+}
+
+// hash_to_g2 (hash_to_g2.rs:40-43): k_hash_to_fq2 writes u where k_m2g_point reads it.
+extern "C" int bn254s_hash_to_g2_batch(bn254s_ctx* c, const uint64_t* inputs, size_t n, size_t len, uint64_t* out_points) {
+  if (!c || !out_points || (!inputs && len) || n == 0 || n >= (size_t)UINT_MAX) return BN254S_E_INVALID_ARG;
+  HIP_TRY(c, hipSetDevice(c->device));
+  u64* d_in = c->words("h2f.in", n * len + 1);
+  u64* d = c->words("m2g.batch", m2g_batch_words(n));
+  if (!d_in || !d) return BN254S_E_OOM;
+  if (len) HIP_TRY(c, hipMemcpyAsync(d_in, inputs, n * len * 8, hipMemcpyHostToDevice, c->stream));
+  k_hash_to_fq2<<<(unsigned)((n + 63) / 64), 64, 0, c->stream>>>(d_in, n, len, d);
+  HIP_TRY(c, hipGetLastError());
+  return map_to_g2_on_device(c, "hash_to_g2_batch", d, n, out_points);
 }

@@ -85,6 +85,10 @@ def load_library():
     lib.bn254s_g2_recover_from_x.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
     lib.bn254s_g2_subgroup_check_batch.argtypes = [vp, vp, C.c_size_t, vp]
     lib.bn254s_g2_subgroup_check.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(vp)]
+    lib.bn254s_g2_clear_cofactor_batch.argtypes = [vp, vp, C.c_size_t, vp, vp]
+    lib.bn254s_g2_clear_cofactor.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
+    lib.bn254s_map_to_g2_batch.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.bn254s_hash_to_g2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bn254s_hash_to_fq2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bn254s_ctl_values.argtypes = [C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_commit_values.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
@@ -433,6 +437,54 @@ class Context:
         self._check(self._lib.bn254s_g2_subgroup_check(self._h, C.byref(params), _ptr(points), _ptr(offsets), n, per_proof,
                                                        flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_g2_subgroup_check")
         return flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+
+    def g2_clear_cofactor_batch(self, points):
+        """points [n,16] (x.c0, x.c1, y.c0, y.c1, canonical, below p, on the twist curve) -> (images [n,16], finite [n] uint8):
+        images[i] = [h] P_i for the cofactor h = 2p - r, a member of the r-torsion subgroup, zeros where finite[i] is 0 ([h] P_i is
+        the point at infinity), by the endomorphism form on the device, no proof (bn254s_g2_clear_cofactor_batch).  A coordinate
+        >= p or a point off the curve raises (-1, the message names the first such point)."""
+        points = np.ascontiguousarray(points, dtype=np.uint64)
+        n = points.shape[0]
+        images, finite = np.zeros((n, 16), np.uint64), np.zeros(n, np.uint8)
+        self._check(self._lib.bn254s_g2_clear_cofactor_batch(self._h, _ptr(points), n, _ptr(images), finite.ctypes.data_as(C.c_void_p)),
+                    "bn254s_g2_clear_cofactor_batch")
+        return images, finite
+
+    def g2_clear_cofactor(self, points, offsets, per_proof=128, params: Optional[Params] = None):
+        """points [n,16], offsets [n,16] (R_i: random subgroup points, set_random_g2) -> (images [n,16], finite [n], g2_jobs [n,20]
+        = h | P_i, proofs): the front-end plus the G2 proofs of the n jobs (h, P_i, R_i), cut into ceil(n / per_proof) proofs like
+        prove_batch(1, ...); output i is R_i + [h]P_i = R_i + images[i], R_i exactly where finite[i] is 0
+        (bn254s_g2_clear_cofactor).  Check it with verify_g2_clear_cofactor."""
+        params = params or default_params()
+        points, offsets = (np.ascontiguousarray(a, dtype=np.uint64) for a in (points, offsets))
+        n = points.shape[0]
+        if offsets.shape != (n, 16):
+            raise ValueError(f"offsets {offsets.shape} for {n} points")
+        k = (n + per_proof - 1) // per_proof
+        images, finite, jobs = np.zeros((n, 16), np.uint64), np.zeros(n, np.uint8), np.zeros((n, 20), np.uint64)
+        outs = (C.c_void_p * k)()
+        self._check(self._lib.bn254s_g2_clear_cofactor(self._h, C.byref(params), _ptr(points), _ptr(offsets), n, per_proof,
+                                                       _ptr(images), finite.ctypes.data_as(C.c_void_p), _ptr(jobs), outs),
+                    "bn254s_g2_clear_cofactor")
+        return images, finite, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+
+    def map_to_g2_batch(self, u):
+        """u [n,8] (c0, c1, canonical, below p) -> points [n,16]: the reference's native map_to_g2 (hash_to_g2.rs:113-148) on the
+        device, no proof - the points map_to_g2 returns for the same u (bn254s_map_to_g2_batch)."""
+        u = np.ascontiguousarray(u, dtype=np.uint64)
+        n = u.shape[0]
+        pts = np.zeros((n, 16), np.uint64)
+        self._check(self._lib.bn254s_map_to_g2_batch(self._h, _ptr(u), n, _ptr(pts)), "bn254s_map_to_g2_batch")
+        return pts
+
+    def hash_to_g2_batch(self, inputs):
+        """inputs [n, len] Goldilocks elements -> points [n,16]: hash_to_g2 (hash_to_g2.rs:40-43), hash_to_fq2 of every row and
+        map_to_g2 of the result without leaving the device, no proof (bn254s_hash_to_g2_batch)."""
+        inputs = np.ascontiguousarray(inputs, dtype=np.uint64)
+        n, ln = inputs.shape
+        pts = np.zeros((n, 16), np.uint64)
+        self._check(self._lib.bn254s_hash_to_g2_batch(self._h, _ptr(inputs) if ln else None, n, ln, _ptr(pts)), "bn254s_hash_to_g2_batch")
+        return pts
 
     def hash_to_fq2_batch(self, inputs: np.ndarray) -> np.ndarray:
         """inputs [n, len] Goldilocks elements -> u [n, 8]: hash_to_fq2 (hash_to_g2.rs:76-87) of every row, on the device."""
@@ -812,6 +864,65 @@ def verify_g2_subgroup(points, offsets, flags, g2_jobs, proofs, per_proof, ctx: 
             if back != bool(flags[i]):
                 raise VerifyError(f"{tag}: flag {i} is {int(flags[i])}, the proven offset_{i} + [r] point_{i} "
                                   f"{'equals' if back else 'differs from'} offset_{i}")
+
+
+def verify_g2_clear_cofactor(points, offsets, images, finite, g2_jobs, proofs, per_proof, ctx: Optional[Context] = None,
+                             params: Optional[Params] = None):
+    """Checks a g2_clear_cofactor: job i is h | P_i (h = 2p - r from tools/synth.py), every coordinate of P_i is below p and P_i
+    is on the twist curve in Python integer arithmetic, every G2 proof (kind 1) verifies against its jobs (h, P_i, offsets[i])
+    (Context.verify with a context, else verify_host), and the proven output of job i equals offsets[i] + images[i] in Python
+    integer arithmetic where finite[i] is 1 and offsets[i] word for word where it is 0 (where images[i] must be zeros).
+    `proofs`: objects with `words`, `degree_bits` and `outputs`, such as Proof.  Returns None or raises VerifyError naming the
+    first point, job, image or proof that fails."""
+    from tools import synth
+
+    tag, p = "g2_clear_cofactor", synth.P
+    points, offsets, images, g2_jobs = (np.ascontiguousarray(a, dtype=np.uint64) for a in (points, offsets, images, g2_jobs))
+    finite = np.asarray(finite).reshape(-1)
+    n = points.shape[0]
+    if points.shape != (n, 16) or offsets.shape != (n, 16) or images.shape != (n, 16) or g2_jobs.shape != (n, 20) or finite.shape != (n,):
+        raise VerifyError(f"{tag}: shapes: points {points.shape}, offsets {offsets.shape}, images {images.shape}, finite {finite.shape}, "
+                          f"g2_jobs {g2_jobs.shape}")
+    if len(proofs) != (n + per_proof - 1) // per_proof:
+        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    h_words = np.array(synth._to_words(synth.G2_COFACTOR), np.uint64)
+    for i in range(n):
+        pt = synth.g2_from_words(points[i])
+        if max(pt[0] + pt[1]) >= p:
+            raise VerifyError(f"{tag}: point {i} has a coordinate that is not below p")
+        if not synth.g2_on_curve(pt):
+            raise VerifyError(f"{tag}: point {i} is not on the twist curve")
+        if not np.array_equal(g2_jobs[i, :4], h_words):
+            raise VerifyError(f"{tag}: scalar of job {i} != h")
+        if not np.array_equal(g2_jobs[i, 4:], points[i]):
+            raise VerifyError(f"{tag}: x of job {i} != point {i}")
+    scalars = np.ascontiguousarray(g2_jobs[:, :4])
+    for k, pr in enumerate(proofs):
+        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
+        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 16)
+        if outs.shape[0] != hi - lo:
+            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+        s_, x_, o_ = (np.ascontiguousarray(a[lo:hi]) for a in (scalars, points, offsets))
+        try:
+            if ctx is not None:
+                ctx.verify(1, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+            else:
+                verify_host(1, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+        except VerifyError as e:
+            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+        for i in range(lo, hi):
+            if finite[i]:
+                img = synth.g2_from_words(images[i])
+                if max(img[0] + img[1]) >= p or not synth.g2_on_curve(img):
+                    raise VerifyError(f"{tag}: image {i} is not a point of the twist curve with coordinates below p")
+                want = synth.g2_add_complete(synth.g2_from_words(offsets[i]), img)
+                if want is None or not np.array_equal(outs[i - lo], synth.g2_points_to_words([want])[0]):
+                    raise VerifyError(f"{tag}: image {i}: the proven offset_{i} + [h] point_{i} != offset_{i} + image_{i}")
+            else:
+                if images[i].any():
+                    raise VerifyError(f"{tag}: image {i} is not zeros although finite[{i}] is 0")
+                if not np.array_equal(outs[i - lo], offsets[i]):
+                    raise VerifyError(f"{tag}: image {i}: finite[{i}] is 0, the proven offset_{i} + [h] point_{i} differs from offset_{i}")
 
 
 class BatchInFlight:

@@ -158,6 +158,18 @@ def finish(output_words, offset_pt):
     return synth.g2_add(out, neg)
 
 
+def map_to_g2(u):
+    """The reference's native map_to_g2 (hash_to_g2.rs:113-148) for one u in Fq2: the candidates, the choice by "is a square" of
+    the norms of g(x1) and g(x2), the root with the sign of u, and [h] over every bit of the cofactor (mul_by_cofactor).  The
+    point bn254s_map_to_g2 returns, and bn254s_map_to_g2_batch without proofs."""
+    x1, x2, _ = candidates(u)
+    pt = select_point(u, fq_is_square(f2_norm(g(x1))), fq_is_square(f2_norm(g(x2))))
+    img = synth.g2_clear_cofactor(pt)
+    if img is None:
+        raise ValueError("the image is the point at infinity")
+    return img
+
+
 def inputs(n: int, seed: int = 0x706C6F6E6B7932 + 5):
     """n uniform Fq2 inputs u."""
     rng = synth.Xoshiro256ss(seed)

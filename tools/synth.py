@@ -564,3 +564,18 @@ def g2_subgroup_inputs(n: int, seed: int, with_classes: bool = False):
         classes.append((c, d))
     out = (g2_points_to_words(pts), np.array(flags, dtype=np.uint8))
     return out + (classes,) if with_classes else out
+
+
+# ---- G2 cofactor clearing: P -> [h]P, h = 2p - r -------------------------------------------------------------------------
+def g2_clear_cofactor(pt):
+    """The definition: [h] pt over every bit of h = 2p - r (pt on the twist curve, any order); None for infinity."""
+    return g2_mul_unreduced(G2_COFACTOR, pt)
+
+
+def g2_clear_cofactor_psi(pt):
+    """The form csrc/g2_cofactor.hip uses: h = p - 1 + t and [p] = [t] psi - psi^2 (psi^2 - t psi + p = 0, t = 6 x0^2 + 1) give
+    [h]P = T + psi(T + P) - psi^2(P) with T = [6 x0^2]P = [6 x0]([x0]P): two short scalar multiplications, affine complete
+    additions, no use of h."""
+    t = g2_mul_unreduced(6 * X0, g2_mul_unreduced(X0, pt))
+    s = g2_add_complete(t, psi(g2_add_complete(t, pt)))
+    return g2_add_complete(s, g2_neg(psi(psi(pt))))
