@@ -33,15 +33,15 @@
  * GPU / per host thread).  A batch opened with bn254s_prove_batch_begin stays in flight after _begin returns: until its _end
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
  * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x /
- * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor) queues
+ * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor / bn254s_job_outputs) queues
  * behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its own, so it can never share
  * device state with a proof of the open batch; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
  * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch,
- * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch and the front-end halves of
- * bn254s_g1_recover_from_x, bn254s_g2_recover_from_x, bn254s_g2_subgroup_check and bn254s_g2_clear_cofactor, like those of
- * bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub" for the
- * subgroup check, "g2cof" and "g2cof.link" for cofactor clearing, "m2g.batch" for the proof-free map) and are independent of
- * open batches.
+ * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch, bn254s_job_outputs_batch and the front-end
+ * halves of bn254s_g1_recover_from_x, bn254s_g2_recover_from_x, bn254s_g2_subgroup_check, bn254s_g2_clear_cofactor and
+ * bn254s_job_outputs, like those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under
+ * keys of their own ("g2sub" for the subgroup check, "g2cof" and "g2cof.link" for cofactor clearing, "m2g.batch" for the
+ * proof-free map, "jobout" for the job outputs) and are independent of open batches.
  */
 #ifndef BN254_STARK_H
 #define BN254_STARK_H
@@ -378,6 +378,35 @@ int bn254s_map_to_g2_batch(bn254s_ctx* ctx, const uint64_t* u /* n x 8, each coo
  * bn254s_map_to_g2_batch, u staying on the device.  Errors as bn254s_map_to_g2_batch (u is below p by construction). */
 int bn254s_hash_to_g2_batch(bn254s_ctx* ctx, const uint64_t* inputs /* n x len */, size_t n, size_t len,
                             uint64_t* out_points /* n x 16 */);
+/* Job outputs without a proof: what the reference's G1SingleGenerator / G2SingleGenerator / FqSingleGenerator compute with
+ * arkworks, one call after the other on one host thread (src/generators/{g1,g2,fq}/single.rs:48-52), so that the rest of the
+ * circuit can go on before the STARK of the same jobs is proven.  kind as in bn254s_prove_batch: 0 = G1, 1 = G2, 2 = Fq exp;
+ * scalars n x 4 words, x and offset n x 8 (G1) / n x 16 (G2) words, x n x 4 words for Fq exp, whose offset is not read and may be
+ * NULL (bn254s_prove_batch ignores it too).  For n independent jobs, each with its own scalar, the device computes
+ *   outputs_out[i] = s_i x_i + offset_i (kinds 0, 1: affine, every coordinate below p) or x_i^s_i (kind 2; 0^0 = 1, as the trace has it);
+ *   finite_out[i]  = 1, or 0 where s_i x_i + offset_i is the point at infinity: outputs_out[i] is zero words then.  Always 1 for kind 2.
+ * by a fixed-window ladder over the lane's own scalar, one lane per job (csrc/job_outputs.hip; DESIGN.md "Job outputs").  The
+ * scalar is used as the full 256-bit value, never reduced modulo r: on the twist s x != (s mod r) x for x outside the r-torsion
+ * subgroup, and the G2 trace walks all 256 bits.  Every exceptional case of the group law is answered: s = 0 or a multiple of the
+ * order of x (the output is the offset), an accumulator that meets a table entry or its negative, offset = +-[s]x.
+ * BN254S_E_INVALID_ARG: a NULL argument (offset only for kinds 0, 1), n == 0, n >= UINT_MAX, a kind outside 0..2; a coordinate
+ * >= p, found on the host before any device work; a point x_i or offset_i that is not on its curve, found on the device.  The last
+ * two name the argument and the smallest such i in bn254s_last_error ("x_<i>", "offset_<i>") and happen before anything is written
+ * to outputs_out or finite_out.
+ * bn254s_job_outputs_batch: device front-end only, no proof. */
+int bn254s_job_outputs_batch(bn254s_ctx* ctx, int kind, const uint64_t* scalars /* n x 4 */, const uint64_t* x,
+                             const uint64_t* offset, size_t n, uint64_t* outputs_out /* n x (8 | 16 | 4) */,
+                             uint8_t* finite_out /* n */);
+/* The front-end followed by bn254s_prove_batch of the same jobs, cut into ceil(n / per_proof) proofs.  The outputs of the proofs
+ * (bn254s_proof_outputs, computed bit by bit by the trace generator on its own), concatenated, must equal the front-end's word
+ * for word: a mismatch is BN254S_E_INTERNAL and bn254s_last_error names the job.  A job whose output is the point at infinity
+ * cannot be proven (the reference's targets cannot hold it): BN254S_E_INVALID_POINT naming the first such i, before any proof is
+ * started.  Errors of the proofs themselves pass through unchanged - BN254S_E_INVALID_POINT where a running sum of the trace meets
+ * a + (-a), which can happen for a job whose output is finite.  outputs_out is written on success only; on any error every proof
+ * of the call is freed and its slot in proofs_out is NULL.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work
+ * (invalid arguments are reported first; the context is checked last). */
+int bn254s_job_outputs(bn254s_ctx* ctx, int kind, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
+                       const uint64_t* offset, size_t n, size_t per_proof, uint64_t* outputs_out, bn254s_proof** proofs_out);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

@@ -38,6 +38,26 @@ __device__ __forceinline__ P pt_add_complete(const P& p, const P& q) {
   if (pt_add(p, q, r) == 2) r = pt_infinity((const P*)nullptr);
   return r;
 }
+__device__ __forceinline__ g1j pt_double(const g1j& p) { return g1_double(p); }
+__device__ __forceinline__ g2j pt_double(const g2j& p) { return g2_double(p); }
+// The same complete law with the formulas of g1_add / g2_add in another order: u2 and s2 are consumed as they are made, so
+// fewer field elements are alive at the widest point.  For code that has a table or a second point beside the sum: on the twist
+// pt_add_complete puts 340 bytes per lane into scratch memory there (g2_cofactor.hip), this form none.
+template <class P>
+__device__ __forceinline__ P pt_add_lean(const P& p, const P& q) {
+  if (pt_inf(q)) return p;
+  if (pt_inf(p)) return q;
+  const auto z1z1 = fe_sqr(p.z), z2z2 = fe_sqr(q.z);
+  const auto u1 = fe_mul(p.x, z2z2), s1 = fe_mul(fe_mul(p.y, q.z), z2z2);
+  const auto h = fe_sub(fe_mul(q.x, z1z1), u1), rr = fe_sub(fe_mul(fe_mul(q.y, p.z), z1z1), s1);
+  if (fe_is_zero(h)) return fe_is_zero(rr) ? pt_double(p) : pt_infinity((const P*)nullptr);
+  const auto hh = fe_sqr(h), hhh = fe_mul(h, hh), v = fe_mul(u1, hh);
+  P r;
+  r.x = fe_sub(fe_sub(fe_sqr(rr), hhh), fe_add(v, v));
+  r.y = fe_sub(fe_mul(rr, fe_sub(v, r.x)), fe_mul(s1, hhh));
+  r.z = fe_mul(fe_mul(p.z, q.z), h);
+  return r;
+}
 
 // LDS image of a point: word w of lane k at sh[w * 256 + k] (conflict-free for consecutive lanes)
 __device__ __forceinline__ void lds_put_fq(u64* sh, int w0, int k, const fq& v) {

@@ -55,22 +55,9 @@ __device__ __forceinline__ g2j g2_madd(const g2j& p, const fq2& x2, const fq2& y
   return r;
 }
 // p + q, complete like pt_add_complete (chain_scan.h): either operand may be O, equal points double, opposite points give O.
-// The formulas of g2_add in another order: u2 and s2 are consumed as they are made, so fewer Fq2 values are alive at the widest
-// point - with pt_add_complete in its place the compiler puts 340 bytes per lane into scratch memory, with this form none.
-__device__ __forceinline__ g2j g2_add_lean(const g2j& p, const g2j& q) {
-  if (pt_inf(q)) return p;
-  if (pt_inf(p)) return q;
-  const fq2 z1z1 = fq2_sqr(p.z), z2z2 = fq2_sqr(q.z);
-  const fq2 u1 = fq2_mul(p.x, z2z2), s1 = fq2_mul(fq2_mul(p.y, q.z), z2z2);
-  const fq2 h = fq2_sub(fq2_mul(q.x, z1z1), u1), rr = fq2_sub(fq2_mul(fq2_mul(q.y, p.z), z1z1), s1);
-  if (fq2_is_zero(h)) return fq2_is_zero(rr) ? g2_double(p) : pt_infinity((const g2j*)nullptr);
-  const fq2 hh = fq2_sqr(h), hhh = fq2_mul(h, hh), v = fq2_mul(u1, hh);
-  g2j r;
-  r.x = fq2_sub(fq2_sub(fq2_sqr(rr), hhh), fq2_dbl(v));
-  r.y = fq2_sub(fq2_mul(rr, fq2_sub(v, r.x)), fq2_mul(s1, hhh));
-  r.z = fq2_mul(fq2_mul(p.z, q.z), h);
-  return r;
-}
+// It is pt_add_lean (chain_scan.h) on the twist: with pt_add_complete in its place the compiler puts 340 bytes per lane into
+// scratch memory, with this form none.
+__device__ __forceinline__ g2j g2_add_lean(const g2j& p, const g2j& q) { return pt_add_lean(p, q); }
 // t == -(x, y) for a Jacobian t and an affine, finite (x, y), by cross-multiplication: X == x Z^2 and Y == -y Z^3.  O is not
 // the negative of a finite point.
 __device__ __forceinline__ bool g2_is_neg_of_affine(const g2j& t, const fq2& x, const fq2& y) {

@@ -89,6 +89,8 @@ def load_library():
     lib.bn254s_g2_clear_cofactor.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
     lib.bn254s_map_to_g2_batch.argtypes = [vp, vp, C.c_size_t, vp]
     lib.bn254s_hash_to_g2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+    lib.bn254s_job_outputs_batch.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, vp, vp]
+    lib.bn254s_job_outputs.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(vp)]
     lib.bn254s_hash_to_fq2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bn254s_ctl_values.argtypes = [C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_commit_values.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
@@ -493,6 +495,41 @@ class Context:
         out = np.zeros((n, 8), np.uint64)
         self._check(self._lib.bn254s_hash_to_fq2_batch(self._h, _ptr(inputs) if ln else None, n, ln, _ptr(out)), "bn254s_hash_to_fq2_batch")
         return out
+
+    def _job_arrays(self, kind, scalars, x, offset):
+        scalars, x = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x))
+        # a kind outside 0..2 goes on to the library, which answers BN254S_E_INVALID_ARG before it reads an array
+        pw = {0: 8, 1: 16, 2: 4}.get(kind, x.shape[-1] if x.ndim == 2 else 0)
+        offset = None if kind == 2 or offset is None else np.ascontiguousarray(offset, dtype=np.uint64)
+        n = scalars.shape[0]
+        if scalars.shape != (n, 4) or x.shape != (n, pw) or (offset is not None and offset.shape != (n, pw)):
+            raise ValueError(f"job_outputs: scalars {scalars.shape}, x {x.shape}, offset {None if offset is None else offset.shape}")
+        return pw, n, scalars, x, offset
+
+    def job_outputs_batch(self, kind, scalars, x, offset=None):
+        """kind 0 = G1, 1 = G2, 2 = Fq exp (no offset); scalars [n,4], x and offset [n, 8 | 16 | 4] -> (outputs [n, 8 | 16 | 4],
+        finite [n] uint8): outputs[i] = s_i x_i + offset_i, or x_i^s_i, for n independent jobs on the device, no proof
+        (bn254s_job_outputs_batch) - what the reference's SingleGenerators compute.  Scalars are the full 256-bit values.  Where
+        finite[i] is 0 the output is the point at infinity and outputs[i] is zeros.  A coordinate >= p or a point off its curve
+        raises (-1, the message names the argument and the first such job)."""
+        pw, n, scalars, x, offset = self._job_arrays(kind, scalars, x, offset)
+        outs, finite = np.zeros((n, pw), np.uint64), np.zeros(n, np.uint8)
+        self._check(self._lib.bn254s_job_outputs_batch(self._h, kind, _ptr(scalars), _ptr(x), _ptr(offset), n, _ptr(outs),
+                                                       finite.ctypes.data_as(C.c_void_p)), "bn254s_job_outputs_batch")
+        return outs, finite
+
+    def job_outputs(self, kind, scalars, x, offset=None, per_proof=128, params: Optional[Params] = None):
+        """-> (outputs [n, 8 | 16 | 4], proofs): the front-end plus prove_batch(kind, ...) of the same jobs, the outputs of the
+        proofs checked word for word against the front-end's (bn254s_job_outputs).  A job whose output is the point at infinity
+        raises (-4, the message names it).  Check the result with verify_job_outputs."""
+        params = params or default_params()
+        pw, n, scalars, x, offset = self._job_arrays(kind, scalars, x, offset)
+        k = (n + per_proof - 1) // per_proof
+        outs = np.zeros((n, pw), np.uint64)
+        slots = (C.c_void_p * k)()
+        self._check(self._lib.bn254s_job_outputs(self._h, kind, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof,
+                                                 _ptr(outs), slots), "bn254s_job_outputs")
+        return outs, [Proof(self._lib, C.c_void_p(slots[i])) for i in range(k)]
 
     def ctl_values(self, kind, scalars, x, offset, outputs):
         """(input rows [n, 81|145|33], output rows [n, 33|65|17]): the extra looking values of the two CTLs."""
@@ -923,6 +960,45 @@ def verify_g2_clear_cofactor(points, offsets, images, finite, g2_jobs, proofs, p
                     raise VerifyError(f"{tag}: image {i} is not zeros although finite[{i}] is 0")
                 if not np.array_equal(outs[i - lo], offsets[i]):
                     raise VerifyError(f"{tag}: image {i}: finite[{i}] is 0, the proven offset_{i} + [h] point_{i} differs from offset_{i}")
+
+
+def verify_job_outputs(kind, scalars, x, offset, outputs, proofs, per_proof, ctx: Optional[Context] = None,
+                       params: Optional[Params] = None):
+    """Checks a job_outputs: the outputs of proof k are outputs[lo .. hi - 1] word for word for its jobs lo .. hi - 1, and every
+    proof verifies against its jobs (s_i, x_i, offset_i) and those outputs (Context.verify with a context, else verify_host).
+    kind 0 = G1, 1 = G2, 2 = Fq exp (offset None).  `proofs`: objects with `words`, `degree_bits` and `outputs`, such as Proof.
+    Returns None or raises VerifyError naming the first output or proof that fails."""
+    if kind not in (0, 1, 2):
+        raise ValueError(f"job_outputs: kind {kind} (0 = G1, 1 = G2, 2 = Fq exp)")
+    tag, pw = "job_outputs", {0: 8, 1: 16, 2: 4}[kind]
+    scalars, x, outputs = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, outputs))
+    offset = None if kind == 2 or offset is None else np.ascontiguousarray(offset, dtype=np.uint64)
+    n = scalars.shape[0]
+    if (scalars.shape != (n, 4) or x.shape != (n, pw) or outputs.shape != (n, pw) or (kind != 2 and offset is None) or
+            (offset is not None and offset.shape != (n, pw))):
+        raise VerifyError(f"{tag}: shapes: scalars {scalars.shape}, x {x.shape}, offset {None if offset is None else offset.shape}, "
+                          f"outputs {outputs.shape}")
+    if len(proofs) != (n + per_proof - 1) // per_proof:
+        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    for k, pr in enumerate(proofs):
+        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
+        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, pw)
+        if outs.shape[0] != hi - lo:
+            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+        bad = np.nonzero(np.any(outs != outputs[lo:hi], axis=1))[0]
+        if bad.size:
+            raise VerifyError(f"{tag}: output {lo + int(bad[0])} is not the proven output of proof {k}")
+    for k, pr in enumerate(proofs):
+        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
+        s_, x_ = np.ascontiguousarray(scalars[lo:hi]), np.ascontiguousarray(x[lo:hi])
+        o_ = None if offset is None else np.ascontiguousarray(offset[lo:hi])
+        try:
+            if ctx is not None:
+                ctx.verify(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+            else:
+                verify_host(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+        except VerifyError as e:
+            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
 
 
 class BatchInFlight:

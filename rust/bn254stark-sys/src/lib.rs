@@ -113,4 +113,13 @@ extern "C" {
     pub fn bn254s_g2_msm(ctx: *mut Bn254sCtx, params: *const Bn254sParams, scalars: *const u64, x: *const u64, offset: *const u64,
                          n: usize, per_proof: usize, result: *mut u64, offsets_out: *mut u64, proofs: *mut *mut Bn254sProof) -> c_int;
     pub fn bn254s_hash_to_fq2(input: *const u64, len: usize, out: *mut u64) -> c_int;
+    /// the outputs s_i x_i + offset_i (kind 0 = G1, 1 = G2) or x_i^s_i (kind 2, offset unused) of n jobs on the device, no proof:
+    /// what the SingleGenerators compute (src/generators/{g1,g2,fq}/single.rs:48-52).  outputs_out: n x (8 | 16 | 4) words, zeros
+    /// where finite_out[i] is 0 (the output is the point at infinity)
+    pub fn bn254s_job_outputs_batch(ctx: *mut Bn254sCtx, kind: c_int, scalars: *const u64, x: *const u64, offset: *const u64,
+                                    n: usize, outputs_out: *mut u64, finite_out: *mut u8) -> c_int;
+    /// the front-end plus ceil(n / per_proof) proofs of the same jobs (bn254s_prove_batch), their outputs checked word for word
+    pub fn bn254s_job_outputs(ctx: *mut Bn254sCtx, kind: c_int, params: *const Bn254sParams, scalars: *const u64, x: *const u64,
+                              offset: *const u64, n: usize, per_proof: usize, outputs_out: *mut u64,
+                              proofs_out: *mut *mut Bn254sProof) -> c_int;
 }
