@@ -464,6 +464,15 @@ int bn254s_selftest_fq_inv(bn254s_ctx* ctx, const uint64_t* x, size_t n, uint64_
  * BN254S_E_INVALID_ARG: a NULL argument, an unknown group, an operand of p or more, x = 0 in group 1, a Z = 0 in group 3
  * (the curve code has no point at infinity); nothing is launched then. */
 int bn254s_selftest_fq(bn254s_ctx* ctx, int group, const uint64_t* in, size_t n, uint64_t* out);
+/* Debug: the LogUp range-check columns (csrc/aux.hip) of a caller's trace, through the same code the provers run.  trace:
+ * column-major [ncols][rows] canonical words (host), rows a power of two in 64 .. 2^20; the n_rc columns from rc_begin on are the
+ * range-checked ones, table_col / freq_col the table and its multiplicities; betas: the two challenges (canonical).  With
+ * m = ceil(n_rc / 2), out[2 (m + 1)][rows] = per challenge the helper columns h_k = 1/(beta + f_2k) + 1/(beta + f_2k+1) (the
+ * last of an odd n_rc has one term) and then Z: Z_0 = 0, Z_{i+1} = Z_i + sum_k h_k(i) - freq(i) / (beta + table(i)).
+ * BN254S_E_INVALID_ARG: a NULL argument, a shape outside the above, a word of p or more (nothing is launched then).
+ * BN254S_E_INTERNAL: a range-checked or table value above 65535 (found on the device; `out` is not meaningful then). */
+int bn254s_selftest_logup(bn254s_ctx* ctx, const uint64_t* trace, size_t rows, int ncols, int rc_begin, int n_rc, int table_col,
+                          int freq_col, const uint64_t betas[2], uint64_t* out);
 /* Trace generation only: column-major trace[W][rows] copied to the host buffer.
  * kind: 0 = G1 scalar mul (W 781), 1 = G2 scalar mul (W 1295), 2 = Fq exp (W 427; offset ignored). */
 int bn254s_generate_trace(bn254s_ctx* ctx, int kind, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset,

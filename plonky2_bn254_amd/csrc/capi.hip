@@ -6,6 +6,7 @@
 #include "merkle.h"
 #include "trace_g1.h"
 #include "fq_selftest.h"
+#include "aux.h"
 #include "poseidon_dev.h"
 
 // one per translation unit: loads its code object (defined at the end of each .hip file)
@@ -513,6 +514,48 @@ int bn254s_selftest_fq_inv(bn254s_ctx* c, const uint64_t* x, size_t n, uint64_t*
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(out, d + 4 * n, 64 * n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BN254S_OK;
+}
+
+// Debug: the LogUp columns of a caller's trace through aux_build, the path the provers run (aux.hip).  Every word is checked to be
+// canonical here; values above 65535 in the range-checked or the table column are the kernels' business (masked index, error word).
+int bn254s_selftest_logup(bn254s_ctx* c, const uint64_t* trace, size_t rows, int ncols, int rc_begin, int n_rc, int table_col,
+                          int freq_col, const uint64_t betas[2], uint64_t* out) {
+  if (!c || !trace || !betas || !out) return BN254S_E_INVALID_ARG;
+  if (rows < 64 || rows > ((size_t)1 << 20) || (rows & (rows - 1)) || ncols < 1 || ncols > 4096 || n_rc < 1 || rc_begin < 0 ||
+      rc_begin > ncols - n_rc || table_col < 0 || table_col >= ncols || freq_col < 0 || freq_col >= ncols)
+    return BN254S_E_INVALID_ARG;
+  if (betas[0] >= GL_P || betas[1] >= GL_P) return BN254S_E_INVALID_ARG;
+  for (size_t k = 0; k < (size_t)ncols * rows; k++)
+    if (trace[k] >= GL_P) return BN254S_E_INVALID_ARG;
+  StarkShape sh;
+  sh.W = ncols;
+  sh.rc_begin = rc_begin;
+  sh.rc_end = rc_begin + n_rc;
+  sh.table_col = table_col;
+  sh.freq_col = freq_col;
+  sh.n_ctl = 0;
+  memset(&sh.ctl, 0, sizeof(sh.ctl));
+  const size_t tw = (size_t)ncols * rows, aw = (size_t)sh.n_lookup_cols() * rows;
+  HIP_TRY(c, hipSetDevice(c->device));
+  u64* d = c->words("lu.io", tw + aw + aux_scratch_words(sh, rows) + 2);
+  if (!d) return BN254S_E_OOM;
+  u64* d_aux = d + tw;
+  u64* d_scr = d_aux + aw;
+  int* d_err = (int*)(d_scr + aux_scratch_words(sh, rows));
+  const u64 gammas[2] = {0, 0};
+  int h_err = 0;
+  HIP_TRY(c, hipMemcpyAsync(d, trace, 8 * tw, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(d_err, 0, 8, c->stream));
+  aux_build(sh, d, rows, betas, gammas, d_aux, d_scr, d_err, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(out, d_aux, 8 * aw, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (h_err) {
+    c->set_err("LogUp columns: device error " + std::to_string(h_err) + " (a range-checked or table value above 65535)");
+    return h_err;
+  }
   return BN254S_OK;
 }
 

@@ -14,11 +14,8 @@ static constexpr size_t FRI_OPENING_ZQ_WORDS = 2 * 256 * 4, FRI_OPENING_TABLE_WO
 void fri_opening_tables(unsigned log_r, gl2 zeta, gl2 zeta_next, u64* d_tables, hipStream_t st);
 void fri_openings(const u64* d_coeffs, size_t N, unsigned log_r, int npolys, const u64* d_tables, u64* d_out, hipStream_t st);
 
-// d_out[2N][2]: sum_b alpha^(k_b) (F_b(x) - F_b(z_b)) / (x - z_b) on the LDE domain, bit-reversed order
-void fri_combine(const StarkShape& sh, const u64* d_tl, const u64* d_al, const u64* d_ql, const u64* d_apow, const u64* d_xs,
-                 gl2 zeta, gl2 zeta_next, gl2 r0, gl2 r1, gl2 r2, gl2 alpha, size_t M2, u64* d_out, hipStream_t st);
-
-// The same from coefficient vectors (no resident LDE): comb[6][N] = the three alpha-weighted sums (f1, quotient part of f0, f2; c0 / c1
+// d_out[2N][2]: sum_b alpha^(k_b) (F_b(x) - F_b(z_b)) / (x - z_b) on the LDE domain, bit-reversed order, in two steps from the
+// coefficient vectors (no resident LDE needed): comb[6][N] = the three alpha-weighted sums (f1, quotient part of f0, f2; c0 / c1
 // each) formed on the coefficients; after the ordinary LDE of those six columns fri_combine_final applies the point-wise part.
 void fri_combine_coeffs(const StarkShape& sh, const u64* d_tcoef, const u64* d_acoef, const u64* d_qcoef, const u64* d_apow, size_t N,
                         u64* d_comb, hipStream_t st);

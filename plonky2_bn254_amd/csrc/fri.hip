@@ -7,9 +7,9 @@
 //   fri_proof_of_work               - grinding (smallest witness; upstream takes any)
 //   fri_prover_query_rounds         - leaf rows and Merkle paths at the 84 query indices
 // The reference prover works on coefficients (divide_by_linear, reduce_with_powers, coset FFT per layer).
-// Here everything after the openings stays in the evaluation domain: the batched quotient is formed
-// point-wise on the 2N-point coset from the LDE values that are already resident in HBM, and a layer is
-// folded by interpolating each 16-point coset {x w_16^i} (one leaf = 16 consecutive bit-reversed values)
+// Here the alpha-weighted sums of the batched quotient are formed on the coefficient vectors and extended once
+// (six columns); everything after that stays in the evaluation domain: the division is point-wise on the
+// 2N-point coset, and a layer is folded by interpolating each 16-point coset {x w_16^i} (one leaf = 16 consecutive bit-reversed values)
 // and evaluating at beta.  Both give the same field elements as the coefficient route (the folded
 // polynomial sum_j beta^j P_j(Y) restricted to Y = x^16), with no extension-field FFT at all.
 #include "fri.h"
@@ -99,11 +99,11 @@ void fri_openings(const u64* d_coeffs, size_t N, unsigned log_r, int npolys, con
   k_openings<<<dim3(npolys, (unsigned)R), 256, 0, st>>>(d_coeffs, N, log_r, d_tables, d_tables + FRI_OPENING_ZQ_WORDS, d_out);
 }
 
-// ---- batched quotient on the LDE domain ---------------------------------------------------------------
+// ---- batched quotient -----------------------------------------------------------------------------------
 struct CombineArgs {
-  const u64* tl;   // trace LDE [W][2N]
-  const u64* al;   // aux LDE [A][2N]
-  const u64* ql;   // quotient LDE [4][2N]
+  const u64* tl;   // trace coefficients [W][N]
+  const u64* al;   // aux coefficients [A][N]
+  const u64* ql;   // quotient coefficients [4][N]
   const u32* apow3; // alpha^j cut in 22-bit limbs: 8 u32 per j = (c0: w0 w1 w2 -, c1: w0 w1 w2 -), j < W + A + 4
   const u64* xs;   // x_j (bit-reversed order)
   int W, A, num_lookup;
@@ -111,59 +111,18 @@ struct CombineArgs {
   gl2 r0, r1, r2;      // F_b(z_b) from the openings
   gl2 a_n1n2, a_n2;    // alpha^(n1+n2), alpha^(n2)
   u64* out;            // [2N][2] extension values, bit-reversed order
-  size_t M2;
+  size_t M2;           // points per column: N for k_fri_combine_coeffs, 2N for k_fri_combine_final
 };
 
-__global__ __launch_bounds__(256) void k_fri_combine(CombineArgs A) {
-  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= A.M2) return;
-  const size_t M2 = A.M2;
-  // sum alpha^j v_j, components c0 / c1 (Acc3: carry-free columns, weights through scalar loads)
-  Acc3 g0, g1, z0, z1, q0, q1;
-  acc3_init(g0);
-  acc3_init(g1);
-  acc3_init(z0);
-  acc3_init(z1);
-  acc3_init(q0);
-  acc3_init(q1);
-  auto mad2 = [&](Acc3& a0, Acc3& a1, u64 v, const u32* e) {
-    const u32 v0 = (u32)v & M22, v1 = (u32)(v >> 22) & M22, v2 = (u32)(v >> 44);
-    acc3_mad(a0, v0, v1, v2, e[0], e[1], e[2]);
-    acc3_mad(a1, v0, v1, v2, e[4], e[5], e[6]);
-  };
-#pragma unroll 8
-  for (int c = 0; c < A.W; c++) mad2(g0, g1, A.tl[(size_t)c * M2 + j], A.apow3 + 8 * (size_t)c);  // unrolled: loads in flight
-  const u32* ap = A.apow3 + 8 * (size_t)A.W;
-#pragma unroll 8
-  for (int c = 0; c < A.num_lookup; c++) mad2(g0, g1, A.al[(size_t)c * M2 + j], ap + 8 * (size_t)c);
-  for (int c = A.num_lookup; c < A.A; c++) {  // the CTL Z columns also enter the batch opened at 1
-    u64 v = A.al[(size_t)c * M2 + j];
-    mad2(g0, g1, v, ap + 8 * (size_t)c);
-    mad2(z0, z1, v, A.apow3 + 8 * (size_t)(c - A.num_lookup));
-  }
-  gl2 f1 = gl2_make(acc3_red(g0), acc3_red(g1));
-  ap = A.apow3 + 8 * (size_t)(A.W + A.A);
-  for (int c = 0; c < 4; c++) mad2(q0, q1, A.ql[(size_t)c * M2 + j], ap + 8 * (size_t)c);
-  gl2 f0 = gl2_add(f1, gl2_make(acc3_red(q0), acc3_red(q1)));
-  gl2 f2 = gl2_make(acc3_red(z0), acc3_red(z1));
-  const u64 x = A.xs[j];
-  gl2 xe = gl2_make(x, 0);
-  gl2 t0 = gl2_mul(gl2_sub(f0, A.r0), gl2_inv(gl2_sub(xe, A.zeta)));
-  gl2 t1 = gl2_mul(gl2_sub(f1, A.r1), gl2_inv(gl2_sub(xe, A.zeta_next)));
-  gl2 t2 = gl2_mul_base(gl2_sub(f2, A.r2), gl_inv(gl_sub(x, 1)));
-  gl2 r = gl2_add(gl2_add(gl2_mul(t0, A.a_n1n2), gl2_mul(t1, A.a_n2)), t2);
-  reinterpret_cast<ulonglong2*>(A.out)[j] = make_ulonglong2(r.c0, r.c1);
-}
-
-// ---- the same batch polynomial from COEFFICIENTS (prover.hip "stream": no LDE of the commitments is resident) -----------------
-// The three alpha-weighted sums of k_fri_combine are linear in the polynomials, so they can be formed on the coefficient vectors
-// (all commitments share one coefficient layout): comb[0,1] = f1 (trace + aux), comb[2,3] = the quotient part of f0, comb[4,5]
-// = f2 (CTL Z columns), components c0 / c1.  The six columns then go through the ordinary LDE and k_fri_combine_final applies the
-// point-wise part.  Same field elements as k_fri_combine (sums of the same products).
+// The three alpha-weighted sums of the batch are linear in the polynomials, so they are formed on the COEFFICIENT vectors (all
+// commitments share one coefficient layout; N points instead of the 2N of the LDE, and no LDE of the commitments has to be
+// resident): comb[0,1] = f1 (trace + aux), comb[2,3] = the quotient part of f0, comb[4,5] = f2 (CTL Z columns), components c0 /
+// c1.  The six columns then go through the ordinary LDE and k_fri_combine_final applies the point-wise part.  Same field elements
+// as sums over the LDE values (sums of the same products).  Acc3: carry-free columns, weights through scalar loads.
 __global__ __launch_bounds__(256) void k_fri_combine_coeffs(CombineArgs A, u64* __restrict__ comb) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= A.M2) return;
-  const size_t M2 = A.M2;  // (= N here: the arrays are coefficient vectors)
+  const size_t M2 = A.M2;  // (= N here)
   Acc3 g0, g1, z0, z1, q0, q1;
   acc3_init(g0);
   acc3_init(g1);
@@ -195,6 +154,12 @@ __global__ __launch_bounds__(256) void k_fri_combine_coeffs(CombineArgs A, u64* 
   comb[4 * M2 + j] = acc3_red(z0);
   comb[5 * M2 + j] = acc3_red(z1);
 }
+// a * conj(a) = c0^2 - 7 c1^2 (the denominator of gl2_inv)
+__device__ __forceinline__ u64 gl2_norm(gl2 a) {
+  const u64 t = gl_mul(a.c1, a.c1);
+  const u64 t7 = gl_add(gl_add(gl_dbl(gl_dbl(t)), gl_dbl(t)), t);
+  return gl_sub(gl_mul(a.c0, a.c0), t7);
+}
 __global__ __launch_bounds__(256) void k_fri_combine_final(CombineArgs A, const u64* __restrict__ cl /* [6][M2] LDE of comb */) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= A.M2) return;
@@ -204,9 +169,20 @@ __global__ __launch_bounds__(256) void k_fri_combine_final(CombineArgs A, const 
   const gl2 f2 = gl2_make(cl[4 * M2 + j], cl[5 * M2 + j]);
   const u64 x = A.xs[j];
   gl2 xe = gl2_make(x, 0);
-  gl2 t0 = gl2_mul(gl2_sub(f0, A.r0), gl2_inv(gl2_sub(xe, A.zeta)));
-  gl2 t1 = gl2_mul(gl2_sub(f1, A.r1), gl2_inv(gl2_sub(xe, A.zeta_next)));
-  gl2 t2 = gl2_mul_base(gl2_sub(f2, A.r2), gl_inv(gl_sub(x, 1)));
+  // 1/(x - zeta), 1/(x - g zeta), 1/(x - 1): an extension inverse is conj / norm, so the three cost ONE base-field inversion of
+  // the product of the two norms and x - 1 (Montgomery's trick) plus six products.  A zero denominator inverts to 0 as gl_inv
+  // does, without touching the other two.
+  const gl2 d0 = gl2_sub(xe, A.zeta), d1 = gl2_sub(xe, A.zeta_next);
+  const u64 n0 = gl2_norm(d0), n1 = gl2_norm(d1), n2 = gl_sub(x, 1);
+  const u64 m0 = n0 ? n0 : 1, m1 = n1 ? n1 : 1, m2 = n2 ? n2 : 1;
+  const u64 m01 = gl_mul(m0, m1);
+  u64 ri = gl_inv(gl_mul(m01, m2));
+  const u64 i2 = n2 ? gl_mul(ri, m01) : 0;
+  ri = gl_mul(ri, m2);  // 1 / (m0 m1)
+  const u64 i0 = n0 ? gl_mul(ri, m1) : 0, i1 = n1 ? gl_mul(ri, m0) : 0;
+  gl2 t0 = gl2_mul(gl2_sub(f0, A.r0), gl2_make(gl_mul(d0.c0, i0), gl_mul(gl_neg(d0.c1), i0)));
+  gl2 t1 = gl2_mul(gl2_sub(f1, A.r1), gl2_make(gl_mul(d1.c0, i1), gl_mul(gl_neg(d1.c1), i1)));
+  gl2 t2 = gl2_mul_base(gl2_sub(f2, A.r2), i2);
   gl2 r = gl2_add(gl2_add(gl2_mul(t0, A.a_n1n2), gl2_mul(t1, A.a_n2)), t2);
   reinterpret_cast<ulonglong2*>(A.out)[j] = make_ulonglong2(r.c0, r.c1);
 }
@@ -265,12 +241,6 @@ __global__ void k_gather_rows(const u64* __restrict__ lde, size_t M2, const u32*
 }
 void fri_gather_rows(const u64* d_lde, size_t M2, int ncols, const u32* d_indices, int nq, u64* d_out, hipStream_t st) {
   k_gather_rows<<<dim3((unsigned)((nq + 63) / 64), ncols), 64, 0, st>>>(d_lde, M2, d_indices, nq, d_out);
-}
-
-void fri_combine(const StarkShape& sh, const u64* d_tl, const u64* d_al, const u64* d_ql, const u64* d_apow, const u64* d_xs,
-                 gl2 zeta, gl2 zeta_next, gl2 r0, gl2 r1, gl2 r2, gl2 alpha, size_t M2, u64* d_out, hipStream_t st) {
-  CombineArgs A = combine_args(sh, d_tl, d_al, d_ql, d_apow, d_xs, zeta, zeta_next, r0, r1, r2, alpha, M2, d_out);
-  k_fri_combine<<<(unsigned)((M2 + 255) / 256), 256, 0, st>>>(A);
 }
 
 // ---- arity-16 fold in the evaluation domain ---------------------------------------------------------------

@@ -349,11 +349,10 @@ static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params&
   } else {
     mem.drop("ldechunk");
     mem.drop("sponge");
-    mem.drop("comb");
   }
   u64* d_ldechunk = stream ? mem.words("ldechunk", (size_t)CH * M2) : nullptr;  // the LDE of one column chunk
   u64* d_sponge = stream ? mem.words("sponge", (size_t)12 * M2) : nullptr;      // sponge states of the streaming leaf hash
-  u64* d_comb = stream ? mem.words("comb", (size_t)6 * N + (size_t)6 * M2) : nullptr;  // FRI batch polynomial: coefficients | LDE
+  u64* d_comb = mem.words("comb", (size_t)6 * N + (size_t)6 * M2);  // FRI batch polynomial: coefficients | LDE
   u64* d_tlde = stream ? d_ldechunk : mem.words("tlde", (size_t)W * M2);
   const size_t tree_words = merkle_tree_digests(log_m2, P.cap_height) * 4;
   u64* d_trees = mem.words("trees", 3 * tree_words);
@@ -398,7 +397,7 @@ static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params&
     }
   }
   if (!d_hist || !d_in || !d_tvals || !d_tcoef || !d_tmp || !d_tlde || !d_trees || !d_avals || !d_acoef || !d_alde || !d_scr || !d_q ||
-      !d_tabs || !d_open || !d_fri || !d_fritrees || !d_qout || (stream && (!d_ldechunk || !d_sponge || !d_comb))) {
+      !d_tabs || !d_open || !d_fri || !d_fritrees || !d_qout || !d_comb || (stream && (!d_ldechunk || !d_sponge))) {
     err = mem.err;
     mem.release();  // a workspace that could not be completed is given back: the context stays usable for smaller proofs
     return BN254S_E_OOM;
@@ -722,13 +721,12 @@ static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params&
     CHK(hipStreamSynchronize(st));
     BigSection big(c, st, BIG_EXCL);
     sb(ST_FRI);
-    if (stream) {  // the batch polynomial on the coefficient vectors, one LDE of its six columns, then the point-wise part
-      fri_combine_coeffs(sh, d_tcoef, d_acoef, d_qcoef, d_apow, N, d_comb, st);
-      do_lde(d_comb, d_comb + (size_t)6 * N, 6);
-      fri_combine_final(sh, d_comb + (size_t)6 * N, pt.x, zeta, zeta_next, r0, r1, r2, fri_alpha, M2, d_fri, st);
-    } else {
-      fri_combine(sh, d_tlde, d_alde, d_qlde, d_apow, pt.x, zeta, zeta_next, r0, r1, r2, fri_alpha, M2, d_fri, st);
-    }
+    // The batch polynomial is linear in the committed polynomials: its three alpha-weighted sums are formed on the coefficient
+    // vectors (N points, not the 2N of the LDE; in the compact workspace d_acoef is d_avals, still live: the openings above read
+    // it), then one LDE of the six sum columns, then the point-wise part.  The same field elements as summing the LDE values.
+    fri_combine_coeffs(sh, d_tcoef, d_acoef, d_qcoef, d_apow, N, d_comb, st);
+    do_lde(d_comb, d_comb + (size_t)6 * N, 6);
+    fri_combine_final(sh, d_comb + (size_t)6 * N, pt.x, zeta, zeta_next, r0, r1, r2, fri_alpha, M2, d_fri, st);
   }
   std::vector<std::vector<u64>> layer_caps(L, std::vector<u64>(CAPW));
   std::vector<const u64*> layer_vals(L), layer_trees(L);

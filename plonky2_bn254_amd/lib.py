@@ -103,6 +103,8 @@ def load_library():
     lib.bn254s_selftest_leaf_hash.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp]
     lib.bn254s_selftest_fq_inv.argtypes = [vp, vp, C.c_size_t, vp]
     lib.bn254s_selftest_fq.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
+    if hasattr(lib, "bn254s_selftest_logup"):   # (an older build loaded through BN254S_LIB for an A/B run has no such entry)
+        lib.bn254s_selftest_logup.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.bn254s_bench_copy.argtypes = [vp, C.c_size_t, C.c_int]
     lib.bn254s_bench_leafhash.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]
     lib.bn254s_g1_generate_trace.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
@@ -624,6 +626,18 @@ class Context:
         assert rows.ndim == 2 and rows.shape[1] == wi, (rows.shape, wi)
         out = np.zeros((rows.shape[0], wo), np.uint64)
         self._check(self._lib.bn254s_selftest_fq(self._h, group, _ptr(rows), rows.shape[0], _ptr(out)), "bn254s_selftest_fq")
+        return out
+
+    def selftest_logup(self, trace: np.ndarray, rc_begin: int, n_rc: int, table_col: int, freq_col: int, betas) -> np.ndarray:
+        """Debug: the LogUp columns of trace[ncols][rows] through the provers' aux_build: out[2 (m + 1)][rows], per challenge the
+        m = ceil(n_rc / 2) helper columns and Z (bn254s_selftest_logup)."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        assert trace.ndim == 2
+        ncols, rows = trace.shape
+        b = np.array([int(betas[0]), int(betas[1])], dtype=np.uint64)
+        out = np.zeros((2 * ((n_rc + 1) // 2 + 1), rows), np.uint64)
+        self._check(self._lib.bn254s_selftest_logup(self._h, _ptr(trace), rows, ncols, rc_begin, n_rc, table_col, freq_col, _ptr(b),
+                                                    _ptr(out)), "bn254s_selftest_logup")
         return out
 
     def poseidon_permute(self, states: np.ndarray) -> np.ndarray:
