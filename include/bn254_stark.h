@@ -33,15 +33,16 @@
  * GPU / per host thread).  A batch opened with bn254s_prove_batch_begin stays in flight after _begin returns: until its _end
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
  * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x /
- * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor / bn254s_job_outputs) queues
+ * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor / bn254s_job_outputs / bn254s_map_to_g1) queues
  * behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its own, so it can never share
  * device state with a proof of the open batch; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
  * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch,
- * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch, bn254s_job_outputs_batch and the front-end
- * halves of bn254s_g1_recover_from_x, bn254s_g2_recover_from_x, bn254s_g2_subgroup_check, bn254s_g2_clear_cofactor and
- * bn254s_job_outputs, like those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under
- * keys of their own ("g2sub" for the subgroup check, "g2cof" and "g2cof.link" for cofactor clearing, "m2g.batch" for the
- * proof-free map, "jobout" for the job outputs) and are independent of open batches.
+ * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch, bn254s_job_outputs_batch,
+ * bn254s_hash_to_fq_batch, bn254s_map_to_g1_batch, bn254s_hash_to_g1_batch and the front-end halves of bn254s_g1_recover_from_x,
+ * bn254s_g2_recover_from_x, bn254s_g2_subgroup_check, bn254s_g2_clear_cofactor, bn254s_job_outputs and bn254s_map_to_g1, like
+ * those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub"
+ * for the subgroup check, "g2cof" and "g2cof.link" for cofactor clearing, "m2g.batch" for the proof-free map, "jobout" for the
+ * job outputs, "m2g1", "h2f1.in" and "h2f1.out" for map_to_g1 and hash_to_fq) and are independent of open batches.
  */
 #ifndef BN254_STARK_H
 #define BN254_STARK_H
@@ -378,6 +379,47 @@ int bn254s_map_to_g2_batch(bn254s_ctx* ctx, const uint64_t* u /* n x 8, each coo
  * bn254s_map_to_g2_batch, u staying on the device.  Errors as bn254s_map_to_g2_batch (u is below p by construction). */
 int bn254s_hash_to_g2_batch(bn254s_ctx* ctx, const uint64_t* inputs /* n x len */, size_t n, size_t len,
                             uint64_t* out_points /* n x 16 */);
+/* hash_to_fq: the first coordinate of hash_to_fq2 (src/utils/hash_to_g2.rs:76-87) - the same Poseidon challenger over `len`
+ * Goldilocks elements, stopped after 16 challenges, whose low 32 bits are the little-endian limbs of a 512-bit integer that is
+ * reduced modulo p.  out = words 0..3 of bn254s_hash_to_fq2 for every input: u in Fq (4 words), the input of bn254s_map_to_g1.
+ * Host only, no context. */
+int bn254s_hash_to_fq(const uint64_t* input, size_t len, uint64_t* out /* 4 */);
+/* n inputs of `len` elements each at once, on the device (inputs[n][len] -> out[n][4]); same values as n calls of the above. */
+int bn254s_hash_to_fq_batch(bn254s_ctx* ctx, const uint64_t* inputs, size_t n, size_t len, uint64_t* out /* n x 4 */);
+/* map_to_g1: u in Fq -> a point of G1, total and of one shape for every u.  The reference has no such gadget: it is its map_to_g2
+ * (src/utils/hash_to_g2.rs:113-148: Shallue-van de Woestijne, Z = 1) read over Fq on y^2 = x^3 + 3, the circuit one writes with
+ * FqTarget::is_square (src/fields/fq.rs:283-295), sqrt_with_sgn (fq.rs:266-281), inv (src/fields/inv.rs: inv(0) = 0), sgn
+ * (src/fields/sgn.rs:9-18: the parity of the canonical value) and G1Target::g_circuit (src/curves/g1.rs:43-51).  With
+ * g(x) = x^3 + 3, nz2 = -1/2, tv4 = sqrt(-12) = (p - 12)^((p+1)/4) (ark-ff's root for p = 3 mod 4; it is even) and tv6 = -16/3:
+ *   tv1 = 4 u^2;  tv2 = 1 + tv1;  tv1 = 1 - tv1;  tv3 = inv(tv1 tv2)
+ *   tv5 = u tv1 tv3 tv4;  x1 = nz2 - tv5;  x2 = nz2 + tv5;  t = tv2^2 tv3;  x3 = 1 + tv6 t^2
+ *   x = x1 if g(x1) is a square, else x2 if g(x2) is a square, else x3;  y = sqrt(g(x)) with the parity of u
+ * G1 has the cofactor 1: nothing is cleared and no offset is needed.  For every u_i (4 words, canonical: some u_i >= p is
+ * BN254S_E_INVALID_ARG, found on the host before any device work and before anything is written, and bn254s_last_error names the
+ * first such i as "u_<i>") the device computes the candidates with one inversion and g(x_j)^((p+1)/4) for all three
+ * (csrc/map_to_g1.hip):
+ *   out_points[i]    = (x, y), 8 words, both below p, on the curve, y of the parity of u_i (y is never zero: -3 is no cube);
+ *   sq_flags[2i + j] = 1 iff g(x_{j+1}) is a square in Fq, j = 0, 1 (2n bytes; may be NULL);
+ *   fq_jobs[2i + j]  = (p-1)/2 | g(x_{j+1}) (8 words; may be NULL): the Fq-exp job whose output is that Legendre symbol, in the
+ *                      order of bn254s_map_to_g2's fq_jobs.
+ * A root that squares to neither g nor -g, or no candidate with a square g (device self-checks): BN254S_E_INTERNAL.  Nothing is
+ * written on an error.  bn254s_map_to_g1_batch: device front-end only, no proof. */
+int bn254s_map_to_g1_batch(bn254s_ctx* ctx, const uint64_t* u /* n x 4, canonical < p */, size_t n,
+                           uint64_t* out_points /* n x 8 */, uint8_t* sq_flags /* may be NULL: 2n bytes */,
+                           uint64_t* fq_jobs /* may be NULL: 2n x 8 = scalar (p-1)/2 | g(x_j) */);
+/* hash_to_g1 for n inputs of `len` Goldilocks elements each: bn254s_hash_to_fq_batch and then bn254s_map_to_g1_batch, u staying
+ * on the device.  Errors as bn254s_map_to_g1_batch (u is below p by construction). */
+int bn254s_hash_to_g1_batch(bn254s_ctx* ctx, const uint64_t* inputs /* n x len */, size_t n, size_t len,
+                            uint64_t* out_points /* n x 8 */);
+/* The front-end plus the Fq-exp proofs of the 2n Legendre jobs, cut into ceil(2n / per_proof) proofs exactly as
+ * bn254s_prove_batch (kind 2) cuts them.  The outputs of the proofs are checked word for word against the flags: job k must give
+ * 1 where sq_flags[k] is 1 and p - 1 where it is 0; a mismatch is BN254S_E_INTERNAL.  out_points, sq_flags and fq_jobs are written
+ * on success only.  On any error every proof of the call is freed and its slot in fq_proofs is NULL.  n >= 2^31 (2n must stay
+ * below 2^32) is BN254S_E_INVALID_ARG; per_proof > 16384: BN254S_E_UNSUPPORTED before any device work (invalid arguments are
+ * reported first; the context is checked last). */
+int bn254s_map_to_g1(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* u /* n x 4 */, size_t n, size_t per_proof,
+                     uint64_t* out_points /* n x 8 */, uint8_t* sq_flags /* may be NULL: 2n */,
+                     uint64_t* fq_jobs /* may be NULL: 2n x 8 */, bn254s_proof** fq_proofs /* ceil(2n / per_proof) */);
 /* Job outputs without a proof: what the reference's G1SingleGenerator / G2SingleGenerator / FqSingleGenerator compute with
  * arkworks, one call after the other on one host thread (src/generators/{g1,g2,fq}/single.rs:48-52), so that the rest of the
  * circuit can go on before the STARK of the same jobs is proven.  kind as in bn254s_prove_batch: 0 = G1, 1 = G2, 2 = Fq exp;

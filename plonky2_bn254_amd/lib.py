@@ -92,6 +92,12 @@ def load_library():
     lib.bn254s_job_outputs_batch.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_job_outputs.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(vp)]
     lib.bn254s_hash_to_fq2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+    if hasattr(lib, "bn254s_map_to_g1"):   # (as for bn254s_selftest_logup below: an older build in an A/B run has none of them)
+        lib.bn254s_hash_to_fq.argtypes = [vp, C.c_size_t, vp]
+        lib.bn254s_hash_to_fq_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+        lib.bn254s_map_to_g1_batch.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+        lib.bn254s_hash_to_g1_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+        lib.bn254s_map_to_g1.argtypes = [vp, C.POINTER(Params), vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
     lib.bn254s_ctl_values.argtypes = [C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_commit_values.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
     lib.bn254s_bench_ntt.argtypes = [vp, C.c_size_t, C.c_int, C.POINTER(C.c_float)]
@@ -498,6 +504,49 @@ class Context:
         self._check(self._lib.bn254s_hash_to_fq2_batch(self._h, _ptr(inputs) if ln else None, n, ln, _ptr(out)), "bn254s_hash_to_fq2_batch")
         return out
 
+    def hash_to_fq_batch(self, inputs: np.ndarray) -> np.ndarray:
+        """inputs [n, len] Goldilocks elements -> u [n, 4]: hash_to_fq, the first coordinate of hash_to_fq2 (hash_to_g2.rs:76-87),
+        of every row, on the device (bn254s_hash_to_fq_batch)."""
+        inputs = np.ascontiguousarray(inputs, dtype=np.uint64)
+        n, ln = inputs.shape
+        out = np.zeros((n, 4), np.uint64)
+        self._check(self._lib.bn254s_hash_to_fq_batch(self._h, _ptr(inputs) if ln else None, n, ln, _ptr(out)), "bn254s_hash_to_fq_batch")
+        return out
+
+    def map_to_g1_batch(self, u):
+        """u [n,4] (canonical, below p) -> (points [n,8], sq_flags [2n] uint8, fq_jobs [2n,8]): the Shallue-van de Woestijne map
+        onto y^2 = x^3 + 3 (the reference's map_to_g2, hash_to_g2.rs:113-148, read over Fq) on the device, no proof.
+        sq_flags[2i + j] = 1 iff g(x_{j+1}) of input i is a square, fq_jobs[2i + j] = (p-1)/2 | g(x_{j+1}), points[i] = (x, y) for
+        the first candidate with a square g, y of the parity of u_i (bn254s_map_to_g1_batch)."""
+        u = np.ascontiguousarray(u, dtype=np.uint64)
+        n = u.shape[0]
+        pts, flags, jobs = np.zeros((n, 8), np.uint64), np.zeros(2 * n, np.uint8), np.zeros((2 * n, 8), np.uint64)
+        self._check(self._lib.bn254s_map_to_g1_batch(self._h, _ptr(u), n, _ptr(pts), flags.ctypes.data_as(C.c_void_p), _ptr(jobs)),
+                    "bn254s_map_to_g1_batch")
+        return pts, flags, jobs
+
+    def hash_to_g1_batch(self, inputs):
+        """inputs [n, len] Goldilocks elements -> points [n,8]: hash_to_fq of every row and map_to_g1 of the result without
+        leaving the device, no proof (bn254s_hash_to_g1_batch)."""
+        inputs = np.ascontiguousarray(inputs, dtype=np.uint64)
+        n, ln = inputs.shape
+        pts = np.zeros((n, 8), np.uint64)
+        self._check(self._lib.bn254s_hash_to_g1_batch(self._h, _ptr(inputs) if ln else None, n, ln, _ptr(pts)), "bn254s_hash_to_g1_batch")
+        return pts
+
+    def map_to_g1(self, u, per_proof=128, params: Optional[Params] = None):
+        """-> (points [n,8], sq_flags [2n], fq_jobs [2n,8], proofs): the front-end plus the Fq-exp proofs of the 2n Legendre jobs,
+        cut into ceil(2n / per_proof) proofs like prove_batch(2, ...) (bn254s_map_to_g1).  Check it with verify_map_to_g1."""
+        params = params or default_params()
+        u = np.ascontiguousarray(u, dtype=np.uint64)
+        n = u.shape[0]
+        k = (2 * n + per_proof - 1) // per_proof
+        pts, flags, jobs = np.zeros((n, 8), np.uint64), np.zeros(2 * n, np.uint8), np.zeros((2 * n, 8), np.uint64)
+        outs = (C.c_void_p * k)()
+        self._check(self._lib.bn254s_map_to_g1(self._h, C.byref(params), _ptr(u), n, per_proof, _ptr(pts),
+                                               flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_map_to_g1")
+        return pts, flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+
     def _job_arrays(self, kind, scalars, x, offset):
         scalars, x = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x))
         # a kind outside 0..2 goes on to the library, which answers BN254S_E_INVALID_ARG before it reads an array
@@ -802,6 +851,64 @@ def verify_g1_recover(xs, points, flags, fq_jobs, proofs, per_proof, ctx: Option
                 raise VerifyError(f"{tag}: y of point {i} is not the even root of x_{i}^3 + 3 below p")
         elif py != 0:
             raise VerifyError(f"{tag}: point {i} is not (x_{i}, 0) although its flag is clear")
+
+
+def verify_map_to_g1(u, points, sq_flags, fq_jobs, proofs, per_proof, ctx: Optional[Context] = None, params: Optional[Params] = None):
+    """Checks a map_to_g1: jobs 2i and 2i + 1 are ((p-1)/2, g(x1)) and ((p-1)/2, g(x2)) for the candidates of u_i in Python integer
+    arithmetic (tools/map_to_g1_ref.py), every Fq-exp proof verifies against its jobs (Context.verify with a context, else
+    verify_host), the proven Legendre symbol of job k is 1 or p - 1 and agrees with sq_flags[k], and points[i] is the point that
+    the flags select: the first candidate with a square g(x), y its root with the parity of u_i.  `proofs`: objects with `words`,
+    `degree_bits` and `outputs`, such as Proof.  Returns None or raises VerifyError naming the first input or proof that fails."""
+    from tools import map_to_g1_ref as ref
+    from tools import synth
+
+    tag, p = "map_to_g1", synth.P
+    u, points, fq_jobs = (np.ascontiguousarray(a, dtype=np.uint64) for a in (u, points, fq_jobs))
+    sq_flags = np.asarray(sq_flags).reshape(-1)
+    n = u.shape[0]
+    if u.shape != (n, 4) or points.shape != (n, 8) or fq_jobs.shape != (2 * n, 8) or sq_flags.shape != (2 * n,):
+        raise VerifyError(f"{tag}: shapes: u {u.shape}, points {points.shape}, sq_flags {sq_flags.shape}, fq_jobs {fq_jobs.shape}")
+    if len(proofs) != (2 * n + per_proof - 1) // per_proof:
+        raise VerifyError(f"{tag}: {len(proofs)} proofs for {2 * n} jobs of {per_proof} per proof")
+    us = []
+    for i in range(n):
+        ui = synth.words_to_int(u[i])
+        if ui >= p:
+            raise VerifyError(f"{tag}: u_{i} is not below p")
+        us.append(ui)
+        for j, xc in enumerate(ref.candidates(ui)[:2]):
+            if synth.words_to_int(fq_jobs[2 * i + j, :4]) != (p - 1) // 2:
+                raise VerifyError(f"{tag}: scalar of job {2 * i + j} (input {i}) != (p - 1)/2")
+            if synth.words_to_int(fq_jobs[2 * i + j, 4:]) != ref.g(xc):
+                raise VerifyError(f"{tag}: x of job {2 * i + j} != g(x{j + 1}) of input {i}")
+    for k, pr in enumerate(proofs):
+        lo, hi = k * per_proof, min(2 * n, (k + 1) * per_proof)
+        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 4)
+        if outs.shape[0] != hi - lo:
+            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+        s_, x_ = np.ascontiguousarray(fq_jobs[lo:hi, :4]), np.ascontiguousarray(fq_jobs[lo:hi, 4:])
+        try:
+            if ctx is not None:
+                ctx.verify(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
+            else:
+                verify_host(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
+        except VerifyError as e:
+            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+        for j in range(lo, hi):
+            leg = synth.words_to_int(outs[j - lo])
+            if leg not in (1, p - 1):
+                raise VerifyError(f"{tag}: output {j} of proof {k} (input {j // 2}) is neither 1 nor p - 1")
+            if (leg == 1) != bool(sq_flags[j]):
+                raise VerifyError(f"{tag}: flag {j} (g(x{j % 2 + 1}) of input {j // 2}) is {int(sq_flags[j])}, the proven Legendre "
+                                  f"symbol of job {j} is {'1' if leg == 1 else 'p - 1'}")
+    for i in range(n):
+        try:
+            want = ref.select_point(us[i], bool(sq_flags[2 * i]), bool(sq_flags[2 * i + 1]))
+        except ValueError:
+            raise VerifyError(f"{tag}: g of the candidate that the flags of input {i} select is not a square") from None
+        if (synth.words_to_int(points[i, :4]), synth.words_to_int(points[i, 4:])) != want:
+            raise VerifyError(f"{tag}: point {i} is not the image of input {i}: the first candidate with a square g(x) and the root "
+                              "of the parity of u")
 
 
 def verify_g2_recover(xs, sgns, points, flags, fq_jobs, proofs, per_proof, ctx: Optional[Context] = None,

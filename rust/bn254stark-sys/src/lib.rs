@@ -113,6 +113,15 @@ extern "C" {
     pub fn bn254s_g2_msm(ctx: *mut Bn254sCtx, params: *const Bn254sParams, scalars: *const u64, x: *const u64, offset: *const u64,
                          n: usize, per_proof: usize, result: *mut u64, offsets_out: *mut u64, proofs: *mut *mut Bn254sProof) -> c_int;
     pub fn bn254s_hash_to_fq2(input: *const u64, len: usize, out: *mut u64) -> c_int;
+    /// hash_to_fq: the first coordinate of hash_to_fq2 (out: 4 words); host only
+    pub fn bn254s_hash_to_fq(input: *const u64, len: usize, out: *mut u64) -> c_int;
+    /// map_to_g1 of n inputs u (4 words each, below p) on the device, no proof: out_points n x 8 words; sq_flags (2n bytes) and
+    /// fq_jobs (2n x 8 words: (p-1)/2 | g(x_j)) may be null
+    pub fn bn254s_map_to_g1_batch(ctx: *mut Bn254sCtx, u: *const u64, n: usize, out_points: *mut u64, sq_flags: *mut u8,
+                                  fq_jobs: *mut u64) -> c_int;
+    /// the front-end plus ceil(2n / per_proof) Fq-exp proofs of the Legendre jobs, their outputs checked against the flags
+    pub fn bn254s_map_to_g1(ctx: *mut Bn254sCtx, params: *const Bn254sParams, u: *const u64, n: usize, per_proof: usize,
+                            out_points: *mut u64, sq_flags: *mut u8, fq_jobs: *mut u64, fq_proofs: *mut *mut Bn254sProof) -> c_int;
     /// the outputs s_i x_i + offset_i (kind 0 = G1, 1 = G2) or x_i^s_i (kind 2, offset unused) of n jobs on the device, no proof:
     /// what the SingleGenerators compute (src/generators/{g1,g2,fq}/single.rs:48-52).  outputs_out: n x (8 | 16 | 4) words, zeros
     /// where finite_out[i] is 0 (the output is the point at infinity)
