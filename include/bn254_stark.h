@@ -214,7 +214,10 @@ int bn254s_ctl_values(int kind, const uint64_t* scalars, const uint64_t* x, cons
  * offsets: n non-infinity G2 points (what set_random_g2 supplies), 16 words each.  out_points: n x 16 words.
  * fq_jobs (may be NULL): 2n x 8 words (scalar | x) of the Legendre jobs; g2_jobs (may be NULL): n x 20 words (scalar | point)
  * of the cofactor-clearing jobs - the claimed inputs bn254s_verify needs.  fq_proofs: ceil(2n / 128) proofs, g2_proofs:
- * ceil(n / 128) proofs, each to be released with bn254s_proof_free. */
+ * ceil(n / 128) proofs, each to be released with bn254s_proof_free.
+ * Errors: BN254S_E_INVALID_ARG (a NULL pointer other than the job arrays, n == 0) before anything is touched.  On any other
+ * error - BN254S_E_INVALID_POINT with "output equals +-offset" among them: the caller draws another offset - no proof is left
+ * to the caller and every slot of fq_proofs and g2_proofs is NULL, as after the other proven calls. */
 int bn254s_map_to_g2(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* u, const uint64_t* offsets, size_t n,
                      uint64_t* out_points, uint64_t* fq_jobs, uint64_t* g2_jobs, bn254s_proof** fq_proofs,
                      bn254s_proof** g2_proofs);

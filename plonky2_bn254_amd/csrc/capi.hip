@@ -2,7 +2,7 @@
 // The proving entry points live in prover.hip.
 #include <algorithm>
 #include <cstring>
-#include "ctx.h"
+#include "proven_jobs.h"  // fq_below_p
 #include "merkle.h"
 #include "trace_g1.h"
 #include "fq_selftest.h"
@@ -561,12 +561,6 @@ int bn254s_selftest_logup(bn254s_ctx* c, const uint64_t* trace, size_t rows, int
 
 // Debug: the BN254 Fq / Fq2 device arithmetic and the cooperative pieces of the doubling chains on RAW residues (fq_selftest.hip).
 // Unreduced limbs never reach the kernels: every operand is checked to be below p here, and so is what a group cannot represent.
-static bool selftest_fq_below_p(const uint64_t* w) {
-  static const uint64_t P[4] = {0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
-  for (int j = 3; j >= 0; j--)
-    if (w[j] != P[j]) return w[j] < P[j];
-  return false;
-}
 int bn254s_selftest_fq(bn254s_ctx* c, int group, const uint64_t* in, size_t n, uint64_t* out) {
   if (!c || !in || !out || group < 0 || group >= FQ_SELFTEST_GROUPS) return BN254S_E_INVALID_ARG;
   if (n == 0) return BN254S_OK;
@@ -579,7 +573,7 @@ int bn254s_selftest_fq(bn254s_ctx* c, int group, const uint64_t* in, size_t n, u
   for (size_t i = 0; i < n; i++) {
     const uint64_t* r = in + wi * i;
     for (size_t k = 0; k < wi; k += 4)
-      if (!selftest_fq_below_p(r + k)) return BN254S_E_INVALID_ARG;
+      if (!fq_below_p(r + k)) return BN254S_E_INVALID_ARG;
     if (group == 1 && is_zero(r, 8)) return BN254S_E_INVALID_ARG;  // fq2_inv(x): x != 0
     if (group == 3 && (is_zero(r + 8, 4) || is_zero(r + 20, 4) || is_zero(r + 40, 8) || is_zero(r + 64, 8)))
       return BN254S_E_INVALID_ARG;  // Z = 0: the Jacobian code has no point at infinity

@@ -10,7 +10,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include "recover_host.h"
+#include "proven_jobs.h"
 #include "sqrt_ladder.h"
 
 namespace {
@@ -42,14 +42,6 @@ __global__ __launch_bounds__(G1R_LANES) void k_g1_recover(const u64* __restrict_
   flags[k] = square ? 1 : 0;
 }
 
-// index of the first x_i >= p, or n
-size_t first_unreduced(const uint64_t* xs, size_t n) {
-  for (size_t i = 0; i < n; i++) {
-    if (!recover_below_p(xs + 4 * i)) return i;
-  }
-  return n;
-}
-
 // the arguments that both entry points share, other than the context
 bool recover_args_ok(const uint64_t* xs, size_t n, const uint64_t* points_out, const uint8_t* flags_out) {
   return xs && points_out && flags_out && n > 0 && n < ((size_t)1 << 32);
@@ -57,11 +49,7 @@ bool recover_args_ok(const uint64_t* xs, size_t n, const uint64_t* points_out, c
 
 // The front-end into host memory: points[n x 8], flags[n], jobs[n x 8] (jobs may be NULL).  Nothing is written on an error.
 int recover_front(bn254s_ctx* c, const uint64_t* xs, size_t n, uint64_t* points, uint8_t* flags, uint64_t* jobs) {
-  const size_t bad = first_unreduced(xs, n);
-  if (bad != n) {
-    c->set_err("g1_recover_from_x: x_" + std::to_string(bad) + " is not below p");
-    return BN254S_E_INVALID_ARG;
-  }
+  if (!coords_below_p(c, "g1_recover_from_x", "x", nullptr, 1, xs, n)) return BN254S_E_INVALID_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   u64* d = c->words("g1rec", 4 * n /* xs */ + 8 * n /* points */ + 8 * n /* jobs */ + 1 /* err */ + (n + 7) / 8 /* flags */);
@@ -99,21 +87,13 @@ extern "C" int bn254s_g1_recover_from_x_batch(bn254s_ctx* c, const uint64_t* xs,
 
 extern "C" int bn254s_g1_recover_from_x(bn254s_ctx* c, const bn254s_params* params, const uint64_t* xs, size_t n, size_t per_proof,
                                         uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs, bn254s_proof** fq_proofs) {
-  // every check before device work; the context last, so that the shape checks can be exercised without one
-  if (!recover_args_ok(xs, n, points_out, flags_out) || !params || !fq_proofs || per_proof == 0 ||
-      params->struct_size != sizeof(bn254s_params))
-    return BN254S_E_INVALID_ARG;
-  const size_t n_proofs = (n + per_proof - 1) / per_proof;
-  for (size_t i = 0; i < n_proofs; i++) fq_proofs[i] = nullptr;
-  if (per_proof > G1R_PER_PROOF_MAX) {
-    if (c) c->set_err("g1_recover_from_x: per_proof above 16384 (2^23 rows, the largest Fq-exp proof)");
-    return BN254S_E_UNSUPPORTED;
-  }
-  if (!c) return BN254S_E_INVALID_ARG;
-  std::vector<u64> jobs(8 * n);
-  int rc = recover_front(c, xs, n, points_out, flags_out, jobs.data());
+  int rc = proven_args(c, "g1_recover_from_x", "Fq-exp proof", recover_args_ok(xs, n, points_out, flags_out), params, fq_proofs, n,
+                       per_proof);
   if (rc != BN254S_OK) return rc;
-  rc = recover_prove_legendre(c, "g1_recover_from_x", params, jobs, flags_out, n, per_proof, fq_proofs);
+  std::vector<u64> jobs(8 * n);
+  rc = recover_front(c, xs, n, points_out, flags_out, jobs.data());
+  if (rc != BN254S_OK) return rc;
+  rc = prove_legendre(c, "g1_recover_from_x", params, jobs, flags_out, n, per_proof, fq_proofs);
   if (rc != BN254S_OK) return rc;
   if (fq_jobs) memcpy(fq_jobs, jobs.data(), jobs.size() * 8);
   return BN254S_OK;

@@ -22,13 +22,13 @@
 // rather than kept in registers beside Q.
 #include <climits>
 #include "g2_endo.h"
+#include "proven_jobs.h"
 #include "g2_cofactor.h"
 #include "g2_cofactor_constants.inc"
 
 namespace {
 
 constexpr int G2C_LANES = 64;
-constexpr size_t G2C_PER_PROOF_MAX = 16384;  // 2^23 rows, the largest G2 proof (bn254s_prove_batch)
 
 // (X, Y, Z) -> (X/Z^2, Y/Z^3, 1) for a finite point
 __device__ __forceinline__ g2j g2_normalise(const g2j& p) {
@@ -127,11 +127,7 @@ bool front_args_ok(const uint64_t* points, size_t n, const uint64_t* images_out,
 
 // The front-end into host memory: images[n x 16], finite[n].  Nothing is written on an error.
 int cofactor_front(bn254s_ctx* c, const uint64_t* points, size_t n, uint64_t* images, uint8_t* finite) {
-  std::string what;
-  if (!g2_coords_ok("g2_clear_cofactor", "point", points, n, &what)) {
-    c->set_err(what);
-    return BN254S_E_INVALID_ARG;
-  }
+  if (!coords_below_p(c, "g2_clear_cofactor", "point", COORD_G2, 4, points, n)) return BN254S_E_INVALID_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   const size_t nb = (n + 7) / 8;  // words that hold n bytes
@@ -179,46 +175,21 @@ extern "C" int bn254s_g2_clear_cofactor_batch(bn254s_ctx* c, const uint64_t* poi
 extern "C" int bn254s_g2_clear_cofactor(bn254s_ctx* c, const bn254s_params* params, const uint64_t* points, const uint64_t* offsets,
                                         size_t n, size_t per_proof, uint64_t* images_out, uint8_t* finite_out, uint64_t* g2_jobs,
                                         bn254s_proof** g2_proofs) {
-  // every check before device work; the context last, so that the shape checks can be exercised without one
-  if (!front_args_ok(points, n, images_out, finite_out) || !offsets || !params || !g2_proofs || per_proof == 0 ||
-      params->struct_size != sizeof(bn254s_params))
-    return BN254S_E_INVALID_ARG;
-  const size_t n_proofs = (n + per_proof - 1) / per_proof;
-  for (size_t i = 0; i < n_proofs; i++) g2_proofs[i] = nullptr;
-  if (per_proof > G2C_PER_PROOF_MAX) {
-    if (c) c->set_err("g2_clear_cofactor: per_proof above 16384 (2^23 rows, the largest G2 proof)");
-    return BN254S_E_UNSUPPORTED;
-  }
-  if (!c) return BN254S_E_INVALID_ARG;
-  std::string what;
-  if (!g2_coords_ok("g2_clear_cofactor", "offset", offsets, n, &what)) {  // (the trace generator takes canonical words)
-    c->set_err(what);
-    return BN254S_E_INVALID_ARG;
-  }
-  std::vector<u64> images(16 * n);
+  int rc = proven_args(c, "g2_clear_cofactor", "G2 proof", front_args_ok(points, n, images_out, finite_out) && offsets, params,
+                       g2_proofs, n, per_proof);
+  if (rc != BN254S_OK) return rc;
+  // (the trace generator takes canonical words)
+  if (!coords_below_p(c, "g2_clear_cofactor", "offset", COORD_G2, 4, offsets, n)) return BN254S_E_INVALID_ARG;
+  std::vector<u64> images(16 * n), outs;
   std::vector<uint8_t> finite(n);
-  int rc = cofactor_front(c, points, n, images.data(), finite.data());
+  rc = cofactor_front(c, points, n, images.data(), finite.data());
   if (rc != BN254S_OK) return rc;
   std::vector<u64> h(4 * n);
   for (size_t i = 0; i < n; i++) memcpy(h.data() + 4 * i, G2C_H, 32);
-  rc = bn254s_prove_batch(c, 1, params, h.data(), points, offsets, n, per_proof, g2_proofs);
-  if (rc != BN254S_OK) return rc;  // (the batch has freed its proofs; BN254S_E_INVALID_POINT: the caller draws another offset)
+  rc = prove_and_collect(c, "g2_clear_cofactor", 1, params, h.data(), points, offsets, n, per_proof, g2_proofs, outs);
+  if (rc != BN254S_OK) return rc;  // (BN254S_E_INVALID_POINT: the caller draws another offset)
   // linkage: the trace generator computes R_i + [h]P_i bit by bit on its own; minus R_i it must be the front-end's image
   auto link = [&]() -> int {
-    std::vector<u64> outs(16 * n);
-    size_t pos = 0;
-    for (size_t i = 0; i < n_proofs; i++) {
-      const uint64_t* o;
-      size_t len = 0;
-      const size_t cnt = n - pos < per_proof ? n - pos : per_proof;
-      if (bn254s_proof_outputs(g2_proofs[i], &o, &len) != BN254S_OK || len != 16 * cnt) {
-        c->set_err("g2_clear_cofactor: proof " + std::to_string(i) + " has " + std::to_string(len / 16) + " outputs, expected " +
-                   std::to_string(cnt));
-        return BN254S_E_INTERNAL;
-      }
-      memcpy(outs.data() + 16 * pos, o, 128 * cnt);
-      pos += cnt;
-    }
     // (the proofs used the pool meanwhile: the operands travel again, in a buffer of their own)
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
@@ -251,10 +222,7 @@ extern "C" int bn254s_g2_clear_cofactor(bn254s_ctx* c, const bn254s_params* para
   };
   rc = link();
   if (rc != BN254S_OK) {
-    for (size_t i = 0; i < n_proofs; i++) {
-      bn254s_proof_free(g2_proofs[i]);
-      g2_proofs[i] = nullptr;
-    }
+    release_proofs(g2_proofs, n, per_proof);
     return rc;
   }
   memcpy(images_out, images.data(), n * 128);

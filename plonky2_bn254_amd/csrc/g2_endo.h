@@ -1,9 +1,7 @@
 // What the kernels on points of the twist curve E'(Fq2) share (g2_subgroup.hip, g2_cofactor.hip): the endomorphism
-// psi = twist^-1 o Frobenius_p o twist, psi(x, y) = (conj(x) xi^((p-1)/3), conj(y) xi^((p-1)/2)), the complete additions on
-// Jacobian coordinates, and the host-side range check of the coordinates.
+// psi = twist^-1 o Frobenius_p o twist, psi(x, y) = (conj(x) xi^((p-1)/3), conj(y) xi^((p-1)/2)), and the complete additions
+// on Jacobian coordinates.  Device code only.
 #pragma once
-#include <string>
-#include "recover_host.h"
 #include "chain_scan.h"
 #include "g2_recover_constants.inc"
 #include "g2_subgroup_constants.inc"
@@ -71,19 +69,6 @@ __device__ __forceinline__ bool g2_on_twist(const fq2& x, const fq2& y) {
   b.c0 = g2s_limbs(G2R_B_C0);
   b.c1 = g2s_limbs(G2R_B_C1);
   return fq2_eq(fq2_sqr(y), fq2_add(fq2_mul(fq2_sqr(x), x), b));
-}
-
-// The first of n points (16 canonical words each) with a coordinate that is not below p puts its message, "<tag>: <name>_<i> has
-// <coordinate> not below p", into *what; true if all are fine.
-inline bool g2_coords_ok(const char* tag, const char* name, const uint64_t* pts, size_t n, std::string* what) {
-  static const char* const coord[4] = {"x.c0", "x.c1", "y.c0", "y.c1"};
-  for (size_t i = 0; i < n; i++)
-    for (int c = 0; c < 4; c++)
-      if (!recover_below_p(pts + 16 * i + 4 * c)) {
-        *what = std::string(tag) + ": " + name + "_" + std::to_string(i) + " has " + coord[c] + " not below p";
-        return false;
-      }
-  return true;
 }
 
 }  // namespace

@@ -13,7 +13,7 @@
 //      For g.c1 == 0 delta could vanish (alpha = -g.c0), so delta = g.c0 there: the same two formulas give (t, 0) and (0, t).
 // g is never zero (the twist has odd order: no point with y = 0; equivalently -b' is not a cube in Fq2), and -1 is a non-residue
 // of Fq, so N is never zero either: "N is a square" and "the Legendre symbol of N is 1" agree, and delta, t are never zero.
-#include "recover_host.h"
+#include "proven_jobs.h"
 #include "fq2_root.h"
 
 namespace {
@@ -58,23 +58,6 @@ __global__ __launch_bounds__(G1R_LANES) void k_g2_recover(const u64* __restrict_
   flags[k] = square ? 1 : 0;
 }
 
-// The first input with a coordinate that is not below p or a sign byte above 1 puts its message into *what; true if all are fine.
-bool inputs_ok(const uint64_t* xs, const uint8_t* sgns, size_t n, std::string* what) {
-  for (size_t i = 0; i < n; i++) {
-    for (int c = 0; c < 2; c++) {
-      if (!recover_below_p(xs + 8 * i + 4 * c)) {
-        *what = "g2_recover_from_x: x_" + std::to_string(i) + " has c" + std::to_string(c) + " not below p";
-        return false;
-      }
-    }
-    if (sgns && sgns[i] > 1) {
-      *what = "g2_recover_from_x: sgn_" + std::to_string(i) + " is " + std::to_string(sgns[i]) + ", neither 0 nor 1";
-      return false;
-    }
-  }
-  return true;
-}
-
 // the arguments that both entry points share, other than the context
 bool recover_args_ok(const uint64_t* xs, size_t n, const uint64_t* points_out, const uint8_t* flags_out) {
   return xs && points_out && flags_out && n > 0 && n < ((size_t)1 << 32);
@@ -82,9 +65,12 @@ bool recover_args_ok(const uint64_t* xs, size_t n, const uint64_t* points_out, c
 
 // The front-end into host memory: points[n x 16], flags[n], jobs[n x 8] (jobs may be NULL).  Nothing is written on an error.
 int recover_front(bn254s_ctx* c, const uint64_t* xs, const uint8_t* sgns, size_t n, uint64_t* points, uint8_t* flags, uint64_t* jobs) {
-  std::string what;
-  if (!inputs_ok(xs, sgns, n, &what)) {
-    c->set_err(what);
+  // the first input with a coordinate that is not below p or a sign byte above 1 is reported, the coordinates before the sign
+  size_t s = 0;
+  while (s < n && (!sgns || sgns[s] <= 1)) s++;
+  if (!coords_below_p(c, "g2_recover_from_x", "x", COORD_FQ2, 2, xs, s < n ? s + 1 : n)) return BN254S_E_INVALID_ARG;
+  if (s < n) {
+    c->set_err("g2_recover_from_x: sgn_" + std::to_string(s) + " is " + std::to_string(sgns[s]) + ", neither 0 nor 1");
     return BN254S_E_INVALID_ARG;
   }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -131,21 +117,13 @@ extern "C" int bn254s_g2_recover_from_x_batch(bn254s_ctx* c, const uint64_t* xs,
 extern "C" int bn254s_g2_recover_from_x(bn254s_ctx* c, const bn254s_params* params, const uint64_t* xs, const uint8_t* sgns, size_t n,
                                         size_t per_proof, uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs,
                                         bn254s_proof** fq_proofs) {
-  // every check before device work; the context last, so that the shape checks can be exercised without one
-  if (!recover_args_ok(xs, n, points_out, flags_out) || !params || !fq_proofs || per_proof == 0 ||
-      params->struct_size != sizeof(bn254s_params))
-    return BN254S_E_INVALID_ARG;
-  const size_t n_proofs = (n + per_proof - 1) / per_proof;
-  for (size_t i = 0; i < n_proofs; i++) fq_proofs[i] = nullptr;
-  if (per_proof > G1R_PER_PROOF_MAX) {
-    if (c) c->set_err("g2_recover_from_x: per_proof above 16384 (2^23 rows, the largest Fq-exp proof)");
-    return BN254S_E_UNSUPPORTED;
-  }
-  if (!c) return BN254S_E_INVALID_ARG;
-  std::vector<u64> jobs(8 * n);
-  int rc = recover_front(c, xs, sgns, n, points_out, flags_out, jobs.data());
+  int rc = proven_args(c, "g2_recover_from_x", "Fq-exp proof", recover_args_ok(xs, n, points_out, flags_out), params, fq_proofs, n,
+                       per_proof);
   if (rc != BN254S_OK) return rc;
-  rc = recover_prove_legendre(c, "g2_recover_from_x", params, jobs, flags_out, n, per_proof, fq_proofs);
+  std::vector<u64> jobs(8 * n);
+  rc = recover_front(c, xs, sgns, n, points_out, flags_out, jobs.data());
+  if (rc != BN254S_OK) return rc;
+  rc = prove_legendre(c, "g2_recover_from_x", params, jobs, flags_out, n, per_proof, fq_proofs);
   if (rc != BN254S_OK) return rc;
   if (fq_jobs) memcpy(fq_jobs, jobs.data(), jobs.size() * 8);
   return BN254S_OK;

@@ -29,11 +29,11 @@
 // steps.  P stays affine through the ladder (mixed addition, Z2 = 1).
 #include <climits>
 #include "g2_endo.h"
+#include "proven_jobs.h"
 
 namespace {
 
 constexpr int G2S_LANES = 64;
-constexpr size_t G2S_PER_PROOF_MAX = 16384;  // 2^23 rows, the largest G2 proof (bn254s_prove_batch)
 
 // points: n x 16 canonical words (x.c0, x.c1, y.c0, y.c1), every coordinate below p; flags: n bytes.  A point off the curve
 // writes no flag and lowers *bad_idx to its index.
@@ -74,11 +74,7 @@ bool front_args_ok(const uint64_t* points, size_t n, const uint8_t* flags_out) {
 
 // The front-end into host memory: flags[n].  Nothing is written on an error.
 int subgroup_front(bn254s_ctx* c, const uint64_t* points, size_t n, uint8_t* flags) {
-  std::string what;
-  if (!g2_coords_ok("g2_subgroup_check", "point", points, n, &what)) {
-    c->set_err(what);
-    return BN254S_E_INVALID_ARG;
-  }
+  if (!coords_below_p(c, "g2_subgroup_check", "point", COORD_G2, 4, points, n)) return BN254S_E_INVALID_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   const size_t nb = (n + 7) / 8;  // words that hold n bytes
@@ -112,56 +108,27 @@ extern "C" int bn254s_g2_subgroup_check_batch(bn254s_ctx* c, const uint64_t* poi
 
 extern "C" int bn254s_g2_subgroup_check(bn254s_ctx* c, const bn254s_params* params, const uint64_t* points, const uint64_t* offsets,
                                         size_t n, size_t per_proof, uint8_t* flags_out, uint64_t* g2_jobs, bn254s_proof** g2_proofs) {
-  // every check before device work; the context last, so that the shape checks can be exercised without one
-  if (!front_args_ok(points, n, flags_out) || !offsets || !params || !g2_proofs || per_proof == 0 ||
-      params->struct_size != sizeof(bn254s_params))
-    return BN254S_E_INVALID_ARG;
-  const size_t n_proofs = (n + per_proof - 1) / per_proof;
-  for (size_t i = 0; i < n_proofs; i++) g2_proofs[i] = nullptr;
-  if (per_proof > G2S_PER_PROOF_MAX) {
-    if (c) c->set_err("g2_subgroup_check: per_proof above 16384 (2^23 rows, the largest G2 proof)");
-    return BN254S_E_UNSUPPORTED;
-  }
-  if (!c) return BN254S_E_INVALID_ARG;
-  std::string what;
-  if (!g2_coords_ok("g2_subgroup_check", "offset", offsets, n, &what)) {  // (the trace generator takes canonical words; before any output is written)
-    c->set_err(what);
-    return BN254S_E_INVALID_ARG;
-  }
-  std::vector<uint8_t> flags(n);
-  int rc = subgroup_front(c, points, n, flags.data());
+  int rc = proven_args(c, "g2_subgroup_check", "G2 proof", front_args_ok(points, n, flags_out) && offsets, params, g2_proofs, n,
+                       per_proof);
   if (rc != BN254S_OK) return rc;
-  std::vector<u64> r(4 * n);
+  // (the trace generator takes canonical words; before any output is written)
+  if (!coords_below_p(c, "g2_subgroup_check", "offset", COORD_G2, 4, offsets, n)) return BN254S_E_INVALID_ARG;
+  std::vector<uint8_t> flags(n);
+  rc = subgroup_front(c, points, n, flags.data());
+  if (rc != BN254S_OK) return rc;
+  std::vector<u64> r(4 * n), outs;
   for (size_t i = 0; i < n; i++) memcpy(r.data() + 4 * i, G2S_R, 32);
-  rc = bn254s_prove_batch(c, 1, params, r.data(), points, offsets, n, per_proof, g2_proofs);
-  if (rc != BN254S_OK) return rc;  // (the batch has freed its proofs; BN254S_E_INVALID_POINT: the caller draws another offset)
+  rc = prove_and_collect(c, "g2_subgroup_check", 1, params, r.data(), points, offsets, n, per_proof, g2_proofs, outs);
+  if (rc != BN254S_OK) return rc;  // (BN254S_E_INVALID_POINT: the caller draws another offset)
   // linkage: the trace generator computes R_i + [r]P_i bit by bit on its own; it must be R_i exactly where the flag is set
-  size_t pos = 0;
-  for (size_t i = 0; i < n_proofs && rc == BN254S_OK; i++) {
-    const uint64_t* o;
-    size_t len = 0;
-    const size_t cnt = n - pos < per_proof ? n - pos : per_proof;
-    if (bn254s_proof_outputs(g2_proofs[i], &o, &len) != BN254S_OK || len != 16 * cnt) {
-      c->set_err("g2_subgroup_check: proof " + std::to_string(i) + " has " + std::to_string(len / 16) + " outputs, expected " +
-                 std::to_string(cnt));
-      rc = BN254S_E_INTERNAL;
+  for (size_t j = 0; j < n; j++) {
+    const bool back = memcmp(outs.data() + 16 * j, offsets + 16 * j, 128) == 0;
+    if (back != (flags[j] != 0)) {
+      c->set_err("g2_subgroup_check: the proven R + [r]P of point " + std::to_string(j) +
+                 (back ? " is R, but its flag is clear" : " is not R, but its flag is set"));
+      release_proofs(g2_proofs, n, per_proof);
+      return BN254S_E_INTERNAL;
     }
-    for (size_t j = 0; j < cnt && rc == BN254S_OK; j++) {
-      const bool back = memcmp(o + 16 * j, offsets + 16 * (pos + j), 128) == 0;
-      if (back != (flags[pos + j] != 0)) {
-        c->set_err("g2_subgroup_check: the proven R + [r]P of point " + std::to_string(pos + j) +
-                   (back ? " is R, but its flag is clear" : " is not R, but its flag is set"));
-        rc = BN254S_E_INTERNAL;
-      }
-    }
-    pos += cnt;
-  }
-  if (rc != BN254S_OK) {
-    for (size_t i = 0; i < n_proofs; i++) {
-      bn254s_proof_free(g2_proofs[i]);
-      g2_proofs[i] = nullptr;
-    }
-    return rc;
   }
   memcpy(flags_out, flags.data(), n);
   if (g2_jobs)

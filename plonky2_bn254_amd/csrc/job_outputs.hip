@@ -37,11 +37,10 @@
 #include <string>
 #include <vector>
 #include "g2_endo.h"
+#include "proven_jobs.h"
 #include "window_ladder.h"
 
 namespace {
-
-constexpr size_t JO_PER_PROOF_MAX = 16384;  // 2^23 rows, the largest proof of every kind (bn254s_prove_batch)
 
 __device__ __forceinline__ bool jo_on_curve(const fq& x, const fq& y) {  // y^2 == x^3 + 3
   const fq one = fq_one();
@@ -133,18 +132,6 @@ __global__ __launch_bounds__(WL_LANES) void k_job_outputs(const u64* __restrict_
   }
 }
 
-// four canonical words per coordinate: the first coordinate of the n x ncoord that is not below p names itself in *what
-bool coords_ok(const char* arg, const char* const* coord, int ncoord, const uint64_t* w, size_t n, std::string* what) {
-  for (size_t i = 0; i < n; i++)
-    for (int c = 0; c < ncoord; c++)
-      if (!recover_below_p(w + 4 * (ncoord * i + c))) {
-        *what = std::string("job_outputs: ") + arg + "_" + std::to_string(i) + (ncoord > 1 ? std::string(" has ") + coord[c] : " is") +
-                " not below p";
-        return false;
-      }
-  return true;
-}
-
 bool batch_args_ok(int kind, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, size_t n, const uint64_t* outputs) {
   return kind >= 0 && kind <= 2 && scalars && x && (kind == 2 || offset) && outputs && n > 0 &&
          n < (size_t)UINT_MAX;  // the first bad index travels as a 32-bit word
@@ -154,15 +141,12 @@ constexpr size_t point_words(int kind) { return kind == 0 ? 8 : kind == 1 ? 16 :
 // The front-end into host memory: outputs[n x PW], finite[n].  Nothing is written on an error.
 int jobout_front(bn254s_ctx* c, int kind, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, size_t n,
                  uint64_t* outputs, uint8_t* finite) {
-  static const char* const coord[3][4] = {{"x", "y"}, {"x.c0", "x.c1", "y.c0", "y.c1"}, {""}};
+  const char* const* coord = kind == 0 ? COORD_G1 : COORD_G2;  // (not read for the one coordinate of kind 2)
   const size_t PW = point_words(kind);
   const bool curve = kind != 2;
-  std::string what;
-  if (!coords_ok("x", coord[kind], (int)PW / 4, x, n, &what) ||
-      (curve && !coords_ok("offset", coord[kind], (int)PW / 4, offset, n, &what))) {
-    c->set_err(what);
+  if (!coords_below_p(c, "job_outputs", "x", coord, (int)PW / 4, x, n) ||
+      (curve && !coords_below_p(c, "job_outputs", "offset", coord, (int)PW / 4, offset, n)))
     return BN254S_E_INVALID_ARG;
-  }
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   const size_t nb = (n + 7) / 8;  // words that hold n bytes
@@ -205,54 +189,28 @@ extern "C" int bn254s_job_outputs_batch(bn254s_ctx* c, int kind, const uint64_t*
 
 extern "C" int bn254s_job_outputs(bn254s_ctx* c, int kind, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
                                   const uint64_t* offset, size_t n, size_t per_proof, uint64_t* outputs_out, bn254s_proof** proofs_out) {
-  // every check before device work; the context last, so that the shape checks can be exercised without one
-  if (!batch_args_ok(kind, scalars, x, offset, n, outputs_out) || !params || !proofs_out || per_proof == 0 ||
-      params->struct_size != sizeof(bn254s_params))
-    return BN254S_E_INVALID_ARG;
-  const size_t n_proofs = (n + per_proof - 1) / per_proof;
-  for (size_t i = 0; i < n_proofs; i++) proofs_out[i] = nullptr;
-  if (per_proof > JO_PER_PROOF_MAX) {
-    if (c) c->set_err("job_outputs: per_proof above 16384 (2^23 rows, the largest proof)");
-    return BN254S_E_UNSUPPORTED;
-  }
-  if (!c) return BN254S_E_INVALID_ARG;
+  int rc = proven_args(c, "job_outputs", "proof", batch_args_ok(kind, scalars, x, offset, n, outputs_out), params, proofs_out, n,
+                       per_proof);
+  if (rc != BN254S_OK) return rc;
   const size_t PW = point_words(kind);
-  std::vector<u64> outs(PW * n);
+  std::vector<u64> outs(PW * n), proven;
   std::vector<uint8_t> finite(n);
-  int rc = jobout_front(c, kind, scalars, x, offset, n, outs.data(), finite.data());
+  rc = jobout_front(c, kind, scalars, x, offset, n, outs.data(), finite.data());
   if (rc != BN254S_OK) return rc;
   for (size_t i = 0; i < n; i++)
     if (!finite[i]) {  // the reference's targets cannot hold the point at infinity: no such job can be proven
       c->set_err("job_outputs: the output of job " + std::to_string(i) + " is the point at infinity");
       return BN254S_E_INVALID_POINT;
     }
-  rc = bn254s_prove_batch(c, kind, params, scalars, x, offset, n, per_proof, proofs_out);
-  if (rc != BN254S_OK) return rc;  // (the batch has freed its proofs)
+  rc = prove_and_collect(c, "job_outputs", kind, params, scalars, x, offset, n, per_proof, proofs_out, proven);
+  if (rc != BN254S_OK) return rc;
   // linkage: the trace generator computes every output bit by bit on its own; it must be the front-end's, word for word
-  size_t pos = 0;
-  for (size_t i = 0; i < n_proofs && rc == BN254S_OK; i++) {
-    const uint64_t* o;
-    size_t len = 0;
-    const size_t cnt = n - pos < per_proof ? n - pos : per_proof;
-    if (bn254s_proof_outputs(proofs_out[i], &o, &len) != BN254S_OK || len != PW * cnt) {
-      c->set_err("job_outputs: proof " + std::to_string(i) + " has " + std::to_string(len / PW) + " outputs, expected " +
-                 std::to_string(cnt));
-      rc = BN254S_E_INTERNAL;
+  for (size_t j = 0; j < n; j++)
+    if (memcmp(proven.data() + PW * j, outs.data() + PW * j, 8 * PW) != 0) {
+      c->set_err("job_outputs: the proven output of job " + std::to_string(j) + " is not the front-end's");
+      release_proofs(proofs_out, n, per_proof);
+      return BN254S_E_INTERNAL;
     }
-    for (size_t j = 0; j < cnt && rc == BN254S_OK; j++)
-      if (memcmp(o + PW * j, outs.data() + PW * (pos + j), 8 * PW) != 0) {
-        c->set_err("job_outputs: the proven output of job " + std::to_string(pos + j) + " is not the front-end's");
-        rc = BN254S_E_INTERNAL;
-      }
-    pos += cnt;
-  }
-  if (rc != BN254S_OK) {
-    for (size_t i = 0; i < n_proofs; i++) {
-      bn254s_proof_free(proofs_out[i]);
-      proofs_out[i] = nullptr;
-    }
-    return rc;
-  }
   memcpy(outputs_out, outs.data(), 8 * PW * n);
   return BN254S_OK;
 }

@@ -11,7 +11,7 @@
 // cofactor 1: nothing is cleared, no G2 job is made, no offset is needed; the STARK work is the two Legendre jobs per input.
 //   k_m2g1_point: the candidates, c_i = g(x_i)^((p+1)/4) by the ladder of sqrt_ladder.h for all three, the flags
 //                 "c_i^2 == g(x_i)" of x1 and x2, the choice, y = +-c of the chosen candidate, and the jobs (p-1)/2 | g(x_i)
-//   [2n fq_exp proofs of the Legendre symbols, linked to the flags: recover_host.h]
+//   [2n fq_exp proofs of the Legendre symbols, linked to the flags: proven_jobs.h]
 // g(x) is never zero (-3 is not a cube modulo p), so c^2 is g or -g, never both, and y is never zero.
 //   k_hash_to_fq: hash_to_fq = the first coordinate of hash_to_fq2 (hash_to_g2.rs:76-87; hash_to_fq.h)
 #include <climits>
@@ -20,7 +20,7 @@
 #include <vector>
 #include "fq2_root.h"  // fq_select, fq_from_limbs
 #include "hash_to_fq.h"
-#include "recover_host.h"
+#include "proven_jobs.h"
 #include "sqrt_ladder.h"
 #include "map_to_g1_constants.inc"
 
@@ -136,11 +136,7 @@ int m2g1_on_device(bn254s_ctx* c, const char* tag, u64* d, size_t n, uint64_t* p
 
 // The front-end for u in host memory; the first u_i >= p is reported before any device work.
 int m2g1_front(bn254s_ctx* c, const char* tag, const uint64_t* u, size_t n, uint64_t* points, uint8_t* flags, uint64_t* jobs) {
-  for (size_t i = 0; i < n; i++)
-    if (!recover_below_p(u + 4 * i)) {
-      c->set_err(std::string(tag) + ": u_" + std::to_string(i) + " is not below p");
-      return BN254S_E_INVALID_ARG;
-    }
+  if (!coords_below_p(c, tag, "u", nullptr, 1, u, n)) return BN254S_E_INVALID_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
   u64* d = c->words("m2g1", m2g1_words(n));
   if (!d) return BN254S_E_OOM;
@@ -191,22 +187,15 @@ extern "C" int bn254s_hash_to_g1_batch(bn254s_ctx* c, const uint64_t* inputs, si
 
 extern "C" int bn254s_map_to_g1(bn254s_ctx* c, const bn254s_params* params, const uint64_t* u, size_t n, size_t per_proof,
                                 uint64_t* out_points, uint8_t* sq_flags, uint64_t* fq_jobs, bn254s_proof** fq_proofs) {
-  // every check before device work; the context last, so that the shape checks can be exercised without one
-  if (!u || !out_points || n == 0 || n >= ((size_t)1 << 31) || !params || !fq_proofs || per_proof == 0 ||
-      params->struct_size != sizeof(bn254s_params))
-    return BN254S_E_INVALID_ARG;
-  const size_t n_jobs = 2 * n, n_proofs = (n_jobs + per_proof - 1) / per_proof;
-  for (size_t i = 0; i < n_proofs; i++) fq_proofs[i] = nullptr;
-  if (per_proof > G1R_PER_PROOF_MAX) {
-    if (c) c->set_err("map_to_g1: per_proof above 16384 (2^23 rows, the largest Fq-exp proof)");
-    return BN254S_E_UNSUPPORTED;
-  }
-  if (!c) return BN254S_E_INVALID_ARG;
+  const size_t n_jobs = 2 * n;
+  int rc = proven_args(c, "map_to_g1", "Fq-exp proof", u && out_points && n > 0 && n < ((size_t)1 << 31), params, fq_proofs, n_jobs,
+                       per_proof);
+  if (rc != BN254S_OK) return rc;
   std::vector<u64> points(8 * n), jobs(8 * n_jobs);
   std::vector<uint8_t> flags(n_jobs);
-  int rc = m2g1_front(c, "map_to_g1", u, n, points.data(), flags.data(), jobs.data());
+  rc = m2g1_front(c, "map_to_g1", u, n, points.data(), flags.data(), jobs.data());
   if (rc != BN254S_OK) return rc;
-  rc = recover_prove_legendre(c, "map_to_g1", params, jobs, flags.data(), n_jobs, per_proof, fq_proofs);
+  rc = prove_legendre(c, "map_to_g1", params, jobs, flags.data(), n_jobs, per_proof, fq_proofs);
   if (rc != BN254S_OK) return rc;
   memcpy(out_points, points.data(), points.size() * 8);
   if (sq_flags) memcpy(sq_flags, flags.data(), flags.size());

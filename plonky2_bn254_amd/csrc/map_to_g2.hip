@@ -22,7 +22,7 @@
 #include "fq2_root.h"
 #include "g2_cofactor.h"
 #include "hash_to_fq.h"
-#include "recover_host.h"
+#include "proven_jobs.h"
 #include "transcript.h"
 #include "../../include/bn254_stark.h"
 #include "map_to_g2_constants.inc"
@@ -206,15 +206,6 @@ __global__ __launch_bounds__(64) void k_hash_to_fq2(const u64* __restrict__ in, 
   hash_to_fq_lane<2>(in + k * len, len, out + 8 * k);
 }
 
-#define MCHK(call)                                                \
-  do {                                                            \
-    hipError_t e_ = (call);                                       \
-    if (e_ != hipSuccess) {                                       \
-      c->set_err(std::string(#call) + ": " + hipGetErrorString(e_)); \
-      return BN254S_E_HIP;                                        \
-    }                                                             \
-  } while (0)
-
 }  // namespace
 
 // hash_to_fq2 (src/utils/hash_to_g2.rs:76-87): Challenger::observe_elements(input); each coordinate = the low 32 bits of 16
@@ -241,11 +232,14 @@ extern "C" int bn254s_hash_to_fq2_batch(bn254s_ctx* c, const uint64_t* inputs, s
   return BN254S_OK;
 }
 
-extern "C" int bn254s_map_to_g2(bn254s_ctx* c, const bn254s_params* params, const uint64_t* u, const uint64_t* offsets, size_t n,
-                                uint64_t* out_points, uint64_t* fq_jobs, uint64_t* g2_jobs, bn254s_proof** fq_proofs,
-                                bn254s_proof** g2_proofs) {
-  if (!c || !params || !u || !offsets || !out_points || !fq_proofs || !g2_proofs || n == 0) return BN254S_E_INVALID_ARG;
-  MCHK(hipSetDevice(c->device));
+namespace {
+
+constexpr size_t M2G_PER_PROOF = 128;  // instances of a proof, of either kind
+
+// The pipeline of bn254s_map_to_g2 after its argument check; the proofs that exist when it returns an error are the caller's to release.
+int m2g_proven(bn254s_ctx* c, const bn254s_params* params, const uint64_t* u, const uint64_t* offsets, size_t n, uint64_t* out_points,
+               uint64_t* fq_jobs, uint64_t* g2_jobs, bn254s_proof** fq_proofs, bn254s_proof** g2_proofs) {
+  HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   const M2GConsts C = host_consts();
   const unsigned grid = (unsigned)((n + 63) / 64);
@@ -262,58 +256,39 @@ extern "C" int bn254s_map_to_g2(bn254s_ctx* c, const bn254s_params* params, cons
   u64* d_o = d_off + 16 * n;
   u64* d_out = d_o + 16 * n;
   int* d_err = (int*)(d_out + 16 * n);
-  MCHK(hipMemsetAsync(d_err, 0, 8, st));
-  MCHK(hipMemcpyAsync(d_u, u, n * 64, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemsetAsync(d_err, 0, 8, st));
+  HIP_TRY(c, hipMemcpyAsync(d_u, u, n * 64, hipMemcpyHostToDevice, st));
   k_m2g_candidates<<<grid, 64, 0, st>>>(d_u, n, C, d_cand, d_fq_s, d_fq_x);
   std::vector<u64> fs(8 * n), fx(8 * n);
-  MCHK(hipMemcpyAsync(fs.data(), d_fq_s, fs.size() * 8, hipMemcpyDeviceToHost, st));
-  MCHK(hipMemcpyAsync(fx.data(), d_fq_x, fx.size() * 8, hipMemcpyDeviceToHost, st));
-  MCHK(hipStreamSynchronize(st));
+  HIP_TRY(c, hipMemcpyAsync(fs.data(), d_fq_s, fs.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(fx.data(), d_fq_x, fx.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
   // 2n Legendre exponentiations in 128-instance proofs
-  int rc = bn254s_prove_batch(c, 2, params, fs.data(), fx.data(), nullptr, 2 * n, 128, fq_proofs);
+  std::vector<u64> leg;
+  int rc = prove_and_collect(c, "map_to_g2", 2, params, fs.data(), fx.data(), nullptr, 2 * n, M2G_PER_PROOF, fq_proofs, leg);
   if (rc != BN254S_OK) return rc;
-  const size_t n_fq = (2 * n + 127) / 128, n_g2 = (n + 127) / 128;
-  std::vector<u64> leg(8 * n);
-  for (size_t i = 0, pos = 0; i < n_fq; i++) {
-    const uint64_t* o;
-    size_t len;
-    bn254s_proof_outputs(fq_proofs[i], &o, &len);
-    memcpy(leg.data() + pos, o, len * 8);
-    pos += len;
-  }
-  MCHK(hipMemcpyAsync(d_leg, leg.data(), leg.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_leg, leg.data(), leg.size() * 8, hipMemcpyHostToDevice, st));
   k_m2g_select<<<grid, 64, 0, st>>>(d_u, d_cand, d_leg, n, C, d_g2_s, d_g2_x, d_err);
   std::vector<u64> gs(4 * n), gx(16 * n);
   int h_err = 0;
-  MCHK(hipMemcpyAsync(gs.data(), d_g2_s, gs.size() * 8, hipMemcpyDeviceToHost, st));
-  MCHK(hipMemcpyAsync(gx.data(), d_g2_x, gx.size() * 8, hipMemcpyDeviceToHost, st));
-  MCHK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
-  MCHK(hipStreamSynchronize(st));
+  HIP_TRY(c, hipMemcpyAsync(gs.data(), d_g2_s, gs.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(gx.data(), d_g2_x, gx.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
   if (h_err) {
     c->set_err("map_to_g2: square root self-check failed");
-    for (size_t i = 0; i < n_fq; i++) bn254s_proof_free(fq_proofs[i]);
     return h_err;
   }
   // n cofactor-clearing scalar multiplications
-  rc = bn254s_prove_batch(c, 1, params, gs.data(), gx.data(), offsets, n, 128, g2_proofs);
-  if (rc != BN254S_OK) {
-    for (size_t i = 0; i < n_fq; i++) bn254s_proof_free(fq_proofs[i]);
-    return rc;
-  }
-  std::vector<u64> outs(16 * n);
-  for (size_t i = 0, pos = 0; i < n_g2; i++) {
-    const uint64_t* o;
-    size_t len;
-    bn254s_proof_outputs(g2_proofs[i], &o, &len);
-    memcpy(outs.data() + pos, o, len * 8);
-    pos += len;
-  }
-  MCHK(hipMemcpyAsync(d_o, outs.data(), outs.size() * 8, hipMemcpyHostToDevice, st));
-  MCHK(hipMemcpyAsync(d_off, offsets, n * 128, hipMemcpyHostToDevice, st));
+  std::vector<u64> outs;
+  rc = prove_and_collect(c, "map_to_g2", 1, params, gs.data(), gx.data(), offsets, n, M2G_PER_PROOF, g2_proofs, outs);
+  if (rc != BN254S_OK) return rc;
+  HIP_TRY(c, hipMemcpyAsync(d_o, outs.data(), outs.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_off, offsets, n * 128, hipMemcpyHostToDevice, st));
   k_m2g_finish<<<grid, 64, 0, st>>>(d_o, d_off, n, d_out, d_err);
-  MCHK(hipMemcpyAsync(out_points, d_out, n * 128, hipMemcpyDeviceToHost, st));
-  MCHK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
-  MCHK(hipStreamSynchronize(st));
+  HIP_TRY(c, hipMemcpyAsync(out_points, d_out, n * 128, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
   if (fq_jobs) {  // the job arrays (what bn254s_verify needs as claimed inputs): 2n x (scalar 4 | x 4), n x (scalar 4 | x 16)
     for (size_t k = 0; k < 2 * n; k++) {
       memcpy(fq_jobs + 8 * k, fs.data() + 4 * k, 32);
@@ -331,6 +306,23 @@ extern "C" int bn254s_map_to_g2(bn254s_ctx* c, const bn254s_params* params, cons
     return h_err;
   }
   return BN254S_OK;
+}
+
+}  // namespace
+
+// On any error after the argument check no proof is left to the caller and every slot of both arrays is NULL.
+extern "C" int bn254s_map_to_g2(bn254s_ctx* c, const bn254s_params* params, const uint64_t* u, const uint64_t* offsets, size_t n,
+                                uint64_t* out_points, uint64_t* fq_jobs, uint64_t* g2_jobs, bn254s_proof** fq_proofs,
+                                bn254s_proof** g2_proofs) {
+  if (!c || !params || !u || !offsets || !out_points || !fq_proofs || !g2_proofs || n == 0) return BN254S_E_INVALID_ARG;
+  for (size_t i = 0; i < (2 * n + M2G_PER_PROOF - 1) / M2G_PER_PROOF; i++) fq_proofs[i] = nullptr;
+  for (size_t i = 0; i < (n + M2G_PER_PROOF - 1) / M2G_PER_PROOF; i++) g2_proofs[i] = nullptr;
+  const int rc = m2g_proven(c, params, u, offsets, n, out_points, fq_jobs, g2_jobs, fq_proofs, g2_proofs);
+  if (rc != BN254S_OK) {
+    release_proofs(fq_proofs, 2 * n, M2G_PER_PROOF);
+    release_proofs(g2_proofs, n, M2G_PER_PROOF);
+  }
+  return rc;
 }
 
 namespace {
@@ -383,12 +375,7 @@ size_t m2g_batch_words(size_t n) { return 40 * n + 2 + (n + 7) / 8; }
 // The reference's native map_to_g2 (hash_to_g2.rs:113-148) without proofs: the point bn254s_map_to_g2 reads from its proofs.
 extern "C" int bn254s_map_to_g2_batch(bn254s_ctx* c, const uint64_t* u, size_t n, uint64_t* out_points) {
   if (!c || !u || !out_points || n == 0 || n >= (size_t)UINT_MAX) return BN254S_E_INVALID_ARG;
-  for (size_t i = 0; i < n; i++)
-    for (int j = 0; j < 2; j++)
-      if (!recover_below_p(u + 8 * i + 4 * j)) {
-        c->set_err("map_to_g2_batch: u_" + std::to_string(i) + " has c" + std::to_string(j) + " not below p");
-        return BN254S_E_INVALID_ARG;
-      }
+  if (!coords_below_p(c, "map_to_g2_batch", "u", COORD_FQ2, 2, u, n)) return BN254S_E_INVALID_ARG;
   HIP_TRY(c, hipSetDevice(c->device));
   u64* d = c->words("m2g.batch", m2g_batch_words(n));
   if (!d) return BN254S_E_OOM;

@@ -34,7 +34,7 @@
 #include <string>
 #include <type_traits>
 #include <vector>
-#include "ctx.h"
+#include "proven_jobs.h"
 #include "trace_common.h"
 #include "chain_scan.h"
 #include "trace_g1.h"
@@ -43,14 +43,12 @@
 
 namespace {
 
-constexpr size_t MSM_PER_PROOF_MAX = 16384;  // 2^23 rows, the largest G1 / G2 proof (streaming workspace of bn254s_prove_batch)
-
 struct G1 {
   using P = g1j;  // point
   using F = fq;   // coordinate field
   static constexpr int FW = 4, KIND = 0;  // words of a coordinate; job kind of bn254s_prove_batch
   static constexpr size_t CHUNK = 16384;  // inputs per product launch: 3 x 4 x NPTS words = 49 KB of D_k per input, 808 MB at most
-  static constexpr const char *TAG = "g1_msm", *NAME = "G1", *POOL = "msm", *POOL_PTS = "msm.pts";
+  static constexpr const char *TAG = "g1_msm", *LARGEST = "G1 proof", *POOL = "msm", *POOL_PTS = "msm.pts";
   static constexpr size_t pts_words(size_t pcnt) { return 3 * 4 * pcnt; }
   // X, Y, Z one after the other at the count of this chunk, as k_msm_products reads them (a last chunk is shorter than a full
   // one, whose count is pcnt)
@@ -65,7 +63,7 @@ struct G2 {
   static constexpr int FW = 8, KIND = 1;
   // D_k (3 x 2 x 4 x NPTS words) and the chain's znorm (4 x NPTS words) are 28 x 514 x 8 B = 115 KB per input, 943 MB for a chunk
   static constexpr size_t CHUNK = 8192;
-  static constexpr const char *TAG = "g2_msm", *NAME = "G2", *POOL = "g2msm", *POOL_PTS = "g2msm.pts";
+  static constexpr const char *TAG = "g2_msm", *LARGEST = "G2 proof", *POOL = "g2msm", *POOL_PTS = "g2msm.pts";
   static constexpr size_t pts_words(size_t pcnt) { return 6 * 4 * pcnt /* D_k */ + 4 * pcnt /* znorm */; }
   // the six arrays at the count of this chunk (launch_g2_dbl_chain), znorm behind the D_k of a full chunk
   static void dbl_chain(const u64* d_x, int m, u64* pts, size_t pcnt, hipStream_t st) {
@@ -311,47 +309,20 @@ int msm(bn254s_ctx* c, const bn254s_params* params, const uint64_t* scalars, con
         size_t per_proof, uint64_t* result, uint64_t* offsets_out, bn254s_proof** proofs) {
   constexpr size_t PW = 2 * C::FW;
   const std::string tag = C::TAG;
-  // every check before device work; the context last, so that the shape checks can be exercised without one
-  if (!msm_args_ok(scalars, x, offset, n) || !params || !result || !proofs || per_proof == 0 ||
-      params->struct_size != sizeof(bn254s_params))
-    return BN254S_E_INVALID_ARG;
-  const size_t n_proofs = (n + per_proof - 1) / per_proof;
-  for (size_t i = 0; i < n_proofs; i++) proofs[i] = nullptr;
-  if (per_proof > MSM_PER_PROOF_MAX) {
-    if (c) c->set_err(tag + ": per_proof above 16384 (2^23 rows, the largest " + C::NAME + " proof)");
-    return BN254S_E_UNSUPPORTED;
-  }
-  if (!c) return BN254S_E_INVALID_ARG;
-  std::vector<u64> offs(PW * (n + 1));
-  int rc = msm_chain<C>(c, scalars, x, offset, n, offs.data(), result);
+  int rc = proven_args(c, tag, C::LARGEST, msm_args_ok(scalars, x, offset, n) && result, params, proofs, n, per_proof);
   if (rc != BN254S_OK) return rc;
-  rc = bn254s_prove_batch(c, C::KIND, params, scalars, x, offs.data(), n, per_proof, proofs);
-  if (rc != BN254S_OK) return rc;  // (the batch has freed its proofs)
+  std::vector<u64> offs(PW * (n + 1)), outs;
+  rc = msm_chain<C>(c, scalars, x, offset, n, offs.data(), result);
+  if (rc != BN254S_OK) return rc;
+  rc = prove_and_collect(c, tag, C::KIND, params, scalars, x, offs.data(), n, per_proof, proofs, outs);
+  if (rc != BN254S_OK) return rc;
   // linkage: the trace generator computes s_i x_i + offset_i on its own; it must land on offset_{i+1}
-  size_t pos = 0;
-  for (size_t i = 0; i < n_proofs && rc == BN254S_OK; i++) {
-    const uint64_t* o;
-    size_t len;
-    const size_t cnt = n - pos < per_proof ? n - pos : per_proof;
-    if (bn254s_proof_outputs(proofs[i], &o, &len) != BN254S_OK || len != PW * cnt) {
-      c->set_err(tag + ": proof " + std::to_string(i) + " has " + std::to_string(len / PW) + " outputs, expected " + std::to_string(cnt));
-      rc = BN254S_E_INTERNAL;
-    } else if (memcmp(o, offs.data() + PW * (pos + 1), len * 8) != 0) {
-      size_t j = 0;
-      while (memcmp(o + PW * j, offs.data() + PW * (pos + 1 + j), PW * 8) == 0) j++;
-      c->set_err(tag + ": output " + std::to_string(pos + j) + " of the proofs differs from offset_" + std::to_string(pos + j + 1) +
-                 " of the chain");
-      rc = BN254S_E_INTERNAL;
+  for (size_t j = 0; j < n; j++)
+    if (memcmp(outs.data() + PW * j, offs.data() + PW * (j + 1), PW * 8) != 0) {
+      c->set_err(tag + ": output " + std::to_string(j) + " of the proofs differs from offset_" + std::to_string(j + 1) + " of the chain");
+      release_proofs(proofs, n, per_proof);
+      return BN254S_E_INTERNAL;
     }
-    pos += cnt;
-  }
-  if (rc != BN254S_OK) {
-    for (size_t i = 0; i < n_proofs; i++) {
-      bn254s_proof_free(proofs[i]);
-      proofs[i] = nullptr;
-    }
-    return rc;
-  }
   if (offsets_out) memcpy(offsets_out, offs.data(), offs.size() * 8);
   return BN254S_OK;
 }

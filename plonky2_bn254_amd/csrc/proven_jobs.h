@@ -1,0 +1,115 @@
+// Host half of the proven front-ends (msm.hip, job_outputs.hip, g1_recover.hip, g2_recover.hip, g2_subgroup.hip, g2_cofactor.hip,
+// map_to_g1.hip, map_to_g2.hip): the range check of coordinates, the argument ladder of the full calls, "prove the jobs and collect
+// their outputs", the release of the proofs on an error, and the linkage of Legendre jobs to their flags.  Host code only.
+// A front-end brings its kernel, its own pointer / n predicate and its linkage rule: a flat loop over the collected outputs
+// that calls release_proofs when it fails.
+#pragma once
+#include <cstring>
+#include <string>
+#include <vector>
+#include "ctx.h"
+#include "../../include/bn254_stark.h"
+#include "g1_recover_constants.inc"  // p
+
+namespace {
+
+constexpr size_t PER_PROOF_MAX = 16384;  // 2^23 rows, the largest proof of every kind (bn254s_prove_batch)
+
+// four canonical words below p
+inline bool fq_below_p(const uint64_t* w) {
+  for (int j = 3; j >= 0; j--)
+    if (w[j] != G1R_P[j]) return w[j] < G1R_P[j];
+  return false;
+}
+
+// the names of the coordinates of an Fq2 element and of a G1 / G2 point, four words each
+constexpr const char* const COORD_FQ2[2] = {"c0", "c1"};
+constexpr const char* const COORD_G1[2] = {"x", "y"};
+constexpr const char* const COORD_G2[4] = {"x.c0", "x.c1", "y.c0", "y.c1"};
+
+// w: n items of ncoord coordinates.  The first coordinate that is not below p names itself in the context's error text,
+// "<tag>: <name>_<i> has <coord> not below p" ("<tag>: <name>_<i> is not below p" for ncoord == 1); true if all are fine.
+inline bool coords_below_p(bn254s_ctx* c, const std::string& tag, const char* name, const char* const* coord, int ncoord,
+                           const uint64_t* w, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    for (int k = 0; k < ncoord; k++)
+      if (!fq_below_p(w + 4 * (ncoord * i + k))) {
+        c->set_err(tag + ": " + name + "_" + std::to_string(i) + (ncoord > 1 ? std::string(" has ") + coord[k] : " is") + " not below p");
+        return false;
+      }
+  return true;
+}
+
+// The argument ladder of a full call, every check before device work and the context last, so that the shape checks can be
+// exercised without one.  own_ok: the caller's predicate on its own pointers and n.  The ceil(n_jobs / per_proof) slots are NULL
+// from the second rung on.  largest: the proof that the limit is named after ("G2 proof").
+inline int proven_args(bn254s_ctx* c, const std::string& tag, const char* largest, bool own_ok, const bn254s_params* params,
+                       bn254s_proof** proofs, size_t n_jobs, size_t per_proof) {
+  if (!own_ok || !params || !proofs || per_proof == 0 || params->struct_size != sizeof(bn254s_params)) return BN254S_E_INVALID_ARG;
+  for (size_t i = 0; i < (n_jobs + per_proof - 1) / per_proof; i++) proofs[i] = nullptr;
+  if (per_proof > PER_PROOF_MAX) {
+    if (c) c->set_err(tag + ": per_proof above 16384 (2^23 rows, the largest " + largest + ")");
+    return BN254S_E_UNSUPPORTED;
+  }
+  return c ? BN254S_OK : BN254S_E_INVALID_ARG;
+}
+
+// Frees the ceil(n_jobs / per_proof) proofs and leaves their slots NULL: what every error after the proofs exist does.
+inline void release_proofs(bn254s_proof** proofs, size_t n_jobs, size_t per_proof) {
+  for (size_t i = 0; i < (n_jobs + per_proof - 1) / per_proof; i++) {
+    bn254s_proof_free(proofs[i]);
+    proofs[i] = nullptr;
+  }
+}
+
+// bn254s_prove_batch of the n jobs, cut by per_proof, and the outputs of all proofs one after the other in outs (n x PW words,
+// PW = 8 | 16 | 4 for kind 0 | 1 | 2).  On any error no proof is left and every slot is NULL.
+inline int prove_and_collect(bn254s_ctx* c, const std::string& tag, int kind, const bn254s_params* params, const uint64_t* scalars,
+                             const uint64_t* x, const uint64_t* offset, size_t n, size_t per_proof, bn254s_proof** proofs,
+                             std::vector<u64>& outs) {
+  const size_t PW = kind == 0 ? 8 : kind == 1 ? 16 : 4, n_proofs = (n + per_proof - 1) / per_proof;
+  int rc = bn254s_prove_batch(c, kind, params, scalars, x, offset, n, per_proof, proofs);
+  if (rc != BN254S_OK) return rc;  // (the batch has freed its proofs)
+  outs.resize(PW * n);
+  for (size_t i = 0, pos = 0; i < n_proofs; i++) {
+    const uint64_t* o;
+    size_t len = 0;
+    const size_t cnt = n - pos < per_proof ? n - pos : per_proof;
+    if (bn254s_proof_outputs(proofs[i], &o, &len) != BN254S_OK || len != PW * cnt) {
+      c->set_err(tag + ": proof " + std::to_string(i) + " has " + std::to_string(len / PW) + " outputs, expected " + std::to_string(cnt));
+      release_proofs(proofs, n, per_proof);
+      return BN254S_E_INTERNAL;
+    }
+    memcpy(outs.data() + PW * pos, o, 8 * len);
+    pos += cnt;
+  }
+  return BN254S_OK;
+}
+
+// Proves the n Legendre jobs (8 words each: (p-1)/2 | base) as Fq-exp proofs and checks every proven output against its flag:
+// the trace generator computes base_i^((p-1)/2) on its own; it must be 1 where the flag is set and p - 1 where it is not.
+// fq_proofs: ceil(n / per_proof) slots; on any error every proof is freed and its slot is NULL.
+inline int prove_legendre(bn254s_ctx* c, const std::string& tag, const bn254s_params* params, const std::vector<u64>& jobs,
+                          const uint8_t* flags, size_t n, size_t per_proof, bn254s_proof** fq_proofs) {
+  std::vector<u64> s(4 * n), g(4 * n), outs;
+  for (size_t i = 0; i < n; i++) {
+    memcpy(s.data() + 4 * i, jobs.data() + 8 * i, 32);
+    memcpy(g.data() + 4 * i, jobs.data() + 8 * i + 4, 32);
+  }
+  int rc = prove_and_collect(c, tag, 2, params, s.data(), g.data(), nullptr, n, per_proof, fq_proofs, outs);
+  if (rc != BN254S_OK) return rc;
+  u64 pm1[4];
+  memcpy(pm1, G1R_P, 32);
+  pm1[0] -= 1;
+  static const u64 ONE[4] = {1, 0, 0, 0};
+  for (size_t i = 0; i < n; i++)
+    if (memcmp(outs.data() + 4 * i, flags[i] ? ONE : pm1, 32) != 0) {
+      c->set_err(tag + ": the proven Legendre symbol of input " + std::to_string(i) + " is not " +
+                 (flags[i] ? "1, but its flag is set" : "p - 1, but its flag is clear"));
+      release_proofs(fq_proofs, n, per_proof);
+      return BN254S_E_INTERNAL;
+    }
+  return BN254S_OK;
+}
+
+}  // namespace

@@ -131,6 +131,16 @@ def _ptr(a: Optional[np.ndarray]):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _slots(n_jobs, per_proof):
+    """The NULL proof slots of n_jobs jobs cut into proofs of per_proof: what a proving entry point fills."""
+    return (C.c_void_p * ((n_jobs + per_proof - 1) // per_proof))()
+
+
+def _proofs(lib, slots):
+    """The filled slots as Proof objects, which own them from here on."""
+    return [Proof(lib, C.c_void_p(h)) for h in slots]
+
+
 class Proof:
     """Owns a bn254s_proof*; `words` is the canonical u64 layout documented in bn254_stark.h."""
 
@@ -270,22 +280,19 @@ class Context:
     def prove_g1_batch(self, scalars, x, offset, per_proof=128, params: Optional[Params] = None, keep=True):
         params = params or default_params()
         n = scalars.shape[0]
-        k = (n + per_proof - 1) // per_proof
-        outs = (C.c_void_p * k)()
+        outs = _slots(n, per_proof)
         self._check(self._lib.bn254s_prove_g1_batch(self._h, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n,
                                                     per_proof, outs), "bn254s_prove_g1_batch")
-        proofs = [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
-        return proofs
+        return _proofs(self._lib, outs)
 
     def prove_batch(self, kind, scalars, x, offset=None, per_proof=128, params: Optional[Params] = None):
         """kind 0 = G1, 1 = G2, 2 = Fq exp: n jobs cut into independent 128-instance proofs, pipelined on the GPU."""
         params = params or default_params()
         n = scalars.shape[0]
-        k = (n + per_proof - 1) // per_proof
-        outs = (C.c_void_p * k)()
+        outs = _slots(n, per_proof)
         self._check(self._lib.bn254s_prove_batch(self._h, kind, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n,
                                                  per_proof, outs), "bn254s_prove_batch")
-        return [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+        return _proofs(self._lib, outs)
 
     def prove_batch_begin(self, kind, scalars, x, offset=None, per_proof=128, params: Optional[Params] = None):
         """bn254s_prove_batch_begin: queues the batch and returns a handle; `handle.end()` waits and returns the proofs.  Batches
@@ -311,12 +318,10 @@ class Context:
         pts = np.zeros((n, 16), np.uint64)
         fq_jobs = np.zeros((2 * n, 8), np.uint64)
         g2_jobs = np.zeros((n, 20), np.uint64)
-        n_fq, n_g2 = (2 * n + 127) // 128, (n + 127) // 128
-        pf, pg = (C.c_void_p * n_fq)(), (C.c_void_p * n_g2)()
+        pf, pg = _slots(2 * n, 128), _slots(n, 128)
         self._check(self._lib.bn254s_map_to_g2(self._h, C.byref(params), _ptr(u), _ptr(offsets), n, _ptr(pts), _ptr(fq_jobs),
                                                _ptr(g2_jobs), pf, pg), "bn254s_map_to_g2")
-        return (pts, fq_jobs, g2_jobs, [Proof(self._lib, C.c_void_p(pf[i])) for i in range(n_fq)],
-                [Proof(self._lib, C.c_void_p(pg[i])) for i in range(n_g2)])
+        return pts, fq_jobs, g2_jobs, _proofs(self._lib, pf), _proofs(self._lib, pg)
 
     def _msm_chain(self, fn, w, scalars, x, offset):
         scalars, x, offset = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, offset))
@@ -330,13 +335,12 @@ class Context:
         params = params or default_params()
         scalars, x, offset = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, offset))
         n = scalars.shape[0]
-        k = (n + per_proof - 1) // per_proof
         offs = np.zeros((n + 1, w), np.uint64)
         res = np.zeros(w, np.uint64)
-        outs = (C.c_void_p * k)()
+        outs = _slots(n, per_proof)
         self._check(getattr(self._lib, fn)(self._h, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof, _ptr(res),
                                            _ptr(offs), outs), fn)
-        return res, offs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+        return res, offs, _proofs(self._lib, outs)
 
     def g1_msm_chain(self, scalars, x, offset):
         """scalars [n,4], x [n,8], offset = R [8] -> (offsets [n+1,8], result [8]): the witness chain of g1_msm
@@ -376,12 +380,11 @@ class Context:
         params = params or default_params()
         xs = np.ascontiguousarray(xs, dtype=np.uint64)
         n = xs.shape[0]
-        k = (n + per_proof - 1) // per_proof
         pts, flags, jobs = np.zeros((n, 8), np.uint64), np.zeros(n, np.uint8), np.zeros((n, 8), np.uint64)
-        outs = (C.c_void_p * k)()
+        outs = _slots(n, per_proof)
         self._check(self._lib.bn254s_g1_recover_from_x(self._h, C.byref(params), _ptr(xs), n, per_proof, _ptr(pts),
                                                        flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_g1_recover_from_x")
-        return pts, flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+        return pts, flags, jobs, _proofs(self._lib, outs)
 
     @staticmethod
     def _sgns(sgns, n):
@@ -413,12 +416,11 @@ class Context:
         xs = np.ascontiguousarray(xs, dtype=np.uint64)
         n = xs.shape[0]
         sgns, sp = self._sgns(sgns, n)
-        k = (n + per_proof - 1) // per_proof
         pts, flags, jobs = np.zeros((n, 16), np.uint64), np.zeros(n, np.uint8), np.zeros((n, 8), np.uint64)
-        outs = (C.c_void_p * k)()
+        outs = _slots(n, per_proof)
         self._check(self._lib.bn254s_g2_recover_from_x(self._h, C.byref(params), _ptr(xs), sp, n, per_proof, _ptr(pts),
                                                        flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_g2_recover_from_x")
-        return pts, flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+        return pts, flags, jobs, _proofs(self._lib, outs)
 
     def g2_subgroup_check_batch(self, points):
         """points [n,16] (x.c0, x.c1, y.c0, y.c1, canonical, below p, on the twist curve) -> flags [n] uint8: flags[i] = 1 iff
@@ -441,12 +443,11 @@ class Context:
         n = points.shape[0]
         if offsets.shape != (n, 16):
             raise ValueError(f"offsets {offsets.shape} for {n} points")
-        k = (n + per_proof - 1) // per_proof
         flags, jobs = np.zeros(n, np.uint8), np.zeros((n, 20), np.uint64)
-        outs = (C.c_void_p * k)()
+        outs = _slots(n, per_proof)
         self._check(self._lib.bn254s_g2_subgroup_check(self._h, C.byref(params), _ptr(points), _ptr(offsets), n, per_proof,
                                                        flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_g2_subgroup_check")
-        return flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+        return flags, jobs, _proofs(self._lib, outs)
 
     def g2_clear_cofactor_batch(self, points):
         """points [n,16] (x.c0, x.c1, y.c0, y.c1, canonical, below p, on the twist curve) -> (images [n,16], finite [n] uint8):
@@ -470,13 +471,12 @@ class Context:
         n = points.shape[0]
         if offsets.shape != (n, 16):
             raise ValueError(f"offsets {offsets.shape} for {n} points")
-        k = (n + per_proof - 1) // per_proof
         images, finite, jobs = np.zeros((n, 16), np.uint64), np.zeros(n, np.uint8), np.zeros((n, 20), np.uint64)
-        outs = (C.c_void_p * k)()
+        outs = _slots(n, per_proof)
         self._check(self._lib.bn254s_g2_clear_cofactor(self._h, C.byref(params), _ptr(points), _ptr(offsets), n, per_proof,
                                                        _ptr(images), finite.ctypes.data_as(C.c_void_p), _ptr(jobs), outs),
                     "bn254s_g2_clear_cofactor")
-        return images, finite, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+        return images, finite, jobs, _proofs(self._lib, outs)
 
     def map_to_g2_batch(self, u):
         """u [n,8] (c0, c1, canonical, below p) -> points [n,16]: the reference's native map_to_g2 (hash_to_g2.rs:113-148) on the
@@ -540,12 +540,11 @@ class Context:
         params = params or default_params()
         u = np.ascontiguousarray(u, dtype=np.uint64)
         n = u.shape[0]
-        k = (2 * n + per_proof - 1) // per_proof
         pts, flags, jobs = np.zeros((n, 8), np.uint64), np.zeros(2 * n, np.uint8), np.zeros((2 * n, 8), np.uint64)
-        outs = (C.c_void_p * k)()
+        outs = _slots(2 * n, per_proof)
         self._check(self._lib.bn254s_map_to_g1(self._h, C.byref(params), _ptr(u), n, per_proof, _ptr(pts),
                                                flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_map_to_g1")
-        return pts, flags, jobs, [Proof(self._lib, C.c_void_p(outs[i])) for i in range(k)]
+        return pts, flags, jobs, _proofs(self._lib, outs)
 
     def _job_arrays(self, kind, scalars, x, offset):
         scalars, x = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x))
@@ -575,12 +574,11 @@ class Context:
         raises (-4, the message names it).  Check the result with verify_job_outputs."""
         params = params or default_params()
         pw, n, scalars, x, offset = self._job_arrays(kind, scalars, x, offset)
-        k = (n + per_proof - 1) // per_proof
         outs = np.zeros((n, pw), np.uint64)
-        slots = (C.c_void_p * k)()
+        slots = _slots(n, per_proof)
         self._check(self._lib.bn254s_job_outputs(self._h, kind, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof,
                                                  _ptr(outs), slots), "bn254s_job_outputs")
-        return outs, [Proof(self._lib, C.c_void_p(slots[i])) for i in range(k)]
+        return outs, _proofs(self._lib, slots)
 
     def ctl_values(self, kind, scalars, x, offset, outputs):
         """(input rows [n, 81|145|33], output rows [n, 33|65|17]): the extra looking values of the two CTLs."""
@@ -733,6 +731,48 @@ def verify_host(kind, words, degree_bits, scalars, x, offset, outputs, params: O
         raise RuntimeError(f"bn254s_verify_host failed with {rc}: {buf.value.decode()}")
 
 
+def _proof_slices(tag, proofs, n, per_proof, w):
+    """Checks the number of proofs for n jobs at once, then yields (k, proof, lo, hi, outs) for proof k of jobs lo .. hi - 1, outs
+    [hi - lo, w] its outputs, after checking that it has one per job."""
+    if len(proofs) != (n + per_proof - 1) // per_proof:
+        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+
+    def walk():
+        for k, pr in enumerate(proofs):
+            lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
+            outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, w)
+            if outs.shape[0] != hi - lo:
+                raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+            yield k, pr, lo, hi, outs
+    return walk()
+
+
+def _verify_slice(tag, kind, k, pr, lo, hi, scalars, x, offset, ctx, params):
+    """Proof k against its jobs lo .. hi - 1 of the job arrays: Context.verify with a context, else verify_host."""
+    s_, x_, o_ = (None if a is None else np.ascontiguousarray(a[lo:hi]) for a in (scalars, x, offset))
+    try:
+        if ctx is not None:
+            ctx.verify(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+        else:
+            verify_host(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
+    except VerifyError as e:
+        raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+
+
+def _check_legendre(tag, p, k, lo, hi, outs, flags, note=lambda j: ("", "")):
+    """The proven Legendre symbols of the jobs lo .. hi - 1 of proof k: each is 1 or p - 1 and agrees with its flag.  note(j): what
+    the two messages add after "proof k" and after "flag j"."""
+    from tools import synth
+
+    for j in range(lo, hi):
+        leg = synth.words_to_int(outs[j - lo])
+        if leg not in (1, p - 1):
+            raise VerifyError(f"{tag}: output {j} of proof {k}{note(j)[0]} is neither 1 nor p - 1")
+        if (leg == 1) != bool(flags[j]):
+            raise VerifyError(f"{tag}: flag {j}{note(j)[1]} is {int(flags[j])}, the proven Legendre symbol of job {j} is "
+                              f"{'1' if leg == 1 else 'p - 1'}")
+
+
 def _verify_msm(tag, kind, w, pt, neg, add, scalars, x, R, result, offsets, proofs, per_proof, ctx, params):
     """The checks of verify_g1_msm / verify_g2_msm for points of w words: pt(words) -> affine point, neg / add the group law."""
     scalars, x, R, result, offsets = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, R, result, offsets))
@@ -740,15 +780,10 @@ def _verify_msm(tag, kind, w, pt, neg, add, scalars, x, R, result, offsets, proo
     offsets = offsets.reshape(-1, w)
     if x.shape != (n, w) or offsets.shape != (n + 1, w) or R.size != w or result.size != w:
         raise VerifyError(f"{tag}: shapes: scalars {scalars.shape}, x {x.shape}, offsets {offsets.shape}, R {R.shape}, result {result.shape}")
-    if len(proofs) != (n + per_proof - 1) // per_proof:
-        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    slices = _proof_slices(tag, proofs, n, per_proof, w)
     if not np.array_equal(offsets[0], R.reshape(w)):
         raise VerifyError(f"{tag}: offsets[0] != R")
-    for i, pr in enumerate(proofs):
-        lo, hi = i * per_proof, min(n, (i + 1) * per_proof)
-        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, w)
-        if outs.shape[0] != hi - lo:
-            raise VerifyError(f"{tag}: proof {i} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+    for i, pr, lo, hi, outs in slices:
         bad = np.nonzero(np.any(outs != offsets[lo + 1:hi + 1], axis=1))[0]
         if bad.size:
             j = lo + int(bad[0])
@@ -759,16 +794,8 @@ def _verify_msm(tag, kind, w, pt, neg, add, scalars, x, R, result, offsets, proo
         raise VerifyError(f"{tag}: offsets[n] == R, the result would be the point at infinity") from None
     if pt(result.reshape(w)) != want:
         raise VerifyError(f"{tag}: result != offsets[n] - R")
-    for i, pr in enumerate(proofs):
-        lo, hi = i * per_proof, min(n, (i + 1) * per_proof)
-        s_, x_, o_ = (np.ascontiguousarray(a[lo:hi]) for a in (scalars, x, offsets))
-        try:
-            if ctx is not None:
-                ctx.verify(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-            else:
-                verify_host(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-        except VerifyError as e:
-            raise VerifyError(f"{tag}: proof {i} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+    for i, pr, lo, hi, _ in _proof_slices(tag, proofs, n, per_proof, w):
+        _verify_slice(tag, kind, i, pr, lo, hi, scalars, x, offsets, ctx, params)
 
 
 def verify_g1_msm(scalars, x, R, result, offsets, proofs, per_proof, ctx: Optional[Context] = None, params: Optional[Params] = None):
@@ -811,8 +838,7 @@ def verify_g1_recover(xs, points, flags, fq_jobs, proofs, per_proof, ctx: Option
     n = xs.shape[0]
     if xs.shape != (n, 4) or points.shape != (n, 8) or fq_jobs.shape != (n, 8) or flags.shape != (n,):
         raise VerifyError(f"{tag}: shapes: xs {xs.shape}, points {points.shape}, flags {flags.shape}, fq_jobs {fq_jobs.shape}")
-    if len(proofs) != (n + per_proof - 1) // per_proof:
-        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    slices = _proof_slices(tag, proofs, n, per_proof, 4)
     g = []
     for i in range(n):
         x = synth.words_to_int(xs[i])
@@ -823,25 +849,9 @@ def verify_g1_recover(xs, points, flags, fq_jobs, proofs, per_proof, ctx: Option
             raise VerifyError(f"{tag}: scalar of job {i} != (p - 1)/2")
         if synth.words_to_int(fq_jobs[i, 4:]) != g[i]:
             raise VerifyError(f"{tag}: x of job {i} != x_{i}^3 + 3")
-    for k, pr in enumerate(proofs):
-        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
-        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 4)
-        if outs.shape[0] != hi - lo:
-            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
-        s_, x_ = np.ascontiguousarray(fq_jobs[lo:hi, :4]), np.ascontiguousarray(fq_jobs[lo:hi, 4:])
-        try:
-            if ctx is not None:
-                ctx.verify(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
-            else:
-                verify_host(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
-        except VerifyError as e:
-            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
-        for i in range(lo, hi):
-            leg = synth.words_to_int(outs[i - lo])
-            if leg not in (1, p - 1):
-                raise VerifyError(f"{tag}: output {i} of proof {k} is neither 1 nor p - 1")
-            if (leg == 1) != bool(flags[i]):
-                raise VerifyError(f"{tag}: flag {i} is {int(flags[i])}, the proven Legendre symbol of job {i} is {'1' if leg == 1 else 'p - 1'}")
+    for k, pr, lo, hi, outs in slices:
+        _verify_slice(tag, 2, k, pr, lo, hi, fq_jobs[:, :4], fq_jobs[:, 4:], None, ctx, params)
+        _check_legendre(tag, p, k, lo, hi, outs, flags)
     for i in range(n):
         px, py = synth.words_to_int(points[i, :4]), synth.words_to_int(points[i, 4:])
         if px != synth.words_to_int(xs[i]):
@@ -868,8 +878,7 @@ def verify_map_to_g1(u, points, sq_flags, fq_jobs, proofs, per_proof, ctx: Optio
     n = u.shape[0]
     if u.shape != (n, 4) or points.shape != (n, 8) or fq_jobs.shape != (2 * n, 8) or sq_flags.shape != (2 * n,):
         raise VerifyError(f"{tag}: shapes: u {u.shape}, points {points.shape}, sq_flags {sq_flags.shape}, fq_jobs {fq_jobs.shape}")
-    if len(proofs) != (2 * n + per_proof - 1) // per_proof:
-        raise VerifyError(f"{tag}: {len(proofs)} proofs for {2 * n} jobs of {per_proof} per proof")
+    slices = _proof_slices(tag, proofs, 2 * n, per_proof, 4)
     us = []
     for i in range(n):
         ui = synth.words_to_int(u[i])
@@ -881,26 +890,9 @@ def verify_map_to_g1(u, points, sq_flags, fq_jobs, proofs, per_proof, ctx: Optio
                 raise VerifyError(f"{tag}: scalar of job {2 * i + j} (input {i}) != (p - 1)/2")
             if synth.words_to_int(fq_jobs[2 * i + j, 4:]) != ref.g(xc):
                 raise VerifyError(f"{tag}: x of job {2 * i + j} != g(x{j + 1}) of input {i}")
-    for k, pr in enumerate(proofs):
-        lo, hi = k * per_proof, min(2 * n, (k + 1) * per_proof)
-        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 4)
-        if outs.shape[0] != hi - lo:
-            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
-        s_, x_ = np.ascontiguousarray(fq_jobs[lo:hi, :4]), np.ascontiguousarray(fq_jobs[lo:hi, 4:])
-        try:
-            if ctx is not None:
-                ctx.verify(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
-            else:
-                verify_host(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
-        except VerifyError as e:
-            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
-        for j in range(lo, hi):
-            leg = synth.words_to_int(outs[j - lo])
-            if leg not in (1, p - 1):
-                raise VerifyError(f"{tag}: output {j} of proof {k} (input {j // 2}) is neither 1 nor p - 1")
-            if (leg == 1) != bool(sq_flags[j]):
-                raise VerifyError(f"{tag}: flag {j} (g(x{j % 2 + 1}) of input {j // 2}) is {int(sq_flags[j])}, the proven Legendre "
-                                  f"symbol of job {j} is {'1' if leg == 1 else 'p - 1'}")
+    for k, pr, lo, hi, outs in slices:
+        _verify_slice(tag, 2, k, pr, lo, hi, fq_jobs[:, :4], fq_jobs[:, 4:], None, ctx, params)
+        _check_legendre(tag, p, k, lo, hi, outs, sq_flags, lambda j: (f" (input {j // 2})", f" (g(x{j % 2 + 1}) of input {j // 2})"))
     for i in range(n):
         try:
             want = ref.select_point(us[i], bool(sq_flags[2 * i]), bool(sq_flags[2 * i + 1]))
@@ -929,8 +921,7 @@ def verify_g2_recover(xs, sgns, points, flags, fq_jobs, proofs, per_proof, ctx: 
     if xs.shape != (n, 8) or points.shape != (n, 16) or fq_jobs.shape != (n, 8) or flags.shape != (n,) or sgns.shape != (n,):
         raise VerifyError(f"{tag}: shapes: xs {xs.shape}, sgns {sgns.shape}, points {points.shape}, flags {flags.shape}, "
                           f"fq_jobs {fq_jobs.shape}")
-    if len(proofs) != (n + per_proof - 1) // per_proof:
-        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    slices = _proof_slices(tag, proofs, n, per_proof, 4)
     g = []
     for i in range(n):
         x = (synth.words_to_int(xs[i, :4]), synth.words_to_int(xs[i, 4:]))
@@ -943,25 +934,9 @@ def verify_g2_recover(xs, sgns, points, flags, fq_jobs, proofs, per_proof, ctx: 
             raise VerifyError(f"{tag}: scalar of job {i} != (p - 1)/2")
         if synth.words_to_int(fq_jobs[i, 4:]) != (g[i][0] * g[i][0] + g[i][1] * g[i][1]) % p:
             raise VerifyError(f"{tag}: x of job {i} != norm(x_{i}^3 + b')")
-    for k, pr in enumerate(proofs):
-        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
-        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 4)
-        if outs.shape[0] != hi - lo:
-            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
-        s_, x_ = np.ascontiguousarray(fq_jobs[lo:hi, :4]), np.ascontiguousarray(fq_jobs[lo:hi, 4:])
-        try:
-            if ctx is not None:
-                ctx.verify(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
-            else:
-                verify_host(2, pr.words, pr.degree_bits, s_, x_, None, pr.outputs, params)
-        except VerifyError as e:
-            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
-        for i in range(lo, hi):
-            leg = synth.words_to_int(outs[i - lo])
-            if leg not in (1, p - 1):
-                raise VerifyError(f"{tag}: output {i} of proof {k} is neither 1 nor p - 1")
-            if (leg == 1) != bool(flags[i]):
-                raise VerifyError(f"{tag}: flag {i} is {int(flags[i])}, the proven Legendre symbol of job {i} is {'1' if leg == 1 else 'p - 1'}")
+    for k, pr, lo, hi, outs in slices:
+        _verify_slice(tag, 2, k, pr, lo, hi, fq_jobs[:, :4], fq_jobs[:, 4:], None, ctx, params)
+        _check_legendre(tag, p, k, lo, hi, outs, flags)
     for i in range(n):
         if not np.array_equal(points[i, :8], xs[i]):
             raise VerifyError(f"{tag}: point {i} does not carry x_{i}")
@@ -990,8 +965,7 @@ def verify_g2_subgroup(points, offsets, flags, g2_jobs, proofs, per_proof, ctx: 
     n = points.shape[0]
     if points.shape != (n, 16) or offsets.shape != (n, 16) or g2_jobs.shape != (n, 20) or flags.shape != (n,):
         raise VerifyError(f"{tag}: shapes: points {points.shape}, offsets {offsets.shape}, flags {flags.shape}, g2_jobs {g2_jobs.shape}")
-    if len(proofs) != (n + per_proof - 1) // per_proof:
-        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    slices = _proof_slices(tag, proofs, n, per_proof, 16)
     r_words = np.array(synth._to_words(synth.R_ORDER), np.uint64)
     for i in range(n):
         pt = synth.g2_from_words(points[i])
@@ -1003,20 +977,8 @@ def verify_g2_subgroup(points, offsets, flags, g2_jobs, proofs, per_proof, ctx: 
             raise VerifyError(f"{tag}: scalar of job {i} != r")
         if not np.array_equal(g2_jobs[i, 4:], points[i]):
             raise VerifyError(f"{tag}: x of job {i} != point {i}")
-    scalars = np.ascontiguousarray(g2_jobs[:, :4])
-    for k, pr in enumerate(proofs):
-        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
-        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 16)
-        if outs.shape[0] != hi - lo:
-            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
-        s_, x_, o_ = (np.ascontiguousarray(a[lo:hi]) for a in (scalars, points, offsets))
-        try:
-            if ctx is not None:
-                ctx.verify(1, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-            else:
-                verify_host(1, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-        except VerifyError as e:
-            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+    for k, pr, lo, hi, outs in slices:
+        _verify_slice(tag, 1, k, pr, lo, hi, g2_jobs[:, :4], points, offsets, ctx, params)
         for i in range(lo, hi):
             back = np.array_equal(outs[i - lo], offsets[i])
             if back != bool(flags[i]):
@@ -1041,8 +1003,7 @@ def verify_g2_clear_cofactor(points, offsets, images, finite, g2_jobs, proofs, p
     if points.shape != (n, 16) or offsets.shape != (n, 16) or images.shape != (n, 16) or g2_jobs.shape != (n, 20) or finite.shape != (n,):
         raise VerifyError(f"{tag}: shapes: points {points.shape}, offsets {offsets.shape}, images {images.shape}, finite {finite.shape}, "
                           f"g2_jobs {g2_jobs.shape}")
-    if len(proofs) != (n + per_proof - 1) // per_proof:
-        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
+    slices = _proof_slices(tag, proofs, n, per_proof, 16)
     h_words = np.array(synth._to_words(synth.G2_COFACTOR), np.uint64)
     for i in range(n):
         pt = synth.g2_from_words(points[i])
@@ -1054,20 +1015,8 @@ def verify_g2_clear_cofactor(points, offsets, images, finite, g2_jobs, proofs, p
             raise VerifyError(f"{tag}: scalar of job {i} != h")
         if not np.array_equal(g2_jobs[i, 4:], points[i]):
             raise VerifyError(f"{tag}: x of job {i} != point {i}")
-    scalars = np.ascontiguousarray(g2_jobs[:, :4])
-    for k, pr in enumerate(proofs):
-        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
-        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, 16)
-        if outs.shape[0] != hi - lo:
-            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
-        s_, x_, o_ = (np.ascontiguousarray(a[lo:hi]) for a in (scalars, points, offsets))
-        try:
-            if ctx is not None:
-                ctx.verify(1, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-            else:
-                verify_host(1, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-        except VerifyError as e:
-            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+    for k, pr, lo, hi, outs in slices:
+        _verify_slice(tag, 1, k, pr, lo, hi, g2_jobs[:, :4], points, offsets, ctx, params)
         for i in range(lo, hi):
             if finite[i]:
                 img = synth.g2_from_words(images[i])
@@ -1099,27 +1048,12 @@ def verify_job_outputs(kind, scalars, x, offset, outputs, proofs, per_proof, ctx
             (offset is not None and offset.shape != (n, pw))):
         raise VerifyError(f"{tag}: shapes: scalars {scalars.shape}, x {x.shape}, offset {None if offset is None else offset.shape}, "
                           f"outputs {outputs.shape}")
-    if len(proofs) != (n + per_proof - 1) // per_proof:
-        raise VerifyError(f"{tag}: {len(proofs)} proofs for {n} jobs of {per_proof} per proof")
-    for k, pr in enumerate(proofs):
-        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
-        outs = np.asarray(pr.outputs, dtype=np.uint64).reshape(-1, pw)
-        if outs.shape[0] != hi - lo:
-            raise VerifyError(f"{tag}: proof {k} has {outs.shape[0]} outputs for jobs {lo}..{hi - 1}")
+    for k, pr, lo, hi, outs in _proof_slices(tag, proofs, n, per_proof, pw):
         bad = np.nonzero(np.any(outs != outputs[lo:hi], axis=1))[0]
         if bad.size:
             raise VerifyError(f"{tag}: output {lo + int(bad[0])} is not the proven output of proof {k}")
-    for k, pr in enumerate(proofs):
-        lo, hi = k * per_proof, min(n, (k + 1) * per_proof)
-        s_, x_ = np.ascontiguousarray(scalars[lo:hi]), np.ascontiguousarray(x[lo:hi])
-        o_ = None if offset is None else np.ascontiguousarray(offset[lo:hi])
-        try:
-            if ctx is not None:
-                ctx.verify(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-            else:
-                verify_host(kind, pr.words, pr.degree_bits, s_, x_, o_, pr.outputs, params)
-        except VerifyError as e:
-            raise VerifyError(f"{tag}: proof {k} (jobs {lo}..{hi - 1}) rejected: {e}") from None
+    for k, pr, lo, hi, _ in _proof_slices(tag, proofs, n, per_proof, pw):
+        _verify_slice(tag, kind, k, pr, lo, hi, scalars, x, offset, ctx, params)
 
 
 class BatchInFlight:
@@ -1129,8 +1063,7 @@ class BatchInFlight:
         self._ctx = ctx
         self._keep = (scalars, x, offset, params)
         n = scalars.shape[0]
-        self._k = (n + per_proof - 1) // per_proof
-        self._outs = (C.c_void_p * self._k)()
+        self._outs = _slots(n, per_proof)
         self._h = C.c_void_p()
         ctx._check(ctx._lib.bn254s_prove_batch_begin(ctx._h, kind, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof,
                                                      self._outs, C.byref(self._h)), "bn254s_prove_batch_begin")
@@ -1141,7 +1074,7 @@ class BatchInFlight:
         h, self._h = self._h, None
         self._ctx._check(self._ctx._lib.bn254s_prove_batch_end(h), "bn254s_prove_batch_end")
         self._keep = None
-        return [Proof(self._ctx._lib, C.c_void_p(self._outs[i])) for i in range(self._k)]
+        return _proofs(self._ctx._lib, self._outs)
 
     def __del__(self):
         if getattr(self, "_h", None) is not None:  # never leave a batch running into freed inputs
@@ -1156,12 +1089,11 @@ def prove_batch_multi(contexts, kind, scalars, x, offset=None, per_proof=128, pa
     params = params or default_params()
     lib = contexts[0]._lib
     n = scalars.shape[0]
-    k = (n + per_proof - 1) // per_proof
     handles = (C.c_void_p * len(contexts))(*[c._h for c in contexts])
-    outs = (C.c_void_p * k)()
+    outs = _slots(n, per_proof)
     rc = lib.bn254s_prove_batch_multi(handles, len(contexts), kind, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof,
                                       outs)
     if rc != 0:
         raise RuntimeError(f"bn254s_prove_batch_multi failed with {rc}: " + "; ".join(c._lib.bn254s_last_error(c._h).decode()
                                                                                      for c in contexts))
-    return [Proof(lib, C.c_void_p(outs[i])) for i in range(k)]
+    return _proofs(lib, outs)

@@ -151,3 +151,41 @@ def test_hash_to_fq2_batch_on_device_equals_host_and_python(gpu_ctx):
     pts, fq_jobs, g2_jobs, pf, pg = gpu_ctx.map_to_g2(np.ascontiguousarray(got[:4]), off)
     gpu_ctx.verify(1, pg[0].words, pg[0].degree_bits, np.ascontiguousarray(g2_jobs[:, :4]), np.ascontiguousarray(g2_jobs[:, 4:]), off,
                    pg[0].outputs)
+
+
+@pytest.mark.gpu
+def test_map_to_g2_releases_its_proofs_on_an_error(gpu_ctx):
+    """The error contract of bn254s_map_to_g2 (include/bn254_stark.h): on an error no proof is left to the caller and every
+    slot is NULL.  n = 2: one Fq-exp proof of four jobs, one G2 proof of two.  offsets[0] = [(r - 1)/2] image_0 makes the proven
+    output image_0 + offsets[0] equal -offsets[0], which the finish cannot subtract: BN254S_E_INVALID_POINT after both batches
+    have been proven.  The context proves and verifies an ordinary call afterwards."""
+    import ctypes as C
+    import plonky2_bn254_amd.lib as L
+    n = 2
+    us = m2g.inputs(n, seed=61)
+    u = np.array([synth._to_words(a[0]) + synth._to_words(a[1]) for a in us], dtype=np.uint64)
+    image0 = synth.g2_from_words(gpu_ctx.map_to_g2_batch(u)[0])
+    assert image0 == m2g.map_to_g2(us[0])
+    off0 = synth.g2_mul((synth.R_ORDER - 1) // 2, image0)
+    assert synth.g2_add(image0, off0) == synth.g2_neg(off0)
+    good = synth.g2_inputs(n, seed=13)[2]
+    offsets = good.copy()
+    offsets[0] = synth.g2_points_to_words([off0])[0]
+    pts, fq_jobs, g2_jobs = np.zeros((n, 16), np.uint64), np.zeros((2 * n, 8), np.uint64), np.zeros((n, 20), np.uint64)
+    pf, pg = (C.c_void_p * 1)(1), (C.c_void_p * 1)(1)  # a marker that is no proof: the call must not read it
+    lib, params = gpu_ctx._lib, L.default_params()
+    rc = lib.bn254s_map_to_g2(gpu_ctx._h, C.byref(params), L._ptr(u), L._ptr(offsets), n, L._ptr(pts), L._ptr(fq_jobs), L._ptr(g2_jobs),
+                              pf, pg)
+    msg = lib.bn254s_last_error(gpu_ctx._h).decode()
+    print("map_to_g2 with output == -offset:", rc, msg)
+    assert rc == -4, (rc, msg)
+    assert pf[0] is None and pg[0] is None
+    if msg.startswith("map_to_g2:"):  # the library's own finish check; otherwise the prover refused the job with the same code
+        assert msg == "map_to_g2: output equals +-offset"
+    out, fq_jobs, g2_jobs, pf, pg = gpu_ctx.map_to_g2(u, good)
+    assert synth.g2_from_words(out[0]) == image0
+    assert len(pf) == 1 and len(pg) == 1
+    gpu_ctx.verify(2, pf[0].words, pf[0].degree_bits, np.ascontiguousarray(fq_jobs[:, :4]), np.ascontiguousarray(fq_jobs[:, 4:]), None,
+                   pf[0].outputs)
+    gpu_ctx.verify(1, pg[0].words, pg[0].degree_bits, np.ascontiguousarray(g2_jobs[:, :4]), np.ascontiguousarray(g2_jobs[:, 4:]), good,
+                   pg[0].outputs)
