@@ -518,6 +518,24 @@ int bn254s_selftest_fq(bn254s_ctx* ctx, int group, const uint64_t* in, size_t n,
  * BN254S_E_INTERNAL: a range-checked or table value above 65535 (found on the device; `out` is not meaningful then). */
 int bn254s_selftest_logup(bn254s_ctx* ctx, const uint64_t* trace, size_t rows, int ncols, int rc_begin, int n_rc, int table_col,
                           int freq_col, const uint64_t betas[2], uint64_t* out);
+/* Debug: the plan of one proof - what the prover decides before it touches memory, the workspace layout above all - for a proof of n
+ * instances of `kind` on a device with dev_total_bytes of memory (0 = unknown: the streaming workspace is then never chosen on
+ * account of the size).  Host arithmetic only: no context, no GPU.  force_split / force_lowmem / force_stream / stream_win_log stand
+ * for BN254S_FORCE_SPLIT / _FORCE_LOWMEM / _FORCE_STREAM / BN254S_STREAM_WIN_LOG, which the provers read per call (0 = off;
+ * stream_win_log < 0 = not set).  out[BN254S_PLAN_WORDS]:
+ *   0 kind  1 n  2 W (trace width)  3 A (auxiliary width)  4 constraints  5 words per point  6 N (rows)  7 log_n
+ *   8 log_s (1: a radix-2 level above the tall transforms)  9 log_r  10 R = 2^log_r  11 NH = N >> log_s  12 NSPL = 1 << log_s
+ *   13 stream  14 lowmem (compact or streaming workspace)  15 log_bk  16 BK = 2^log_bk rows per quotient window  17 BK + 1
+ *   18 L (FRI layers)  19..26 their arity bits (0 past L)  27 proof words per query  28 words of a commitment tree
+ *   29 words of the FRI layer values  30 words of the FRI trees  31 words of the job arrays
+ *   32..52 words of the named workspace buffers in, tvals, tcoef, hist, tmp, ldechunk, sponge, comb, tlde, trees, avals, acoef, alde,
+ *          scratch, quot, tabs, open, fri, fritrees, qout, win (0: no buffer of that name - it aliases another one or is not needed)
+ *   53 bytes of pinned host staging
+ * BN254S_E_UNSUPPORTED with the provers' message in err (NUL-terminated, at most err_len bytes; may be NULL): an unsupported height
+ * or StarkConfig.  BN254S_E_INVALID_ARG: kind outside 0..2, n = 0, NULL params / out or a params->struct_size mismatch. */
+#define BN254S_PLAN_WORDS 54
+int bn254s_selftest_proof_plan(int kind, size_t n, const bn254s_params* params, uint64_t dev_total_bytes, int force_split,
+                               int force_lowmem, int force_stream, int stream_win_log, uint64_t* out, char* err, size_t err_len);
 /* Trace generation only: column-major trace[W][rows] copied to the host buffer.
  * kind: 0 = G1 scalar mul (W 781), 1 = G2 scalar mul (W 1295), 2 = Fq exp (W 427; offset ignored). */
 int bn254s_generate_trace(bn254s_ctx* ctx, int kind, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset,

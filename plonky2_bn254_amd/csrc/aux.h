@@ -28,8 +28,6 @@ struct StarkShape {
   GL_HD int n_total_constraints() const { return n_constraints + 2 * (n_helpers() + 2) + 2 * 2 * n_ctl; }
 };
 
-StarkShape g1_shape();
-
 size_t aux_scratch_words(const StarkShape& sh, size_t N);
 void aux_build(const StarkShape& sh, const u64* d_trace, size_t N, const u64 betas[2], const u64 gammas[2], u64* d_aux,
                u64* d_scratch, int* d_err, hipStream_t st);

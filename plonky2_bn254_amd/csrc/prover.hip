@@ -3,6 +3,16 @@
 // followed by starky's prove_with_commitment, as called from G1StarkProofGenerator::run_once
 // (src/generators/g1/stark_proof.rs:151-163).  All polynomial data stays in HBM; the host only runs the
 // Fiat-Shamir transcript on caps / openings (a few KB per round trip) and assembles the proof words.
+//
+// In this file, in the order a proof meets them:
+//   stark_kind()         what differs between the three STARKs, one table (prover.h);
+//   proof_plan()         everything decided before memory is touched, the workspace layout above all (proof_plan.h / .hip);
+//   Workspace            the named buffers of the slot, acquired from the plan (workspace_acquire);
+//   Transforms           iNTT / LDE dispatch by trace height and workspace;
+//   stage_* / commit()   the stages, one function each; the pieces that are host arithmetic alone (opening recombination,
+//                        alpha powers, final polynomial, assembly of the words) are free functions without a HIP call;
+//   prove_on_slot()      the list of stages with the transcript between them;
+//   the C ABI            batches on the worker pool, the out-of-memory retry, accessors.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -16,8 +26,9 @@
 #include "fri.h"
 #include "transcript.h"
 #include "prover.h"
+#include "proof_plan.h"
 
-// ---- shapes -------------------------------------------------------------------------------------------------
+// ---- the three kinds -------------------------------------------------------------------------------------------
 // Stark::lookups (range-checked columns), the two looked CTL tables and the constraint counts of the three AIRs:
 // G1 scalar_mul_{view,stark,ctl}.rs, G2 twins, fields/exp_{view,stark,ctl}.rs.
 template <class L>
@@ -46,11 +57,17 @@ static StarkShape make_shape(bool input_has_a, int n_constraints) {
   s.ctl.filter_col[1] = L::FLAGS + 1;
   return s;
 }
-StarkShape g1_shape() { return make_shape<G1L>(true, 1111); }
-StarkShape shape_for(int kind) {
-  return kind == KIND_G1 ? make_shape<G1L>(true, 1111) : kind == KIND_G2 ? make_shape<G2L>(true, 1693) : make_shape<FQL>(false, 770);
+static int fq_generate_trace_no_offset(const u64* d_scalars, const u64* d_x, const u64*, size_t n, u64* d_trace, size_t N,
+                                       u64* d_scratch, u64* d_outputs, int* d_err, hipStream_t st, bool with_range) {
+  return fq_generate_trace_device(d_scalars, d_x, n, d_trace, N, d_scratch, d_outputs, d_err, st, with_range);
 }
-int point_words(int kind) { return kind == KIND_G1 ? 8 : kind == KIND_G2 ? 16 : 4; }
+const StarkKind& stark_kind(int kind) {
+  static const StarkKind kinds[3] = {
+      {make_shape<G1L>(true, 1111), 8, true, g1_trace_scratch_words, g1_generate_trace_device, g1_quotient_mz_blocks, g1_quotient_launch},
+      {make_shape<G2L>(true, 1693), 16, true, g2_trace_scratch_words, g2_generate_trace_device, g2_quotient_mz_blocks, g2_quotient_launch},
+      {make_shape<FQL>(false, 770), 4, false, fq_trace_scratch_words, fq_generate_trace_no_offset, fq_quotient_mz_blocks, fq_quotient_launch}};
+  return kinds[kind];
+}
 
 // ---- proof object ---------------------------------------------------------------------------------------------
 enum { ST_TRACE = 0, ST_TRACE_NTT, ST_TRACE_MERKLE, ST_AUX, ST_AUX_NTT, ST_AUX_MERKLE, ST_QUOTIENT, ST_QUOTIENT_COMMIT,
@@ -65,11 +82,6 @@ struct bn254s_proof {
   float stage_ms[ST_COUNT] = {0};
 };
 
-static size_t rows_for(size_t n, uint32_t min_rows_log2) {
-  size_t r = std::max((size_t)1 << min_rows_log2, n * 512), p = 1;
-  while (p < r) p <<= 1;
-  return p;
-}
 std::vector<int> fri_arities(const bn254s_params& P, int degree_bits) {  // ConstantArityBits(arity, final)
   std::vector<int> a;
   int d = degree_bits;
@@ -160,187 +172,42 @@ static int get_point_tables(bn254s_ctx* c, unsigned log_n, QPointTables& pt) {
   return 0;
 }
 
-// `after_alloc` (optional) is called once the workspace of the proof is complete: the out-of-memory retry of the batch entry
-// points holds WorkPool::retry_mu up to that point, so that allocation attempts never interleave.
-static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params& P, const u64* scalars, const u64* x,
-                         const u64* off, size_t n, bn254s_proof* pr, std::string& err,
-                         const std::function<void()>* after_alloc = nullptr) {
-  const StarkShape sh = shape_for(kind);
-  const int PW = point_words(kind);
-  const size_t N = rows_for(n, P.min_rows_log2);
-  unsigned log_n = 0;
-  while (((size_t)1 << log_n) < N) log_n++;
-  if (log_n < 16 || log_n > 23) {
-    err = "supported trace heights: 2^16 .. 2^23 rows (up to 16384 instances in one proof)";
-    return BN254S_E_UNSUPPORTED;
-  }
-  if (P.num_challenges != 2 || P.rate_bits != 1 || P.cap_height != 4 || P.arity_bits != 4 || P.min_rows_log2 < 16 ||
-      P.pow_bits == 0 || P.pow_bits > 32 || P.num_queries == 0 || P.num_queries > 256) {
-    err = "unsupported StarkConfig (only standard_fast_config shapes)";
-    return BN254S_E_UNSUPPORTED;
-  }
-  // 2^23 rows: one radix-2 level above the tall transforms (ntt.hip), and the workspace is laid out to fit one GPU: the NTT
-  // stage runs in column chunks (its scratch is a chunk, not a commitment), the auxiliary coefficients overwrite their values,
-  // and the trace values are released before the auxiliary LDE is allocated.  BN254S_FORCE_SPLIT=1 takes
-  // the same path from 2^18 rows on (tests: word-for-word against the oracle at 2^18).
-  const bool force_split = getenv("BN254S_FORCE_SPLIT") && atoi(getenv("BN254S_FORCE_SPLIT"));  // read per call (tests)
-  const unsigned log_s = (log_n == 23 || (force_split && log_n >= 18)) ? 1 : 0;
-  const unsigned log_m2 = log_n + 1, log_r = log_n - 16 - log_s;
-  const size_t R = (size_t)1 << log_r;
-  const size_t M2 = 2 * N, NH = N >> log_s;  // NH: words of one half (= N without the extra level)
-  const int NSPL = 1 << log_s;              // coefficient arrays hold NSPL halves per polynomial
-  // The compact workspace (NTT stage in column chunks, auxiliary commitment in place, auxiliary LDE in the memory of the dead
-  // trace values) is used whenever the plain layout would not fit: 2^23 rows, and G2 from 2^22 rows on (339 GB plain, 211 GB
-  // compact).  BN254S_FORCE_LOWMEM=1 selects it for any tall proof (tests).
-  const bool force_lowmem = getenv("BN254S_FORCE_LOWMEM") && atoi(getenv("BN254S_FORCE_LOWMEM"));
-  const double plain_bytes = 8.0 * (double)N * (4.0 * sh.W + 4.0 * sh.n_aux() + std::max(sh.W, sh.n_aux()));
-  // "stream": even the compact workspace does not fit (G2 at 2^23 rows: its two LDEs alone are 296 GB).  Only the coefficients
-  // stay resident; a commitment streams 16-column chunks through the NTT into a leaf hash that absorbs into resident sponge
-  // states, and wherever LDE rows are needed they are recomputed from the coefficients: the quotient runs over windows of
-  // consecutive rows of a coset (natural order, QArgs window mode), the FRI batch polynomial is formed on the coefficient
-  // vectors (it is linear in them) and extended once, the query rows are gathered from one more pass of chunk LDEs.
-  // BN254S_FORCE_STREAM=1 takes this path for any proof above 2^16 rows (tests: word for word against the oracle at 2^17 / 2^18);
-  // BN254S_STREAM_WIN_LOG = log2 of the rows per window (default: at most 2^22, at least two windows per coset).
-  const bool force_stream = getenv("BN254S_FORCE_STREAM") && atoi(getenv("BN254S_FORCE_STREAM"));
-  const double compact_bytes = 8.0 * ((double)std::max((size_t)sh.W * N, (size_t)sh.n_aux() * 2 * N) + (double)sh.W * N * 3.0 + (double)sh.n_aux() * N);
-  size_t dev_free_b = 0, dev_total_b = 0;
-  (void)hipMemGetInfo(&dev_free_b, &dev_total_b);
-  const bool stream = log_n > 16 && (force_stream || (dev_total_b > 0 && compact_bytes + 20e9 > (double)dev_total_b));
-  const bool lowmem = stream || log_s || (log_n > 16 && (force_lowmem || plain_bytes > 200e9));
-  unsigned log_bk = std::min(22u, log_n - 1);
-  if (const char* e = getenv("BN254S_STREAM_WIN_LOG")) log_bk = std::min(log_n, std::max(8u, (unsigned)atoi(e)));
-  const size_t BK = (size_t)1 << log_bk, WROWS = BK + 1;  // rows per quotient window (+ the next row of the last one)
-  const int W = sh.W, A = sh.n_aux(), NQ = 4, CAPW = 64;
-  const int K = sh.n_total_constraints();
-  hipStream_t st = sl.st;
-  BufPool& mem = sl.mem;
-  u64* d_tmp_fwd = nullptr;  // = d_tmp once the workspace is set up (used by the NTT dispatch lambdas)
-  QPointTables pt;
-  if (int rc = get_point_tables(c, log_n, pt)) {
-    err = "point tables";
-    return rc;
-  }
-  const NttTallTables* TT = nullptr;
-  const NttSplitTables* SP = nullptr;
-  if (log_r) {
-    TT = get_tall_tables(c, log_n - log_s, log_s != 0);
-    if (!TT) {
-      err = "tall NTT tables";
-      return BN254S_E_OOM;
-    }
-  }
-  if (log_s) {
-    SP = get_split_tables(c, log_n);
-    if (!SP) {
-      err = "split NTT tables";
-      return BN254S_E_OOM;
-    }
-  }
-  const int CH = 16;  // columns per chunk of the split commitment
-  // iNTT / LDE / coset iNTT dispatch: 2^16-row traces use the four-step kernels directly, taller ones add the outer pass
-  // from_values of a whole commitment: the fused four-launch form for 2^16 rows, iNTT then LDE otherwise
-  auto do_commit_ntt = [&](const u64* vals, u64* coef, u64* lde, int nc) {
-    if (log_s) {
-      // per chunk: values -> [Pe | Po] (radix-2 level), the tall commitment of the 2 CH half columns, halves' LDEs -> LDE
-      u64* eo = d_tmp_fwd;                          // [CH][2][N]
-      u64* ntmp = d_tmp_fwd + (size_t)CH * 2 * N;   // [2 CH][NH]
-      for (int c0 = 0; c0 < nc; c0 += CH) {
-        const int cn = std::min(CH, nc - c0);
-        ntt_split_inverse(SP, vals + (size_t)c0 * N, coef + (size_t)c0 * N, cn, st);
-        ntt_inverse_lde_tall(&c->ntt, TT, coef + (size_t)c0 * N, coef + (size_t)c0 * N, eo, ntmp, 2 * cn, st);
-        ntt_split_forward(SP, eo, lde + (size_t)c0 * M2, M2, cn, st);
-      }
-    } else if (log_r && lowmem) {
-      for (int c0 = 0; c0 < nc; c0 += CH) {
-        const int cn = std::min(CH, nc - c0);
-        ntt_inverse_lde_tall(&c->ntt, TT, vals + (size_t)c0 * N, coef + (size_t)c0 * N, lde + (size_t)c0 * M2, d_tmp_fwd, cn, st);
-      }
-    } else if (log_r) {
-      ntt_inverse_lde_tall(&c->ntt, TT, vals, coef, lde, d_tmp_fwd, nc, st);
-    } else {
-      ntt_inverse_lde(&c->ntt, vals, coef, lde, d_tmp_fwd, d_tmp_fwd + (size_t)nc * N, nc, st);
-    }
-  };
-  auto do_lde = [&](const u64* coef, u64* lde, int nc) {
-    if (log_s) {
-      u64* eo = d_tmp_fwd;
-      u64* ntmp = d_tmp_fwd + (size_t)CH * 2 * N;
-      for (int c0 = 0; c0 < nc; c0 += CH) {
-        const int cn = std::min(CH, nc - c0);
-        ntt_lde_tall(&c->ntt, TT, coef + (size_t)c0 * N, eo, ntmp, 2 * cn, st);
-        ntt_split_forward(SP, eo, lde + (size_t)c0 * M2, M2, cn, st);
-      }
-    } else if (log_r) ntt_lde_tall(&c->ntt, TT, coef, lde, d_tmp_fwd, nc, st);
-    else ntt_lde(&c->ntt, coef, lde, d_tmp_fwd, nc, st);
-  };
-  // stream mode: the LDE of ONE column chunk (coefficients at `coef`, cn <= CH columns) into d_ldechunk
-  u64* d_ldechunk_fwd = nullptr;  // (= d_ldechunk once the workspace is set up)
-  // (coset_mask: 1 / 2 = only coset 0 / 1 of the output, 3 = both; under the split level coset h of the N-point domain comes from
-  // coset h of both half transforms)
-  auto lde_chunk = [&](const u64* coef, int cn, int coset_mask = 3) {
-    if (log_s) {
-      u64* eo = d_tmp_fwd;
-      u64* ntmp = d_tmp_fwd + (size_t)CH * 2 * N;
-      ntt_lde_tall(&c->ntt, TT, coef, eo, ntmp, 2 * cn, st, coset_mask);
-      ntt_split_forward(SP, eo, d_ldechunk_fwd, M2, cn, st, coset_mask);
-    } else {
-      ntt_lde_tall(&c->ntt, TT, coef, d_ldechunk_fwd, d_tmp_fwd, cn, st, coset_mask);
-    }
-  };
-  // stream mode: from_values of a commitment, chunk by chunk: coefficients stay, the chunk's LDE is absorbed by the leaf hash
-  u64* d_sponge_fwd = nullptr;
-  const unsigned log_m2_fwd = log_n + 1;
-  auto commit_stream = [&](const u64* vals, u64* coef, int nc, u64* tree) {
-    for (int c0 = 0; c0 < nc; c0 += CH) {
-      const int cn = std::min(CH, nc - c0);
-      if (log_s) {
-        u64* eo = d_tmp_fwd;
-        u64* ntmp = d_tmp_fwd + (size_t)CH * 2 * N;
-        ntt_split_inverse(SP, vals + (size_t)c0 * N, coef + (size_t)c0 * N, cn, st);
-        ntt_inverse_lde_tall(&c->ntt, TT, coef + (size_t)c0 * N, coef + (size_t)c0 * N, eo, ntmp, 2 * cn, st);
-        ntt_split_forward(SP, eo, d_ldechunk_fwd, M2, cn, st);
-      } else {
-        ntt_inverse_lde_tall(&c->ntt, TT, vals + (size_t)c0 * N, coef + (size_t)c0 * N, d_ldechunk_fwd, d_tmp_fwd, cn, st);
-      }
-      merkle_absorb(d_ldechunk_fwd, M2, cn, (int)log_m2_fwd, d_sponge_fwd, c0 == 0, c0 + cn == nc ? tree : nullptr, st);
-    }
-  };
-  // leaf hash of a resident commitment: one GPU-filling section, or (BN254S_HASH_SPLIT, 2^16-row proofs) several shorter ones
-  auto hash_sections = [&](const u64* lde, int width, u64* tree, int stage) {
-    const int S = log_n == 16 ? c->hash_split : 1;
-    if (S <= 1) {
-      BigSection big(c, st, BIG_HASH);
-      hipEventRecord(sl.events[2 * stage], st);  // (the stage's clock starts once the section is admitted)
-      merkle_leaves(lde, 1, M2, width, log_m2_fwd, tree, st);
-      return;
-    }
-    const size_t cnt = M2 / S;
-    for (int k = 0; k < S; k++) {
-      BigSection big(c, st, BIG_HASH_PART);
-      if (k == 0) hipEventRecord(sl.events[2 * stage], st);
-      merkle_leaves_range(lde, 1, M2, width, (size_t)k * cnt, cnt, tree, st);
-    }
-  };
-  // proofs running beside this one right now: the small Merkle levels use their throughput kernels then (merkle.h; same digests)
-  auto mmode = [&]() { return c->workers.in_flight.load(std::memory_order_relaxed) >= 4 ? MERKLE_THROUGHPUT : MERKLE_LATENCY; };
-  const std::vector<int> arities = fri_arities(P, log_n);
-  const int L = (int)arities.size();
-  if (L > FRI_MAX_LAYERS) return BN254S_E_UNSUPPORTED;
+// ---- workspace --------------------------------------------------------------------------------------------------
+// The device memory of one proof: the named buffers of the slot (sizes: ProofPlan::words) and the pointers carved out of them.
+struct Workspace {
+  Slot* sl = nullptr;
+  const ProofPlan* pl = nullptr;
+  u64 *in, *tvals, *tcoef, *hist, *tmp, *ldechunk, *sponge, *comb, *tlde, *trees, *avals, *acoef, *alde, *scr, *quot, *tabs, *open,
+      *fri, *fritrees, *qout;
+  int* err;                 // device error word (behind the inputs)
+  unsigned long long* pow;  // proof-of-work result
+  u32* qidx;                // query indices (behind the query rounds)
+  u64 *ttree, *atree, *qtree;
+  u64 *qv, *ab, *qcoef, *qlde, *qpart;  // [2][2][N], [2][2][N], [4][N], [4][2N], [parts][2][2N]
+  u64 *W, *mzt, *apow;
+  size_t cap_off;  // of the cap inside a commitment tree
+  // streaming workspace, from begin_windows() on: trace / auxiliary rows of a quotient window, its point tables, query leaf rows
+  u64 *tw = nullptr, *aw = nullptr, *wpt = nullptr, *qrows = nullptr;
+  int begin_windows(std::string& err);
+};
 
-  // ---- workspace ------------------------------------------------------------------------------------------
-  const size_t in_words = n * (4 + 2 * (size_t)PW);
+// Buffer names, sizes and the order of drops and allocations are part of the behaviour: slots carry buffers from one proof to the
+// next across workspace layouts, and the out-of-memory retry of the batch entry points depends on what is given back and when.
+static int workspace_acquire(Slot& sl, const ProofPlan& pl, Workspace& ws, std::string& err) {
+  BufPool& mem = sl.mem;
+  const PlanBuffers& b = pl.words;
+  const bool stream = pl.stream, lowmem = pl.lowmem;
+  ws.sl = &sl;
+  ws.pl = &pl;
   if (lowmem) {  // buffers of the plain layout left in the slot by an earlier, smaller proof would not fit beside this one
     mem.drop("acoef");
     mem.drop("alde");
   }
-  u64* d_in = mem.words("in", in_words + 16);
-  // compact workspace: the trace values are dead once the auxiliary values exist, the auxiliary LDE takes their place
-  u64* d_tvals = mem.words("tvals", lowmem && !stream ? std::max((size_t)W * N, (size_t)A * M2) : (size_t)W * N);
-  u64* d_tcoef = mem.words("tcoef", (size_t)W * N);
-  u64* d_hist = mem.words("hist", 65536 / 2);
-  // [tmp | y0 | y1] for the fused commitment; one tmp for a tall one; [E,O LDEs | tmp] of one column chunk under the split level
-  u64* d_tmp = mem.words("tmp", log_s ? (size_t)3 * CH * N : lowmem ? (size_t)CH * N : (size_t)(log_r ? 1 : 3) * std::max(W, A) * N);
-  d_tmp_fwd = d_tmp;
+  ws.in = mem.words("in", b.in);
+  ws.tvals = mem.words("tvals", b.tvals);
+  ws.tcoef = mem.words("tcoef", b.tcoef);
+  ws.hist = mem.words("hist", b.hist);
+  ws.tmp = mem.words("tmp", b.tmp);
   mem.drop("win");  // (allocated in the middle of a streaming proof, in the memory of its dead trace values)
   if (stream) {  // no resident LDE: whatever an earlier proof left in the slot under these names goes first
     mem.drop("tlde");
@@ -350,54 +217,32 @@ static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params&
     mem.drop("ldechunk");
     mem.drop("sponge");
   }
-  u64* d_ldechunk = stream ? mem.words("ldechunk", (size_t)CH * M2) : nullptr;  // the LDE of one column chunk
-  u64* d_sponge = stream ? mem.words("sponge", (size_t)12 * M2) : nullptr;      // sponge states of the streaming leaf hash
-  u64* d_comb = mem.words("comb", (size_t)6 * N + (size_t)6 * M2);  // FRI batch polynomial: coefficients | LDE
-  u64* d_tlde = stream ? d_ldechunk : mem.words("tlde", (size_t)W * M2);
-  const size_t tree_words = merkle_tree_digests(log_m2, P.cap_height) * 4;
-  u64* d_trees = mem.words("trees", 3 * tree_words);
-  u64* d_avals = mem.words("avals", (size_t)A * N);
-  u64* d_acoef = lowmem ? d_avals : mem.words("acoef", (size_t)A * N);         // compact workspace: the commitment runs in place
-  u64* d_alde = stream ? d_ldechunk : lowmem ? d_tvals : mem.words("alde", (size_t)A * M2);
-  const size_t trace_scr = kind == KIND_G1 ? g1_trace_scratch_words(n) : kind == KIND_G2 ? g2_trace_scratch_words(n) : fq_trace_scratch_words(n);
-  u64* d_scr = mem.words("scratch", std::max(trace_scr, aux_scratch_words(sh, N)));
-  u64* d_q = mem.words("quot", (size_t)(3 * NQ) * N + (size_t)NQ * M2 + (size_t)QUOTIENT_MAX_PARTS * 2 * (stream ? WROWS : M2));  // qv, ab, qcoef, qlde, partials
-  u64* d_tabs = mem.words("tabs", QUOTIENT_W_WORDS(K) + QUOTIENT_MZT_WORDS + 4 * (size_t)(W + A + NQ));  // W, mzt, apow (8 u32 per power)
-  u64* d_open = mem.words("open", std::max((size_t)(W + A + NQ) * NSPL * R * 5 + FRI_OPENING_TABLE_WORDS, n * (size_t)PW));
-  // FRI layer values (extension, 2 words) and trees
-  size_t fri_words = 0, fri_tree_words = 0;
-  {
-    size_t m = M2;
-    for (int l = 0; l <= L; l++) {
-      fri_words += 2 * m;
-      if (l < L) fri_tree_words += merkle_tree_digests((int)log_m2 - 4 * (l + 1), P.cap_height) * 4;
-      m >>= 4;
-    }
+  ws.ldechunk = stream ? mem.words("ldechunk", b.ldechunk) : nullptr;
+  ws.sponge = stream ? mem.words("sponge", b.sponge) : nullptr;
+  ws.comb = mem.words("comb", b.comb);
+  ws.tlde = stream ? ws.ldechunk : mem.words("tlde", b.tlde);
+  ws.trees = mem.words("trees", b.trees);
+  ws.avals = mem.words("avals", b.avals);
+  ws.acoef = lowmem ? ws.avals : mem.words("acoef", b.acoef);  // compact workspace: the commitment runs in place
+  ws.alde = stream ? ws.ldechunk : lowmem ? ws.tvals : mem.words("alde", b.alde);
+  ws.scr = mem.words("scratch", b.scratch);
+  ws.quot = mem.words("quot", b.quot);
+  ws.tabs = mem.words("tabs", b.tabs);
+  ws.open = mem.words("open", b.open);
+  ws.fri = mem.words("fri", b.fri);
+  ws.fritrees = mem.words("fritrees", b.fritrees);
+  ws.qout = mem.words("qout", b.qout);
+  // pinned staging for the two larger device -> host copies (opening partials, query rounds), part of the workspace
+  if (sl.pinned_bytes < pl.pinned_bytes) {
+    if (sl.pinned) hipHostFree(sl.pinned);
+    sl.pinned = nullptr;
+    sl.pinned_bytes = 0;
+    CHK(hipHostMalloc(&sl.pinned, pl.pinned_bytes));
+    sl.pinned_bytes = pl.pinned_bytes;
   }
-  u64* d_fri = mem.words("fri", fri_words);
-  u64* d_fritrees = mem.words("fritrees", fri_tree_words);
-  // per-query proof words
-  size_t wpq = (size_t)(W + A + NQ) + 3 * 4 * (log_m2 - P.cap_height);
-  {
-    int lg = log_m2;
-    for (int l = 0; l < L; l++) {
-      lg -= arities[l];
-      wpq += 32 + 4 * (lg - P.cap_height);
-    }
-  }
-  u64* d_qout = mem.words("qout", wpq * P.num_queries + 64);
-  {  // pinned staging for the two larger device -> host copies (opening partials, query rounds), part of the workspace
-    const size_t need = std::max((size_t)(W + A + NQ) * NSPL * R * 5, wpq * P.num_queries) * 8;
-    if (sl.pinned_bytes < need) {
-      if (sl.pinned) hipHostFree(sl.pinned);
-      sl.pinned = nullptr;
-      sl.pinned_bytes = 0;
-      CHK(hipHostMalloc(&sl.pinned, need));
-      sl.pinned_bytes = need;
-    }
-  }
-  if (!d_hist || !d_in || !d_tvals || !d_tcoef || !d_tmp || !d_tlde || !d_trees || !d_avals || !d_acoef || !d_alde || !d_scr || !d_q ||
-      !d_tabs || !d_open || !d_fri || !d_fritrees || !d_qout || !d_comb || (stream && (!d_ldechunk || !d_sponge))) {
+  if (!ws.hist || !ws.in || !ws.tvals || !ws.tcoef || !ws.tmp || !ws.tlde || !ws.trees || !ws.avals || !ws.acoef || !ws.alde ||
+      !ws.scr || !ws.quot || !ws.tabs || !ws.open || !ws.fri || !ws.fritrees || !ws.qout || !ws.comb ||
+      (stream && (!ws.ldechunk || !ws.sponge))) {
     err = mem.err;
     mem.release();  // a workspace that could not be completed is given back: the context stays usable for smaller proofs
     return BN254S_E_OOM;
@@ -416,279 +261,397 @@ static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params&
       return BN254S_E_OOM;
     }
   }
-  if (after_alloc) (*after_alloc)();
-  d_ldechunk_fwd = d_ldechunk;
-  d_sponge_fwd = d_sponge;
-  int* d_err = (int*)(d_in + in_words);
-  unsigned long long* d_pow = (unsigned long long*)(d_in + in_words + 2);
-  u32* d_qidx = (u32*)(d_qout + wpq * P.num_queries);
-  u64* d_ttree = d_trees;
-  u64* d_atree = d_trees + tree_words;
-  u64* d_qtree = d_trees + 2 * tree_words;
-  u64* d_qv = d_q;                       // [2][2][N]
-  u64* d_ab = d_q + (size_t)NQ * N;      // [2][2][N]
-  u64* d_qcoef = d_q + (size_t)2 * NQ * N;  // [4][N]
-  u64* d_qlde = d_q + (size_t)3 * NQ * N;   // [4][2N]
-  u64* d_qpart = d_qlde + (size_t)NQ * M2;  // [parts][2][2N]
-  u64* d_W = d_tabs;
-  u64* d_mzt = d_tabs + QUOTIENT_W_WORDS(K);
-  u64* d_apow = d_mzt + QUOTIENT_MZT_WORDS;
-  const size_t cap_off = 4 * merkle_level_offset(log_m2, log_m2 - P.cap_height);
+  const size_t N = pl.N, M2 = pl.M2;
+  const int NQ = ProofPlan::NQ;
+  ws.err = (int*)(ws.in + pl.in_words);
+  ws.pow = (unsigned long long*)(ws.in + pl.in_words + 2);
+  ws.qidx = (u32*)(ws.qout + pl.n_q());
+  ws.ttree = ws.trees;
+  ws.atree = ws.trees + pl.tree_words;
+  ws.qtree = ws.trees + 2 * pl.tree_words;
+  ws.qv = ws.quot;
+  ws.ab = ws.quot + (size_t)NQ * N;
+  ws.qcoef = ws.quot + (size_t)2 * NQ * N;
+  ws.qlde = ws.quot + (size_t)3 * NQ * N;
+  ws.qpart = ws.qlde + (size_t)NQ * M2;
+  ws.W = ws.tabs;
+  ws.mzt = ws.tabs + QUOTIENT_W_WORDS(pl.K);
+  ws.apow = ws.mzt + QUOTIENT_MZT_WORDS;
+  ws.cap_off = 4 * merkle_level_offset(pl.log_m2, pl.log_m2 - pl.P.cap_height);
+  return BN254S_OK;
+}
 
-  if (sl.events.empty()) {
-    sl.events.resize(2 * ST_COUNT);
-    for (auto& e : sl.events) CHK(hipEventCreate(&e));
+// Streaming workspace, once the auxiliary values exist: the trace values are dead, their memory becomes the quotient windows (all
+// columns x WROWS rows), the window's point tables and the leaf rows of the queries.
+int Workspace::begin_windows(std::string& err) {
+  BufPool& mem = sl->mem;
+  const size_t WROWS = pl->WROWS;
+  CHK(hipStreamSynchronize(sl->st));
+  mem.drop("tvals");
+  tvals = nullptr;
+  u64* win = mem.words("win", pl->words.win);
+  if (!win) {
+    err = mem.err;
+    mem.release();
+    return BN254S_E_OOM;
   }
-  hipEvent_t* ev = sl.events.data();
-  // one begin/end event pair per stage; a stage's time never includes waiting for the big-kernel lock
-  auto sb = [&](int stage) { hipEventRecord(ev[2 * stage], st); };
-  auto se = [&](int stage) { hipEventRecord(ev[2 * stage + 1], st); };
-  auto cleanup_events = [&]() {};  // the events belong to the slot
+  tw = win;
+  aw = win + (size_t)pl->W * WROWS;
+  wpt = aw + (size_t)pl->A * WROWS;
+  qrows = wpt + 3 * WROWS;
+  return BN254S_OK;
+}
 
-  // ---- trace generation (scalar_mul_stark.rs:55-69) ---------------------------------------------------------
-  sb(ST_TOTAL);
-  sb(ST_TRACE);
-  CHK(hipMemsetAsync(d_err, 0, 16, st));
+// ---- transforms -------------------------------------------------------------------------------------------------
+// iNTT / LDE / coset iNTT dispatch: 2^16-row traces use the four-step kernels directly, taller ones add the outer pass, the split
+// level one radix-2 level above that; the compact and the streaming workspace work in chunks of CH columns.
+struct Transforms {
+  static constexpr int CH = ProofPlan::CH;
+  bn254s_ctx* c;
+  hipStream_t st;
+  const NttTallTables* TT;
+  const NttSplitTables* SP;
+  const ProofPlan& pl;
+  u64 *tmp, *ldechunk, *sponge;
+  // split level, per chunk: values -> [Pe | Po] (radix-2 level), the tall transform of the 2 CH half columns, halves' LDEs -> LDE
+  u64* eo() const { return tmp; }                              // [CH][2][N]
+  u64* ntmp() const { return tmp + (size_t)CH * 2 * pl.N; }    // [2 CH][NH]
+
+  // from_values of a whole commitment: the fused four-launch form for 2^16 rows, iNTT then LDE otherwise
+  void commit_ntt(const u64* vals, u64* coef, u64* lde, int nc) const {
+    const size_t N = pl.N, M2 = pl.M2;
+    if (pl.log_s) {
+      for (int c0 = 0; c0 < nc; c0 += CH) {
+        const int cn = std::min(CH, nc - c0);
+        ntt_split_inverse(SP, vals + (size_t)c0 * N, coef + (size_t)c0 * N, cn, st);
+        ntt_inverse_lde_tall(&c->ntt, TT, coef + (size_t)c0 * N, coef + (size_t)c0 * N, eo(), ntmp(), 2 * cn, st);
+        ntt_split_forward(SP, eo(), lde + (size_t)c0 * M2, M2, cn, st);
+      }
+    } else if (pl.log_r && pl.lowmem) {
+      for (int c0 = 0; c0 < nc; c0 += CH) {
+        const int cn = std::min(CH, nc - c0);
+        ntt_inverse_lde_tall(&c->ntt, TT, vals + (size_t)c0 * N, coef + (size_t)c0 * N, lde + (size_t)c0 * M2, tmp, cn, st);
+      }
+    } else if (pl.log_r) {
+      ntt_inverse_lde_tall(&c->ntt, TT, vals, coef, lde, tmp, nc, st);
+    } else {
+      ntt_inverse_lde(&c->ntt, vals, coef, lde, tmp, tmp + (size_t)nc * N, nc, st);
+    }
+  }
+  void lde(const u64* coef, u64* out, int nc) const {
+    const size_t N = pl.N, M2 = pl.M2;
+    if (pl.log_s) {
+      for (int c0 = 0; c0 < nc; c0 += CH) {
+        const int cn = std::min(CH, nc - c0);
+        ntt_lde_tall(&c->ntt, TT, coef + (size_t)c0 * N, eo(), ntmp(), 2 * cn, st);
+        ntt_split_forward(SP, eo(), out + (size_t)c0 * M2, M2, cn, st);
+      }
+    } else if (pl.log_r) ntt_lde_tall(&c->ntt, TT, coef, out, tmp, nc, st);
+    else ntt_lde(&c->ntt, coef, out, tmp, nc, st);
+  }
+  // stream mode: the LDE of ONE column chunk (coefficients at `coef`, cn <= CH columns) into ldechunk
+  // (coset_mask: 1 / 2 = only coset 0 / 1 of the output, 3 = both; under the split level coset h of the N-point domain comes from
+  // coset h of both half transforms)
+  void lde_chunk(const u64* coef, int cn, int coset_mask = 3) const {
+    if (pl.log_s) {
+      ntt_lde_tall(&c->ntt, TT, coef, eo(), ntmp(), 2 * cn, st, coset_mask);
+      ntt_split_forward(SP, eo(), ldechunk, pl.M2, cn, st, coset_mask);
+    } else {
+      ntt_lde_tall(&c->ntt, TT, coef, ldechunk, tmp, cn, st, coset_mask);
+    }
+  }
+  // stream mode: one pass of chunk LDEs over the nc columns at `coef`; use(c0, cn) takes what it needs out of ldechunk
+  template <class F>
+  void for_lde_chunks(const u64* coef, int nc, int coset_mask, F use) const {
+    for (int c0 = 0; c0 < nc; c0 += CH) {
+      const int cn = std::min(CH, nc - c0);
+      lde_chunk(coef + (size_t)c0 * pl.N, cn, coset_mask);
+      use(c0, cn);
+    }
+  }
+  // stream mode: from_values of a commitment, chunk by chunk: coefficients stay, the chunk's LDE is absorbed by the leaf hash
+  void commit_stream(const u64* vals, u64* coef, int nc, u64* tree) const {
+    const size_t N = pl.N, M2 = pl.M2;
+    for (int c0 = 0; c0 < nc; c0 += CH) {
+      const int cn = std::min(CH, nc - c0);
+      if (pl.log_s) {
+        ntt_split_inverse(SP, vals + (size_t)c0 * N, coef + (size_t)c0 * N, cn, st);
+        ntt_inverse_lde_tall(&c->ntt, TT, coef + (size_t)c0 * N, coef + (size_t)c0 * N, eo(), ntmp(), 2 * cn, st);
+        ntt_split_forward(SP, eo(), ldechunk, M2, cn, st);
+      } else {
+        ntt_inverse_lde_tall(&c->ntt, TT, vals + (size_t)c0 * N, coef + (size_t)c0 * N, ldechunk, tmp, cn, st);
+      }
+      merkle_absorb(ldechunk, M2, cn, (int)pl.log_m2, sponge, c0 == 0, c0 + cn == nc ? tree : nullptr, st);
+    }
+  }
+  // quotient values qv[2 alphas][2 cosets][N] (natural order on each coset) -> their coset interpolants ab, same layout
+  void quotient_coset_inverse(const u64* qv, u64* ab) const {
+    const size_t N = pl.N;
+    for (int a = 0; a < 2; a++)
+      for (int h = 0; h < 2; h++)
+        if (pl.log_s) ntt_coset_inverse_split(&c->ntt, TT, SP, h, qv + (size_t)(a * 2 + h) * N, ab + (size_t)(a * 2 + h) * N, tmp, 1, st);
+        else if (pl.log_r) ntt_coset_inverse_tall(&c->ntt, TT, h, qv + (size_t)(a * 2 + h) * N, ab + (size_t)(a * 2 + h) * N, tmp, 1, st);
+        else ntt_coset_inverse(&c->ntt, h, qv + (size_t)(a * 2 + h) * N, ab + (size_t)(a * 2 + h) * N, tmp, 1, st);
+  }
+};
+
+// ---- stages -----------------------------------------------------------------------------------------------------
+// What every stage of one proof works with.
+struct Run {
+  bn254s_ctx* c;
+  Slot& sl;
+  hipStream_t st;
+  const ProofPlan& pl;
+  Workspace& ws;
+  const Transforms& tf;
+  QPointTables pt;
+  // one begin/end event pair per stage (they belong to the slot); a stage's time never includes waiting for the big-kernel lock
+  void sb(int stage) const { hipEventRecord(sl.events[2 * stage], st); }
+  void se(int stage) const { hipEventRecord(sl.events[2 * stage + 1], st); }
+  // proofs running beside this one right now: the small Merkle levels use their throughput kernels then (merkle.h; same digests)
+  int mmode() const { return c->workers.in_flight.load(std::memory_order_relaxed) >= 4 ? MERKLE_THROUGHPUT : MERKLE_LATENCY; }
+};
+
+// Uploads the job arrays to d_in = [scalars | x | offsets] and launches the kind's trace generator (shared by the trace stage and
+// bn254s_generate_trace, which differ in stream, scratch owner and with_range).
+static int upload_and_generate(const StarkKind& sk, const u64* scalars, const u64* x, const u64* off, size_t n, u64* d_in, u64* d_trace,
+                               size_t N, u64* d_scr, u64* d_outs, int* d_err, hipStream_t st, bool with_range, std::string& err) {
+  const size_t PW = sk.point_words;
   u64* d_sc = d_in;
   u64* d_x = d_in + 4 * n;
-  u64* d_off = d_x + (size_t)PW * n;
+  u64* d_off = d_x + PW * n;
   CHK(hipMemcpyAsync(d_sc, scalars, n * 32, hipMemcpyHostToDevice, st));
-  CHK(hipMemcpyAsync(d_x, x, n * (size_t)PW * 8, hipMemcpyHostToDevice, st));
-  if (kind != KIND_FQ) CHK(hipMemcpyAsync(d_off, off, n * (size_t)PW * 8, hipMemcpyHostToDevice, st));
-  u64* d_outs = d_open;  // n*PW words fit (reused later)
-  int trc = kind == KIND_G1   ? g1_generate_trace_device(d_sc, d_x, d_off, n, d_tvals, N, d_scr, d_outs, d_err, st, false)
-            : kind == KIND_G2 ? g2_generate_trace_device(d_sc, d_x, d_off, n, d_tvals, N, d_scr, d_outs, d_err, st, false)
-                              : fq_generate_trace_device(d_sc, d_x, n, d_tvals, N, d_scr, d_outs, d_err, st, false);
-  if (trc) {
+  CHK(hipMemcpyAsync(d_x, x, n * PW * 8, hipMemcpyHostToDevice, st));
+  if (sk.has_offset) CHK(hipMemcpyAsync(d_off, off, n * PW * 8, hipMemcpyHostToDevice, st));
+  if (sk.generate_trace(d_sc, d_x, d_off, n, d_trace, N, d_scr, d_outs, d_err, st, with_range)) {
     err = "trace generation launch failed";
     return BN254S_E_HIP;
   }
+  return BN254S_OK;
+}
+
+// trace generation (scalar_mul_stark.rs:55-69); *h_err is valid after the next synchronisation of the stream
+static int stage_trace(const Run& r, const u64* scalars, const u64* x, const u64* off, bn254s_proof* pr, int* h_err, std::string& err) {
+  const ProofPlan& pl = r.pl;
+  const Workspace& ws = r.ws;
+  const StarkShape& sh = pl.sh;
+  hipStream_t st = r.st;
+  r.sb(ST_TRACE);
+  CHK(hipMemsetAsync(ws.err, 0, 16, st));
+  u64* d_outs = ws.open;  // n*PW words fit (reused later)
+  if (int rc = upload_and_generate(stark_kind(pl.kind), scalars, x, off, pl.n, ws.in, ws.tvals, pl.N, ws.scr, d_outs, ws.err, st, false, err))
+    return rc;
   {
     // generate_range_checks: the histogram keeps 128 KB of LDS per workgroup on every CU, which would lock another proof's
     // NTT tiles (35 KB each) out of the CUs it shares: it takes its turn like the other wide kernels
-    BigSection big(c, st, BIG_EXCL);
-    launch_range_columns(d_tvals, N, sh.rc_begin, sh.rc_end, sh.freq_col, sh.table_col, (u32*)d_hist, d_err, st);
+    BigSection big(r.c, st, BIG_EXCL);
+    launch_range_columns(ws.tvals, pl.N, sh.rc_begin, sh.rc_end, sh.freq_col, sh.table_col, (u32*)ws.hist, ws.err, st);
   }
-  pr->outputs.resize(n * (size_t)PW);
-  int h_err = 0;
-  CHK(hipMemcpyAsync(pr->outputs.data(), d_outs, n * (size_t)PW * 8, hipMemcpyDeviceToHost, st));
-  CHK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
-  se(ST_TRACE);
+  pr->outputs.resize(pl.n * (size_t)pl.PW);
+  CHK(hipMemcpyAsync(pr->outputs.data(), d_outs, pl.n * (size_t)pl.PW * 8, hipMemcpyDeviceToHost, st));
+  CHK(hipMemcpyAsync(h_err, ws.err, 4, hipMemcpyDeviceToHost, st));
+  r.se(ST_TRACE);
+  return BN254S_OK;
+}
 
-  // ---- trace commitment (prover.rs:31-38) -----------------------------------------------------------------
-  if (stream) {  // (the NTT and the leaf hash alternate chunk by chunk: one section, timed as the NTT stage)
-    BigSection big(c, st, BIG_NTT);
-    sb(ST_TRACE_NTT);
-    commit_stream(d_tvals, d_tcoef, W, d_ttree);
-    se(ST_TRACE_NTT);
-    sb(ST_TRACE_MERKLE);
+// leaf hash of a resident commitment: one GPU-filling section, or (BN254S_HASH_SPLIT, 2^16-row proofs) several shorter ones
+static void hash_sections(const Run& r, const u64* lde, int width, u64* tree, int stage) {
+  bn254s_ctx* c = r.c;
+  const size_t M2 = r.pl.M2;
+  const int S = r.pl.log_n == 16 ? c->hash_split : 1;
+  if (S <= 1) {
+    BigSection big(c, r.st, BIG_HASH);
+    r.sb(stage);  // (the stage's clock starts once the section is admitted)
+    merkle_leaves(lde, 1, M2, width, r.pl.log_m2, tree, r.st);
+    return;
+  }
+  const size_t cnt = M2 / S;
+  for (int k = 0; k < S; k++) {
+    BigSection big(c, r.st, BIG_HASH_PART);
+    if (k == 0) r.sb(stage);
+    merkle_leaves_range(lde, 1, M2, width, (size_t)k * cnt, cnt, tree, r.st);
+  }
+}
+
+// PolynomialBatch::from_values of `width` columns (prover.rs:31-38): coefficients, LDE, Merkle tree; the cap lands in cap_out
+// (valid on return).  Streaming workspace: no LDE is kept (`lde` is unused), the NTT and the leaf hash alternate chunk by chunk
+// in one section, timed as the NTT stage.
+static int commit(const Run& r, const u64* vals, u64* coef, u64* lde, int width, u64* tree, int ntt_stage, int merkle_stage,
+                  u64* cap_out, std::string& err) {
+  const ProofPlan& pl = r.pl;
+  hipStream_t st = r.st;
+  if (pl.stream) {
+    BigSection big(r.c, st, BIG_NTT);
+    r.sb(ntt_stage);
+    r.tf.commit_stream(vals, coef, width, tree);
+    r.se(ntt_stage);
+    r.sb(merkle_stage);
   } else {
     {
-      BigSection big(c, st, BIG_NTT);
-      sb(ST_TRACE_NTT);
-      do_commit_ntt(d_tvals, d_tcoef, d_tlde, W);
-      se(ST_TRACE_NTT);
+      BigSection big(r.c, st, BIG_NTT);
+      r.sb(ntt_stage);
+      r.tf.commit_ntt(vals, coef, lde, width);
+      r.se(ntt_stage);
     }
-    hash_sections(d_tlde, W, d_ttree, ST_TRACE_MERKLE);
+    hash_sections(r, lde, width, tree, merkle_stage);
   }
-  merkle_upper(log_m2, P.cap_height, d_ttree, st, mmode());
-  u64 caps[3][64];
-  CHK(hipMemcpyAsync(caps[0], d_ttree + cap_off, CAPW * 8, hipMemcpyDeviceToHost, st));
-  se(ST_TRACE_MERKLE);
+  merkle_upper(pl.log_m2, pl.P.cap_height, tree, st, r.mmode());
+  CHK(hipMemcpyAsync(cap_out, tree + r.ws.cap_off, ProofPlan::CAPW * 8, hipMemcpyDeviceToHost, st));
+  r.se(merkle_stage);
   CHK(hipStreamSynchronize(st));
-  if (h_err) {
-    err = "trace generation reported device error " + std::to_string(h_err);
-    cleanup_events();
-    return h_err;
-  }
+  return BN254S_OK;
+}
 
-  // ---- transcript: trace cap, CTL challenges, compact (prover.rs:40-54) --------------------------------
-  Challenger ch;
-  ch.observe_n(caps[0], CAPW);
-  u64 betas[2], gammas[2];
-  for (int i = 0; i < 2; i++) {
-    betas[i] = ch.challenge();
-    gammas[i] = ch.challenge();
-  }
-  u64 init_state[12];
-  ch.compact(init_state);
+// auxiliary columns: LogUp helpers and running sums, CTL running sums
+static void stage_aux(const Run& r, const u64 betas[2], const u64 gammas[2]) {
+  BigSection big(r.c, r.st, BIG_EXCL);
+  r.sb(ST_AUX);
+  aux_build(r.pl.sh, r.ws.tvals, r.pl.N, betas, gammas, r.ws.avals, r.ws.scr, r.ws.err, r.st);
+  r.se(ST_AUX);
+}
 
-  // ---- auxiliary columns + commitment ---------------------------------------------------------------------
-  {
-    BigSection big(c, st, BIG_EXCL);
-    sb(ST_AUX);
-    aux_build(sh, d_tvals, N, betas, gammas, d_avals, d_scr, d_err, st);
-    se(ST_AUX);
-  }
-  u64 *d_tw = nullptr, *d_aw = nullptr, *d_wpt = nullptr, *d_qrows = nullptr;
-  if (stream) {
-    // the trace values are dead: their memory becomes the quotient windows (all columns x WROWS rows), the window's point tables
-    // and the leaf rows of the queries
-    CHK(hipStreamSynchronize(st));
-    mem.drop("tvals");
-    d_tvals = nullptr;
-    u64* win = mem.words("win", (size_t)(W + A) * WROWS + 3 * WROWS + (size_t)(W + A) * P.num_queries);
-    if (!win) {
-      err = mem.err;
-      mem.release();
-      return BN254S_E_OOM;
+// Streaming workspace: the quotient values per coset and window of BK consecutive rows: the LDE of every column chunk is
+// recomputed and the window's rows (plus the next one) are taken out in natural order; the quotient kernels then run on the window
+// (QArgs window mode).
+static void quotient_over_windows(const Run& r, const u64 betas[2], const u64 gammas[2]) {
+  const ProofPlan& pl = r.pl;
+  const Workspace& ws = r.ws;
+  hipStream_t st = r.st;
+  const size_t N = pl.N, M2 = pl.M2, BK = pl.BK, WROWS = pl.WROWS;
+  BigSection big(r.c, st, BIG_NTT);
+  r.sb(ST_QUOTIENT);
+  QPointTables wpt;
+  wpt.x = ws.wpt;
+  wpt.lfirst = ws.wpt + WROWS;
+  wpt.llast = ws.wpt + 2 * WROWS;
+  for (int h = 0; h < 2; h++)
+    for (size_t k0 = 0; k0 < N; k0 += BK) {
+      r.tf.for_lde_chunks(ws.tcoef, pl.W, 1 << h, [&](int c0, int cn) {
+        fri_extract_window(ws.ldechunk, M2, pl.log_n, h, k0, WROWS, cn, ws.tw + (size_t)c0 * WROWS, st);
+      });
+      r.tf.for_lde_chunks(ws.acoef, pl.A, 1 << h, [&](int c0, int cn) {
+        fri_extract_window(ws.ldechunk, M2, pl.log_n, h, k0, WROWS, cn, ws.aw + (size_t)c0 * WROWS, st);
+      });
+      quotient_point_tables_window(ws.wpt, ws.wpt + WROWS, ws.wpt + 2 * WROWS, pl.log_n, h, k0, WROWS, st);
+      QArgs QA;
+      quotient_fill_args(QA, pl.sh, nullptr, nullptr, ws.W, ws.mzt, r.pt, betas, gammas, pl.log_n, ws.qv, ws.qpart);
+      quotient_window_args(QA, ws.tw, ws.aw, wpt, ws.qpart, WROWS, BK, k0, h);
+      stark_kind(pl.kind).quotient_launch(QA, pl.sh, st);
     }
-    d_tw = win;
-    d_aw = win + (size_t)W * WROWS;
-    d_wpt = d_aw + (size_t)A * WROWS;
-    d_qrows = d_wpt + 3 * WROWS;
-    BigSection big(c, st, BIG_NTT);
-    sb(ST_AUX_NTT);
-    commit_stream(d_avals, d_acoef, A, d_atree);
-    se(ST_AUX_NTT);
-    sb(ST_AUX_MERKLE);
-  } else {
-    {
-      BigSection big(c, st, BIG_NTT);
-      sb(ST_AUX_NTT);
-      do_commit_ntt(d_avals, d_acoef, d_alde, A);
-      se(ST_AUX_NTT);
-    }
-    hash_sections(d_alde, A, d_atree, ST_AUX_MERKLE);
-  }
-  merkle_upper(log_m2, P.cap_height, d_atree, st, mmode());
-  CHK(hipMemcpyAsync(caps[1], d_atree + cap_off, CAPW * 8, hipMemcpyDeviceToHost, st));
-  se(ST_AUX_MERKLE);
-  CHK(hipStreamSynchronize(st));
-  ch.observe_n(caps[1], CAPW);
-  u64 alphas[2] = {ch.challenge(), 0};
-  alphas[1] = ch.challenge();
+}
 
-  // ---- quotient ---------------------------------------------------------------------------------------------
+// quotient values on both cosets, their four chunk polynomials, and the quotient commitment; the cap lands in cap_out
+static int stage_quotient(const Run& r, const u64 alphas[2], const u64 betas[2], const u64 gammas[2], u64* cap_out, std::string& err) {
+  const ProofPlan& pl = r.pl;
+  const Workspace& ws = r.ws;
+  const StarkKind& sk = stark_kind(pl.kind);
+  hipStream_t st = r.st;
+  const size_t N = pl.N;
   {
     std::vector<u64> hW, hmzt;
     const int* mz_e0 = nullptr;
-    int nblk = kind == KIND_G1 ? g1_quotient_mz_blocks(&mz_e0) : kind == KIND_G2 ? g2_quotient_mz_blocks(&mz_e0) : fq_quotient_mz_blocks(&mz_e0);
-    quotient_host_tables(K, alphas, mz_e0, nblk, hW, hmzt);
-    CHK(hipMemcpyAsync(d_W, hW.data(), hW.size() * 8, hipMemcpyHostToDevice, st));
-    CHK(hipMemcpyAsync(d_mzt, hmzt.data(), hmzt.size() * 8, hipMemcpyHostToDevice, st));
+    const int nblk = sk.mz_blocks(&mz_e0);
+    quotient_host_tables(pl.K, alphas, mz_e0, nblk, hW, hmzt);
+    CHK(hipMemcpyAsync(ws.W, hW.data(), hW.size() * 8, hipMemcpyHostToDevice, st));
+    CHK(hipMemcpyAsync(ws.mzt, hmzt.data(), hmzt.size() * 8, hipMemcpyHostToDevice, st));
     CHK(hipStreamSynchronize(st));  // host vectors go out of scope
   }
-  if (stream) {
-    // per coset and window of BK consecutive rows: the LDE of every column chunk is recomputed and the window's rows (plus the next
-    // one) are taken out in natural order; the quotient kernels then run on the window (QArgs window mode)
-    BigSection big(c, st, BIG_NTT);
-    sb(ST_QUOTIENT);
-    QPointTables wpt;
-    wpt.x = d_wpt;
-    wpt.lfirst = d_wpt + WROWS;
-    wpt.llast = d_wpt + 2 * WROWS;
-    for (int h = 0; h < 2; h++)
-      for (size_t k0 = 0; k0 < N; k0 += BK) {
-        for (int c0 = 0; c0 < W; c0 += CH) {
-          const int cn = std::min(CH, W - c0);
-          lde_chunk(d_tcoef + (size_t)c0 * N, cn, 1 << h);
-          fri_extract_window(d_ldechunk, M2, log_n, h, k0, WROWS, cn, d_tw + (size_t)c0 * WROWS, st);
-        }
-        for (int c0 = 0; c0 < A; c0 += CH) {
-          const int cn = std::min(CH, A - c0);
-          lde_chunk(d_acoef + (size_t)c0 * N, cn, 1 << h);
-          fri_extract_window(d_ldechunk, M2, log_n, h, k0, WROWS, cn, d_aw + (size_t)c0 * WROWS, st);
-        }
-        quotient_point_tables_window(d_wpt, d_wpt + WROWS, d_wpt + 2 * WROWS, log_n, h, k0, WROWS, st);
-        QArgs QA;
-        quotient_fill_args(QA, sh, nullptr, nullptr, d_W, d_mzt, pt, betas, gammas, log_n, d_qv, d_qpart);
-        quotient_window_args(QA, d_tw, d_aw, wpt, d_qpart, WROWS, BK, k0, h);
-        if (kind == KIND_G1) g1_quotient_launch(QA, sh, st);
-        else if (kind == KIND_G2) g2_quotient_launch(QA, sh, st);
-        else fq_quotient_launch(QA, sh, st);
-      }
+  if (pl.stream) {
+    quotient_over_windows(r, betas, gammas);
   } else {
-    BigSection big(c, st, BIG_EXCL);
-    sb(ST_QUOTIENT);
+    BigSection big(r.c, st, BIG_EXCL);
+    r.sb(ST_QUOTIENT);
     QArgs QA;
-    quotient_fill_args(QA, sh, d_tlde, d_alde, d_W, d_mzt, pt, betas, gammas, log_n, d_qv, d_qpart);
-    if (kind == KIND_G1) g1_quotient_launch(QA, sh, st);
-    else if (kind == KIND_G2) g2_quotient_launch(QA, sh, st);
-    else fq_quotient_launch(QA, sh, st);
+    quotient_fill_args(QA, pl.sh, ws.tlde, ws.alde, ws.W, ws.mzt, r.pt, betas, gammas, pl.log_n, ws.qv, ws.qpart);
+    sk.quotient_launch(QA, pl.sh, st);
   }
-  for (int a = 0; a < 2; a++)
-    for (int h = 0; h < 2; h++)
-      if (log_s) ntt_coset_inverse_split(&c->ntt, TT, SP, h, d_qv + (size_t)(a * 2 + h) * N, d_ab + (size_t)(a * 2 + h) * N, d_tmp, 1, st);
-      else if (log_r) ntt_coset_inverse_tall(&c->ntt, TT, h, d_qv + (size_t)(a * 2 + h) * N, d_ab + (size_t)(a * 2 + h) * N, d_tmp, 1, st);
-      else ntt_coset_inverse(&c->ntt, h, d_qv + (size_t)(a * 2 + h) * N, d_ab + (size_t)(a * 2 + h) * N, d_tmp, 1, st);
+  r.tf.quotient_coset_inverse(ws.qv, ws.ab);
   {
     u64 gn = gl_pow(GL_GEN, N);
     u64 inv2 = gl_inv(2), inv2c = gl_inv(gl_mul(2, gn));
     dim3 g((unsigned)((N + 255) / 256), 2);
-    k_quotient_chunks<<<g, 256, 0, st>>>(d_ab, d_qcoef, N, inv2, inv2c);
+    k_quotient_chunks<<<g, 256, 0, st>>>(ws.ab, ws.qcoef, N, inv2, inv2c);
   }
-  se(ST_QUOTIENT);
-  sb(ST_QUOTIENT_COMMIT);
-  do_lde(d_qcoef, d_qlde, NQ);
-  merkle_build(d_qlde, 1, M2, NQ, log_m2, P.cap_height, d_qtree, st, mmode());
-  CHK(hipMemcpyAsync(caps[2], d_qtree + cap_off, CAPW * 8, hipMemcpyDeviceToHost, st));
-  se(ST_QUOTIENT_COMMIT);
+  r.se(ST_QUOTIENT);
+  r.sb(ST_QUOTIENT_COMMIT);
+  r.tf.lde(ws.qcoef, ws.qlde, ProofPlan::NQ);
+  merkle_build(ws.qlde, 1, pl.M2, ProofPlan::NQ, pl.log_m2, pl.P.cap_height, ws.qtree, st, r.mmode());
+  CHK(hipMemcpyAsync(cap_out, ws.qtree + ws.cap_off, ProofPlan::CAPW * 8, hipMemcpyDeviceToHost, st));
+  r.se(ST_QUOTIENT_COMMIT);
   CHK(hipStreamSynchronize(st));
-  ch.observe_n(caps[2], CAPW);
-  gl2 zeta = ch.challenge_ext();
-  {
-    gl2 zp = zeta;
-    for (unsigned i = 0; i < log_n; i++) zp = gl2_mul(zp, zp);
-    if (gl2_eq(zp, gl2_make(1, 0))) {
-      err = "Opening point is in the subgroup.";
-      cleanup_events();
-      return BN254S_E_TRANSCRIPT;
-    }
-  }
-  const u64 g = gl_root_of_unity(log_n);
-  gl2 zeta_next = gl2_mul_base(zeta, g);
+  return BN254S_OK;
+}
 
-  // ---- openings (StarkOpeningSet::new) ---------------------------------------------------------------------
+// openings on the device (StarkOpeningSet::new): partial evaluations per polynomial and block, copied to h_part (valid on return)
+static int stage_openings(const Run& r, gl2 zeta, gl2 zeta_next, u64* h_part, std::string& err) {
+  const ProofPlan& pl = r.pl;
+  const Workspace& ws = r.ws;
+  hipStream_t st = r.st;
+  const int W = pl.W, A = pl.A, NQ = ProofPlan::NQ, NSPL = pl.NSPL;
+  const size_t R = pl.R, NH = pl.NH;
   {
-    BigSection big(c, st, BIG_EXCL);
-    sb(ST_OPENINGS);
+    BigSection big(r.c, st, BIG_EXCL);
+    r.sb(ST_OPENINGS);
     // split level: P(z) = Pe(z^2) + z Po(z^2), the halves are polynomials of NH coefficients opened at z^2 and (g z)^2
-    u64* d_otab = d_open + (size_t)(W + A + NQ) * NSPL * R * 5;
-    fri_opening_tables(log_r, log_s ? gl2_mul(zeta, zeta) : zeta, log_s ? gl2_mul(zeta_next, zeta_next) : zeta_next, d_otab, st);
-    fri_openings(d_tcoef, NH, log_r, W * NSPL, d_otab, d_open, st);
-    fri_openings(d_acoef, NH, log_r, A * NSPL, d_otab, d_open + (size_t)W * NSPL * R * 5, st);
-    fri_openings(d_qcoef, NH, log_r, NQ * NSPL, d_otab, d_open + (size_t)(W + A) * NSPL * R * 5, st);
+    u64* d_otab = ws.open + pl.n_part();
+    fri_opening_tables(pl.log_r, pl.log_s ? gl2_mul(zeta, zeta) : zeta, pl.log_s ? gl2_mul(zeta_next, zeta_next) : zeta_next, d_otab, st);
+    fri_openings(ws.tcoef, NH, pl.log_r, W * NSPL, d_otab, ws.open, st);
+    fri_openings(ws.acoef, NH, pl.log_r, A * NSPL, d_otab, ws.open + (size_t)W * NSPL * R * 5, st);
+    fri_openings(ws.qcoef, NH, pl.log_r, NQ * NSPL, d_otab, ws.open + (size_t)(W + A) * NSPL * R * 5, st);
   }
-  // device -> host copies land in the slot's pinned staging buffer (pageable destinations go through a runtime-internal
-  // staging allocation that costs ~8 ms the first time and an extra copy every time)
-  const size_t n_part = (size_t)(W + A + NQ) * NSPL * R * 5, n_q = wpq * P.num_queries;
-  u64* h_part = (u64*)sl.pinned;
-  std::vector<u64> h_open((size_t)(W + A + NQ) * 5);
-  CHK(hipMemcpyAsync(h_part, d_open, n_part * 8, hipMemcpyDeviceToHost, st));
-  se(ST_OPENINGS);
+  CHK(hipMemcpyAsync(h_part, ws.open, pl.n_part() * 8, hipMemcpyDeviceToHost, st));
+  r.se(ST_OPENINGS);
   CHK(hipStreamSynchronize(st));
-  {  // P(z) = sum_k1 z^k1 S_k1(z^R) (transposed coefficient layout); P(1) = sum of the block sums
-    std::vector<gl2> zp0(R), zp1(R);
-    gl2 a = gl2_make(1, 0), b = gl2_make(1, 0);
-    const gl2 y0 = log_s ? gl2_mul(zeta, zeta) : zeta, y1 = log_s ? gl2_mul(zeta_next, zeta_next) : zeta_next;
-    for (size_t k1 = 0; k1 < R; k1++) {
-      zp0[k1] = a;
-      zp1[k1] = b;
-      a = gl2_mul(a, y0);
-      b = gl2_mul(b, y1);
-    }
-    for (int p = 0; p < W + A + NQ; p++) {
-      gl2 v0 = gl2_make(0, 0), v1 = gl2_make(0, 0);
-      u64 s1 = 0;
-      for (int half = 0; half < NSPL; half++) {
-        gl2 e0 = gl2_make(0, 0), e1 = gl2_make(0, 0);
-        for (size_t k1 = 0; k1 < R; k1++) {
-          const u64* q = &h_part[(((size_t)p * NSPL + half) * R + k1) * 5];
-          e0 = gl2_add(e0, gl2_mul(zp0[k1], gl2_make(q[0], q[1])));
-          e1 = gl2_add(e1, gl2_mul(zp1[k1], gl2_make(q[2], q[3])));
-          s1 = gl_add(s1, q[4]);
-        }
-        v0 = gl2_add(v0, half ? gl2_mul(zeta, e0) : e0);
-        v1 = gl2_add(v1, half ? gl2_mul(zeta_next, e1) : e1);
-      }
-      u64* o5 = &h_open[(size_t)p * 5];
-      o5[0] = v0.c0; o5[1] = v0.c1; o5[2] = v1.c0; o5[3] = v1.c1; o5[4] = s1;
-    }
+  return BN254S_OK;
+}
+
+// Recombination of the opening partials: P(z) = sum_k1 z^k1 S_k1(z^R) (transposed coefficient layout); P(1) = sum of the block
+// sums.  h_open[p] = {P(zeta).c0, .c1, P(g zeta).c0, .c1, P(1)} for p over (trace | auxiliary | quotient chunks).
+static std::vector<u64> recombine_openings(const ProofPlan& pl, const u64* h_part, gl2 zeta, gl2 zeta_next) {
+  const size_t R = pl.R;
+  const int NSPL = pl.NSPL, n_polys = pl.W + pl.A + ProofPlan::NQ;
+  std::vector<u64> h_open((size_t)n_polys * 5);
+  std::vector<gl2> zp0(R), zp1(R);
+  gl2 a = gl2_make(1, 0), b = gl2_make(1, 0);
+  const gl2 y0 = pl.log_s ? gl2_mul(zeta, zeta) : zeta, y1 = pl.log_s ? gl2_mul(zeta_next, zeta_next) : zeta_next;
+  for (size_t k1 = 0; k1 < R; k1++) {
+    zp0[k1] = a;
+    zp1[k1] = b;
+    a = gl2_mul(a, y0);
+    b = gl2_mul(b, y1);
   }
-  const int num_lookup = sh.n_lookup_cols(), n_ctlz = 2 * sh.n_ctl;
-  auto op = [&](int p, int k) { return h_open[(size_t)p * 5 + k]; };
-  // to_fri_openings order: (local | aux | quotient) at zeta, (next | aux_next) at g*zeta, ctl_zs_first
+  for (int p = 0; p < n_polys; p++) {
+    gl2 v0 = gl2_make(0, 0), v1 = gl2_make(0, 0);
+    u64 s1 = 0;
+    for (int half = 0; half < NSPL; half++) {
+      gl2 e0 = gl2_make(0, 0), e1 = gl2_make(0, 0);
+      for (size_t k1 = 0; k1 < R; k1++) {
+        const u64* q = &h_part[(((size_t)p * NSPL + half) * R + k1) * 5];
+        e0 = gl2_add(e0, gl2_mul(zp0[k1], gl2_make(q[0], q[1])));
+        e1 = gl2_add(e1, gl2_mul(zp1[k1], gl2_make(q[2], q[3])));
+        s1 = gl_add(s1, q[4]);
+      }
+      v0 = gl2_add(v0, half ? gl2_mul(zeta, e0) : e0);
+      v1 = gl2_add(v1, half ? gl2_mul(zeta_next, e1) : e1);
+    }
+    u64* o5 = &h_open[(size_t)p * 5];
+    o5[0] = v0.c0; o5[1] = v0.c1; o5[2] = v1.c0; o5[3] = v1.c1; o5[4] = s1;
+  }
+  return h_open;
+}
+
+// The opening set as the transcript and the proof see it: value k of polynomial p of h_open, and where the CTL running sums sit.
+struct Openings {
+  const ProofPlan& pl;
+  const std::vector<u64>& h_open;
+  u64 operator()(int p, int k) const { return h_open[(size_t)p * 5 + k]; }
+  int n_ctlz() const { return 2 * pl.sh.n_ctl; }
+  u64 ctl_z_first(int i) const { return (*this)(pl.W + pl.sh.n_lookup_cols() + i, 4); }
+};
+
+// to_fri_openings order: (local | aux | quotient) at zeta, (next | aux_next) at g*zeta, ctl_zs_first
+static void observe_openings(Challenger& ch, const Openings& op) {
+  const int W = op.pl.W, A = op.pl.A, NQ = ProofPlan::NQ;
   for (int p = 0; p < W + A + NQ; p++) {
     ch.observe(op(p, 0));
     ch.observe(op(p, 1));
@@ -697,177 +660,228 @@ static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params&
     ch.observe(op(p, 2));
     ch.observe(op(p, 3));
   }
-  for (int i = 0; i < n_ctlz; i++) {
-    ch.observe(op(W + num_lookup + i, 4));
+  for (int i = 0; i < op.n_ctlz(); i++) {
+    ch.observe(op.ctl_z_first(i));
     ch.observe(0);
   }
+}
 
-  // ---- FRI (prove_openings) ------------------------------------------------------------------------------------
-  gl2 fri_alpha = ch.challenge_ext();
-  {
-    std::vector<u32> apow(8 * (size_t)(W + A + NQ), 0);  // alpha^p cut in 22-bit limbs (quotient_common.h W3), 8 u32 per power
-    gl2 ap = gl2_make(1, 0), r0 = gl2_make(0, 0), r1 = r0, r2 = r0;
-    for (int p = 0; p < W + A + NQ; p++) {
-      const W3 s0 = w3_split(ap.c0), s1 = w3_split(ap.c1);
-      u32* e = &apow[8 * (size_t)p];
-      e[0] = s0.w0; e[1] = s0.w1; e[2] = s0.w2;
-      e[4] = s1.w0; e[5] = s1.w1; e[6] = s1.w2;
-      r0 = gl2_add(r0, gl2_mul(ap, gl2_make(op(p, 0), op(p, 1))));
-      if (p < W + A) r1 = gl2_add(r1, gl2_mul(ap, gl2_make(op(p, 2), op(p, 3))));
-      if (p < n_ctlz) r2 = gl2_add(r2, gl2_mul_base(ap, op(W + num_lookup + p, 4)));
-      ap = gl2_mul(ap, fri_alpha);
-    }
-    CHK(hipMemcpyAsync(d_apow, apow.data(), apow.size() * 4, hipMemcpyHostToDevice, st));
-    CHK(hipStreamSynchronize(st));
-    BigSection big(c, st, BIG_EXCL);
-    sb(ST_FRI);
-    // The batch polynomial is linear in the committed polynomials: its three alpha-weighted sums are formed on the coefficient
-    // vectors (N points, not the 2N of the LDE; in the compact workspace d_acoef is d_avals, still live: the openings above read
-    // it), then one LDE of the six sum columns, then the point-wise part.  The same field elements as summing the LDE values.
-    fri_combine_coeffs(sh, d_tcoef, d_acoef, d_qcoef, d_apow, N, d_comb, st);
-    do_lde(d_comb, d_comb + (size_t)6 * N, 6);
-    fri_combine_final(sh, d_comb + (size_t)6 * N, pt.x, zeta, zeta_next, r0, r1, r2, fri_alpha, M2, d_fri, st);
+// The powers of the FRI batching challenge: alpha^p cut in 22-bit limbs (quotient_common.h W3), 8 u32 per power, for the device;
+// and the alpha-weighted sums of the openings of the three batches (at zeta, at g zeta, at 1).
+struct FriAlphaPowers {
+  std::vector<u32> apow;
+  gl2 r0, r1, r2;
+};
+static FriAlphaPowers fri_alpha_powers(const Openings& op, gl2 fri_alpha) {
+  const int W = op.pl.W, A = op.pl.A, NQ = ProofPlan::NQ, n_ctlz = op.n_ctlz();
+  FriAlphaPowers f;
+  f.apow.assign(8 * (size_t)(W + A + NQ), 0);
+  gl2 ap = gl2_make(1, 0);
+  f.r0 = f.r1 = f.r2 = gl2_make(0, 0);
+  for (int p = 0; p < W + A + NQ; p++) {
+    const W3 s0 = w3_split(ap.c0), s1 = w3_split(ap.c1);
+    u32* e = &f.apow[8 * (size_t)p];
+    e[0] = s0.w0; e[1] = s0.w1; e[2] = s0.w2;
+    e[4] = s1.w0; e[5] = s1.w1; e[6] = s1.w2;
+    f.r0 = gl2_add(f.r0, gl2_mul(ap, gl2_make(op(p, 0), op(p, 1))));
+    if (p < W + A) f.r1 = gl2_add(f.r1, gl2_mul(ap, gl2_make(op(p, 2), op(p, 3))));
+    if (p < n_ctlz) f.r2 = gl2_add(f.r2, gl2_mul_base(ap, op.ctl_z_first(p)));
+    ap = gl2_mul(ap, fri_alpha);
   }
-  std::vector<std::vector<u64>> layer_caps(L, std::vector<u64>(CAPW));
-  std::vector<const u64*> layer_vals(L), layer_trees(L);
-  u64* vals = d_fri;
-  u64* ftree = d_fritrees;
+  return f;
+}
+
+// FRI batch polynomial on the LDE domain (prove_openings -> the first layer's values in ws.fri)
+static int stage_fri_combine(const Run& r, const FriAlphaPowers& f, gl2 zeta, gl2 zeta_next, gl2 fri_alpha, std::string& err) {
+  const ProofPlan& pl = r.pl;
+  const Workspace& ws = r.ws;
+  hipStream_t st = r.st;
+  CHK(hipMemcpyAsync(ws.apow, f.apow.data(), f.apow.size() * 4, hipMemcpyHostToDevice, st));
+  CHK(hipStreamSynchronize(st));
+  BigSection big(r.c, st, BIG_EXCL);
+  r.sb(ST_FRI);
+  // The batch polynomial is linear in the committed polynomials: its three alpha-weighted sums are formed on the coefficient
+  // vectors (N points, not the 2N of the LDE; in the compact workspace acoef is avals, still live: the openings above read
+  // it), then one LDE of the six sum columns, then the point-wise part.  The same field elements as summing the LDE values.
+  fri_combine_coeffs(pl.sh, ws.tcoef, ws.acoef, ws.qcoef, ws.apow, pl.N, ws.comb, st);
+  r.tf.lde(ws.comb, ws.comb + (size_t)6 * pl.N, 6);
+  fri_combine_final(pl.sh, ws.comb + (size_t)6 * pl.N, r.pt.x, zeta, zeta_next, f.r0, f.r1, f.r2, fri_alpha, pl.M2, ws.fri, st);
+  return BN254S_OK;
+}
+
+// The committed FRI layers, and what is left after the last fold.
+struct FriLayers {
+  std::vector<std::vector<u64>> caps;
+  std::vector<const u64*> vals, trees;
+  const u64* last = nullptr;  // values of the final layer: 2^lm extension elements on the coset shift * <w>, bit-reversed
   u64 shift = GL_GEN;
-  unsigned lm = log_m2;
+  unsigned lm = 0;
+};
+
+// FRI commit phase: per layer the Merkle tree of the 16-element cosets, its cap into the transcript, the fold by the challenge
+static int stage_fri_commit(const Run& r, Challenger& ch, FriLayers& fl, std::string& err) {
+  const ProofPlan& pl = r.pl;
+  hipStream_t st = r.st;
+  const int L = pl.L, CAPW = ProofPlan::CAPW;
+  fl.caps.assign(L, std::vector<u64>(CAPW));
+  fl.vals.resize(L);
+  fl.trees.resize(L);
+  u64* vals = r.ws.fri;
+  u64* ftree = r.ws.fritrees;
+  fl.shift = GL_GEN;
+  unsigned lm = pl.log_m2;
   const u64 inv16 = gl_inv(16);
   for (int l = 0; l < L; l++) {
     const int lg = (int)lm - 4;
-    merkle_build(vals, 32, 1, 32, lg, P.cap_height, ftree, st, mmode());
-    CHK(hipMemcpyAsync(layer_caps[l].data(), ftree + 4 * merkle_level_offset(lg, lg - P.cap_height), CAPW * 8,
+    merkle_build(vals, 32, 1, 32, lg, pl.P.cap_height, ftree, st, r.mmode());
+    CHK(hipMemcpyAsync(fl.caps[l].data(), ftree + 4 * merkle_level_offset(lg, lg - pl.P.cap_height), CAPW * 8,
                        hipMemcpyDeviceToHost, st));
     CHK(hipStreamSynchronize(st));
-    ch.observe_n(layer_caps[l].data(), CAPW);
+    ch.observe_n(fl.caps[l].data(), CAPW);
     gl2 beta = ch.challenge_ext();
     u64* next = vals + 2 * ((size_t)1 << lm);
-    fri_fold(vals, next, lm, shift, beta, inv16, st);
-    layer_vals[l] = vals;
-    layer_trees[l] = ftree;
-    ftree += merkle_tree_digests(lg, P.cap_height) * 4;
+    fri_fold(vals, next, lm, fl.shift, beta, inv16, st);
+    fl.vals[l] = vals;
+    fl.trees[l] = ftree;
+    ftree += merkle_tree_digests(lg, pl.P.cap_height) * 4;
     vals = next;
-    shift = gl_pow(shift, 16);
+    fl.shift = gl_pow(fl.shift, 16);
     lm -= 4;
   }
-  // final polynomial: coset iDFT of the last (tiny) layer on the host, upper half must vanish
+  fl.last = vals;
+  fl.lm = lm;
+  return BN254S_OK;
+}
+
+// final polynomial: coset iDFT of the last (tiny) layer on the host, upper half must vanish
+static int fri_final_poly(const std::vector<u64>& h_final, unsigned lm, u64 shift, unsigned rate_bits, std::vector<gl2>& final_poly,
+                          std::string& err) {
   const size_t Mf = (size_t)1 << lm;
-  std::vector<u64> h_final(2 * Mf);
-  CHK(hipMemcpyAsync(h_final.data(), vals, h_final.size() * 8, hipMemcpyDeviceToHost, st));
-  CHK(hipStreamSynchronize(st));
-  std::vector<gl2> final_poly(Mf >> P.rate_bits);
-  {
-    const u64 w = gl_root_of_unity(lm), winv = gl_inv(w), sinv = gl_inv(shift), minv = gl_inv((u64)Mf);
-    for (size_t k = 0; k < Mf; k++) {
-      gl2 acc = gl2_make(0, 0);
-      u64 wk = gl_pow(winv, k), t = 1;
-      for (size_t nn = 0; nn < Mf; nn++) {  // value at natural index nn sits at position bitrev(nn)
-        size_t pos = bitrev32((u32)nn, lm);
-        acc = gl2_add(acc, gl2_mul_base(gl2_make(h_final[2 * pos], h_final[2 * pos + 1]), t));
-        t = gl_mul(t, wk);
-      }
-      acc = gl2_mul_base(acc, gl_mul(minv, gl_pow(sinv, k)));
-      if (k < final_poly.size()) final_poly[k] = acc;
-      else if (acc.c0 | acc.c1) {
-        err = "FRI final polynomial has non-zero high coefficients";
-        cleanup_events();
-        return BN254S_E_INTERNAL;
-      }
+  final_poly.assign(Mf >> rate_bits, gl2_make(0, 0));
+  const u64 w = gl_root_of_unity(lm), winv = gl_inv(w), sinv = gl_inv(shift), minv = gl_inv((u64)Mf);
+  for (size_t k = 0; k < Mf; k++) {
+    gl2 acc = gl2_make(0, 0);
+    u64 wk = gl_pow(winv, k), t = 1;
+    for (size_t nn = 0; nn < Mf; nn++) {  // value at natural index nn sits at position bitrev(nn)
+      size_t pos = bitrev32((u32)nn, lm);
+      acc = gl2_add(acc, gl2_mul_base(gl2_make(h_final[2 * pos], h_final[2 * pos + 1]), t));
+      t = gl_mul(t, wk);
     }
-  }
-  for (auto& cf : final_poly) {
-    ch.observe(cf.c0);
-    ch.observe(cf.c1);
-  }
-  // proof of work (fri_proof_of_work): smallest witness with >= pow_bits leading zeros in the response
-  u64 pow_witness = 0;
-  {
-    u64 stt[12];
-    memcpy(stt, ch.state, sizeof(stt));
-    for (int i = 0; i < ch.in_len; i++) stt[i] = ch.in_buf[i];
-    const size_t WIN = (size_t)1 << (P.pow_bits + 1);  // 86 % of the searches end in the first window
-    unsigned long long found = ~0ULL;
-    for (u64 base = 0; found == ~0ULL; base += WIN) {
-      CHK(hipMemsetAsync(d_pow, 0xFF, 8, st));
-      fri_pow_launch(stt, ch.in_len, base, P.pow_bits, WIN, d_pow, st);
-      CHK(hipMemcpyAsync(&found, d_pow, 8, hipMemcpyDeviceToHost, st));
-      CHK(hipStreamSynchronize(st));
-      if (base > ((u64)1 << 40)) {
-        err = "proof of work not found";
-        cleanup_events();
-        return BN254S_E_INTERNAL;
-      }
-    }
-    pow_witness = found;
-    ch.observe(pow_witness);
-    u64 resp = ch.challenge();
-    if (resp >> (64 - P.pow_bits)) {
-      err = "proof of work self-check failed";
-      cleanup_events();
+    acc = gl2_mul_base(acc, gl_mul(minv, gl_pow(sinv, k)));
+    if (k < final_poly.size()) final_poly[k] = acc;
+    else if (acc.c0 | acc.c1) {
+      err = "FRI final polynomial has non-zero high coefficients";
       return BN254S_E_INTERNAL;
     }
   }
-  // query rounds
-  std::vector<u32> qidx(P.num_queries);
-  for (auto& q : qidx) q = (u32)(ch.challenge() % M2);
-  CHK(hipMemcpyAsync(d_qidx, qidx.data(), qidx.size() * 4, hipMemcpyHostToDevice, st));
-  if (stream) {  // leaf rows of the queries: one more pass of chunk LDEs, 84 rows taken out of each
-    const int nq = (int)P.num_queries;
-    for (int c0 = 0; c0 < W; c0 += CH) {
-      const int cn = std::min(CH, W - c0);
-      lde_chunk(d_tcoef + (size_t)c0 * N, cn);
-      fri_gather_rows(d_ldechunk, M2, cn, d_qidx, nq, d_qrows + (size_t)c0 * nq, st);
+  return BN254S_OK;
+}
+
+// proof of work (fri_proof_of_work): smallest witness with >= pow_bits leading zeros in the response
+static int stage_pow(const Run& r, Challenger& ch, u64& pow_witness, std::string& err) {
+  const unsigned pow_bits = r.pl.P.pow_bits;
+  hipStream_t st = r.st;
+  u64 stt[12];
+  memcpy(stt, ch.state, sizeof(stt));
+  for (int i = 0; i < ch.in_len; i++) stt[i] = ch.in_buf[i];
+  const size_t WIN = (size_t)1 << (pow_bits + 1);  // 86 % of the searches end in the first window
+  unsigned long long found = ~0ULL;
+  for (u64 base = 0; found == ~0ULL; base += WIN) {
+    CHK(hipMemsetAsync(r.ws.pow, 0xFF, 8, st));
+    fri_pow_launch(stt, ch.in_len, base, pow_bits, WIN, r.ws.pow, st);
+    CHK(hipMemcpyAsync(&found, r.ws.pow, 8, hipMemcpyDeviceToHost, st));
+    CHK(hipStreamSynchronize(st));
+    if (base > ((u64)1 << 40)) {
+      err = "proof of work not found";
+      return BN254S_E_INTERNAL;
     }
-    for (int c0 = 0; c0 < A; c0 += CH) {
-      const int cn = std::min(CH, A - c0);
-      lde_chunk(d_acoef + (size_t)c0 * N, cn);
-      fri_gather_rows(d_ldechunk, M2, cn, d_qidx, nq, d_qrows + (size_t)(W + c0) * nq, st);
-    }
+  }
+  pow_witness = found;
+  ch.observe(pow_witness);
+  u64 resp = ch.challenge();
+  if (resp >> (64 - pow_bits)) {
+    err = "proof of work self-check failed";
+    return BN254S_E_INTERNAL;
+  }
+  return BN254S_OK;
+}
+
+// query rounds: the indices from the transcript, every opened row and Merkle path gathered on the device into h_q (valid on
+// return); closes the FRI stage and the proof's clock, and reads the device error word
+static int stage_queries(const Run& r, Challenger& ch, const FriLayers& fl, u64* h_q, std::string& err) {
+  const ProofPlan& pl = r.pl;
+  const Workspace& ws = r.ws;
+  hipStream_t st = r.st;
+  const int W = pl.W, A = pl.A, L = pl.L, nq = (int)pl.P.num_queries;
+  std::vector<u32> qidx(pl.P.num_queries);
+  for (auto& q : qidx) q = (u32)(ch.challenge() % pl.M2);
+  CHK(hipMemcpyAsync(ws.qidx, qidx.data(), qidx.size() * 4, hipMemcpyHostToDevice, st));
+  if (pl.stream) {  // leaf rows of the queries: one more pass of chunk LDEs, 84 rows taken out of each
+    r.tf.for_lde_chunks(ws.tcoef, W, 3, [&](int c0, int cn) {
+      fri_gather_rows(ws.ldechunk, pl.M2, cn, ws.qidx, nq, ws.qrows + (size_t)c0 * nq, st);
+    });
+    r.tf.for_lde_chunks(ws.acoef, A, 3, [&](int c0, int cn) {
+      fri_gather_rows(ws.ldechunk, pl.M2, cn, ws.qidx, nq, ws.qrows + (size_t)(W + c0) * nq, st);
+    });
   }
   {
     QueryGatherArgs G;
-    G.lde[0] = d_tlde; G.lde[1] = d_alde; G.lde[2] = d_qlde;
-    if (stream) {
-      G.lde[0] = d_qrows;
-      G.lde[1] = d_qrows + (size_t)W * P.num_queries;
+    G.lde[0] = ws.tlde; G.lde[1] = ws.alde; G.lde[2] = ws.qlde;
+    if (pl.stream) {
+      G.lde[0] = ws.qrows;
+      G.lde[1] = ws.qrows + (size_t)W * pl.P.num_queries;
       G.lde_by_query[0] = G.lde_by_query[1] = 1;
     }
-    G.tree[0] = d_ttree; G.tree[1] = d_atree; G.tree[2] = d_qtree;
-    G.width[0] = W; G.width[1] = A; G.width[2] = NQ;
+    G.tree[0] = ws.ttree; G.tree[1] = ws.atree; G.tree[2] = ws.qtree;
+    G.width[0] = W; G.width[1] = A; G.width[2] = ProofPlan::NQ;
     for (int l = 0; l < L; l++) {
-      G.layer_vals[l] = layer_vals[l];
-      G.layer_tree[l] = layer_trees[l];
+      G.layer_vals[l] = fl.vals[l];
+      G.layer_tree[l] = fl.trees[l];
     }
     G.n_layers = L;
-    G.log_m2 = log_m2;
-    G.cap_height = P.cap_height;
-    G.M2 = M2;
-    G.indices = d_qidx;
-    G.out = d_qout;
-    G.words_per_query = wpq;
-    fri_gather_queries(G, P.num_queries, st);
+    G.log_m2 = pl.log_m2;
+    G.cap_height = pl.P.cap_height;
+    G.M2 = pl.M2;
+    G.indices = ws.qidx;
+    G.out = ws.qout;
+    G.words_per_query = pl.wpq;
+    fri_gather_queries(G, pl.P.num_queries, st);
   }
-  u64* h_q = (u64*)sl.pinned;  // (the opening partials in it were consumed above)
-  CHK(hipMemcpyAsync(h_q, d_qout, n_q * 8, hipMemcpyDeviceToHost, st));
-  CHK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
-  se(ST_FRI);
-  se(ST_TOTAL);
+  int h_err = 0;
+  CHK(hipMemcpyAsync(h_q, ws.qout, pl.n_q() * 8, hipMemcpyDeviceToHost, st));
+  CHK(hipMemcpyAsync(&h_err, ws.err, 4, hipMemcpyDeviceToHost, st));
+  r.se(ST_FRI);
+  r.se(ST_TOTAL);
   CHK(hipStreamSynchronize(st));
   CHK(hipGetLastError());
   if (h_err) {
     err = "device self-check failed: " + std::to_string(h_err);
-    cleanup_events();
     return h_err;
   }
+  return BN254S_OK;
+}
 
-  // ---- assemble (layout: include/bn254_stark.h) ------------------------------------------------------------
+// What the host holds of a proof before its words are laid out.
+struct ProofParts {
+  u64 caps[3][64];  // trace, auxiliary, quotient
+  u64 init_state[12];
+  std::vector<u64> h_open;
+  FriLayers fri;
+  std::vector<gl2> final_poly;
+  u64 pow_witness = 0;
+  const u64* h_q = nullptr;  // query rounds (pinned staging)
+};
+
+// assemble (layout: include/bn254_stark.h)
+static void assemble_proof(const ProofPlan& pl, const ProofParts& pp, bn254s_proof* pr) {
+  const int W = pl.W, A = pl.A, NQ = ProofPlan::NQ, CAPW = ProofPlan::CAPW, L = pl.L;
+  const Openings op{pl, pp.h_open};
+  const int n_ctlz = op.n_ctlz();
   std::vector<u64>& o = pr->words;
   o.clear();
-  o.reserve(3 * CAPW + 4 * (W + A) + n_ctlz + 2 * NQ + L * CAPW + n_q + 2 * final_poly.size() + 13);
+  o.reserve(3 * CAPW + 4 * (W + A) + n_ctlz + 2 * NQ + L * CAPW + pl.n_q() + 2 * pp.final_poly.size() + 13);
   auto mark = [&](int id) { pr->sec_off[id] = o.size(); };
-  for (int t = 0; t < 3; t++) { mark(BN254S_SEC_TRACE_CAP + t); o.insert(o.end(), caps[t], caps[t] + CAPW); }
+  for (int t = 0; t < 3; t++) { mark(BN254S_SEC_TRACE_CAP + t); o.insert(o.end(), pp.caps[t], pp.caps[t] + CAPW); }
   mark(BN254S_SEC_LOCAL_VALUES);
   for (int p = 0; p < W; p++) { o.push_back(op(p, 0)); o.push_back(op(p, 1)); }
   mark(BN254S_SEC_NEXT_VALUES);
@@ -877,23 +891,137 @@ static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params&
   mark(BN254S_SEC_AUX_POLYS_NEXT);
   for (int p = W; p < W + A; p++) { o.push_back(op(p, 2)); o.push_back(op(p, 3)); }
   mark(BN254S_SEC_CTL_ZS_FIRST);
-  for (int i = 0; i < n_ctlz; i++) o.push_back(op(W + num_lookup + i, 4));
+  for (int i = 0; i < n_ctlz; i++) o.push_back(op.ctl_z_first(i));
   mark(BN254S_SEC_QUOTIENT_POLYS);
   for (int p = W + A; p < W + A + NQ; p++) { o.push_back(op(p, 0)); o.push_back(op(p, 1)); }
   mark(BN254S_SEC_FRI_CAPS);
-  for (int l = 0; l < L; l++) o.insert(o.end(), layer_caps[l].begin(), layer_caps[l].end());
+  for (int l = 0; l < L; l++) o.insert(o.end(), pp.fri.caps[l].begin(), pp.fri.caps[l].end());
   mark(BN254S_SEC_QUERY_ROUNDS);
-  o.insert(o.end(), h_q, h_q + n_q);
+  o.insert(o.end(), pp.h_q, pp.h_q + pl.n_q());
   mark(BN254S_SEC_FINAL_POLY);
-  for (auto& cf : final_poly) { o.push_back(cf.c0); o.push_back(cf.c1); }
+  for (auto& cf : pp.final_poly) { o.push_back(cf.c0); o.push_back(cf.c1); }
   mark(BN254S_SEC_POW_WITNESS);
-  o.push_back(pow_witness);
+  o.push_back(pp.pow_witness);
   mark(BN254S_SEC_INIT_CHALLENGER_STATE);
-  o.insert(o.end(), init_state, init_state + 12);
+  o.insert(o.end(), pp.init_state, pp.init_state + 12);
   mark(BN254S_SEC_COUNT);
-  pr->degree_bits = log_n;
-  for (int i = 0; i < ST_COUNT; i++) hipEventElapsedTime(&pr->stage_ms[i], ev[2 * i], ev[2 * i + 1]);
-  cleanup_events();
+  pr->degree_bits = pl.log_n;
+}
+
+// One proof on a slot: the stages in the order of starks/common/prover.rs, the transcript between them.
+// `after_alloc` (optional) is called once the workspace of the proof is complete: the out-of-memory retry of the batch entry
+// points holds WorkPool::retry_mu up to that point, so that allocation attempts never interleave.
+static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params& P, const u64* scalars, const u64* x,
+                         const u64* off, size_t n, bn254s_proof* pr, std::string& err,
+                         const std::function<void()>* after_alloc = nullptr) {
+  // which workspace the proof gets depends on the device's memory; the test overrides are read per call
+  size_t dev_free_b = 0, dev_total_b = 0;
+  (void)hipMemGetInfo(&dev_free_b, &dev_total_b);
+  ProofPlan pl;
+  if (int rc = proof_plan(kind, n, P, dev_total_b, plan_overrides_from_env(), pl, err)) return rc;
+  hipStream_t st = sl.st;
+  QPointTables pt;
+  if (int rc = get_point_tables(c, pl.log_n, pt)) {
+    err = "point tables";
+    return rc;
+  }
+  const NttTallTables* TT = nullptr;
+  const NttSplitTables* SP = nullptr;
+  if (pl.log_r) {
+    TT = get_tall_tables(c, pl.log_n - pl.log_s, pl.log_s != 0);
+    if (!TT) {
+      err = "tall NTT tables";
+      return BN254S_E_OOM;
+    }
+  }
+  if (pl.log_s) {
+    SP = get_split_tables(c, pl.log_n);
+    if (!SP) {
+      err = "split NTT tables";
+      return BN254S_E_OOM;
+    }
+  }
+  Workspace ws;
+  if (int rc = workspace_acquire(sl, pl, ws, err)) return rc;
+  if (after_alloc) (*after_alloc)();
+  const Transforms tf{c, st, TT, SP, pl, ws.tmp, ws.ldechunk, ws.sponge};
+  if (sl.events.empty()) {
+    sl.events.resize(2 * ST_COUNT);
+    for (auto& e : sl.events) CHK(hipEventCreate(&e));
+  }
+  const Run r{c, sl, st, pl, ws, tf, pt};
+  const int CAPW = ProofPlan::CAPW;
+  ProofParts pp;
+  Challenger ch;
+
+  // ---- trace and its commitment (prover.rs:31-38) -----------------------------------------------------------
+  r.sb(ST_TOTAL);
+  int h_err = 0;
+  if (int rc = stage_trace(r, scalars, x, off, pr, &h_err, err)) return rc;
+  if (int rc = commit(r, ws.tvals, ws.tcoef, ws.tlde, pl.W, ws.ttree, ST_TRACE_NTT, ST_TRACE_MERKLE, pp.caps[0], err)) return rc;
+  if (h_err) {
+    err = "trace generation reported device error " + std::to_string(h_err);
+    return h_err;
+  }
+  // ---- transcript: trace cap, CTL challenges, compact (prover.rs:40-54) --------------------------------
+  ch.observe_n(pp.caps[0], CAPW);
+  u64 betas[2], gammas[2];
+  for (int i = 0; i < 2; i++) {
+    betas[i] = ch.challenge();
+    gammas[i] = ch.challenge();
+  }
+  ch.compact(pp.init_state);
+
+  // ---- auxiliary columns + commitment ---------------------------------------------------------------------
+  stage_aux(r, betas, gammas);
+  if (pl.stream)
+    if (int rc = ws.begin_windows(err)) return rc;
+  if (int rc = commit(r, ws.avals, ws.acoef, ws.alde, pl.A, ws.atree, ST_AUX_NTT, ST_AUX_MERKLE, pp.caps[1], err)) return rc;
+  ch.observe_n(pp.caps[1], CAPW);
+  u64 alphas[2] = {ch.challenge(), 0};
+  alphas[1] = ch.challenge();
+
+  // ---- quotient + commitment --------------------------------------------------------------------------------
+  if (int rc = stage_quotient(r, alphas, betas, gammas, pp.caps[2], err)) return rc;
+  ch.observe_n(pp.caps[2], CAPW);
+  gl2 zeta = ch.challenge_ext();
+  {
+    gl2 zp = zeta;
+    for (unsigned i = 0; i < pl.log_n; i++) zp = gl2_mul(zp, zp);
+    if (gl2_eq(zp, gl2_make(1, 0))) {
+      err = "Opening point is in the subgroup.";
+      return BN254S_E_TRANSCRIPT;
+    }
+  }
+  const gl2 zeta_next = gl2_mul_base(zeta, gl_root_of_unity(pl.log_n));
+
+  // ---- openings (StarkOpeningSet::new) ---------------------------------------------------------------------
+  // device -> host copies land in the slot's pinned staging buffer (pageable destinations go through a runtime-internal
+  // staging allocation that costs ~8 ms the first time and an extra copy every time)
+  u64* staging = (u64*)sl.pinned;
+  if (int rc = stage_openings(r, zeta, zeta_next, staging, err)) return rc;
+  pp.h_open = recombine_openings(pl, staging, zeta, zeta_next);
+  const Openings op{pl, pp.h_open};
+  observe_openings(ch, op);
+
+  // ---- FRI (prove_openings) ------------------------------------------------------------------------------------
+  const gl2 fri_alpha = ch.challenge_ext();
+  if (int rc = stage_fri_combine(r, fri_alpha_powers(op, fri_alpha), zeta, zeta_next, fri_alpha, err)) return rc;
+  if (int rc = stage_fri_commit(r, ch, pp.fri, err)) return rc;
+  std::vector<u64> h_final((size_t)2 << pp.fri.lm);
+  CHK(hipMemcpyAsync(h_final.data(), pp.fri.last, h_final.size() * 8, hipMemcpyDeviceToHost, st));
+  CHK(hipStreamSynchronize(st));
+  if (int rc = fri_final_poly(h_final, pp.fri.lm, pp.fri.shift, P.rate_bits, pp.final_poly, err)) return rc;
+  for (auto& cf : pp.final_poly) {
+    ch.observe(cf.c0);
+    ch.observe(cf.c1);
+  }
+  if (int rc = stage_pow(r, ch, pp.pow_witness, err)) return rc;
+  pp.h_q = staging;  // (the opening partials in it were consumed above)
+  if (int rc = stage_queries(r, ch, pp.fri, staging, err)) return rc;
+
+  assemble_proof(pl, pp, pr);
+  for (int i = 0; i < ST_COUNT; i++) hipEventElapsedTime(&pr->stage_ms[i], sl.events[2 * i], sl.events[2 * i + 1]);
   return BN254S_OK;
 }
 
@@ -923,7 +1051,7 @@ int bn254s_prove_batch_begin(bn254s_ctx* c, int kind, const bn254s_params* param
     return BN254S_E_INVALID_ARG;
   *handle = nullptr;
   const size_t n_proofs = (n_total + per_proof - 1) / per_proof;
-  const size_t PW = point_words(kind);
+  const size_t PW = stark_kind(kind).point_words;
   for (size_t i = 0; i < n_proofs; i++) proofs_out[i] = nullptr;
   HIP_TRY(c, hipSetDevice(c->device));
   // proofs in flight (one stream, host thread and workspace each; the streams share GPU_MAX_HW_QUEUES = 16 hardware queues - more
@@ -1061,7 +1189,7 @@ int bn254s_prove_batch_multi(bn254s_ctx** ctxs, size_t n_ctx, int kind, const bn
   for (size_t g = 0; g < n_ctx; g++)
     if (!ctxs[g]) return BN254S_E_INVALID_ARG;
   const size_t n_proofs = (n_total + per_proof - 1) / per_proof;
-  const size_t PW = point_words(kind);
+  const size_t PW = stark_kind(kind).point_words;
   for (size_t i = 0; i < n_proofs; i++) proofs_out[i] = nullptr;
   std::vector<int> rcs(n_ctx, BN254S_OK);
   std::vector<std::thread> th;
@@ -1150,28 +1278,22 @@ int bn254s_generate_trace(bn254s_ctx* c, int kind, const uint64_t* scalars, cons
     return BN254S_E_INVALID_ARG;
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  const int PW = point_words(kind);
-  const StarkShape sh = shape_for(kind);
+  const StarkKind& sk = stark_kind(kind);
+  const int PW = sk.point_words;
+  const StarkShape& sh = sk.shape;
   size_t N = rows_for(n, min_rows_log2);
   const size_t in_words = n * (4 + 2 * (size_t)PW);
   u64* d_in = c->words("gt.in", in_words);
   u64* d_trace = c->words("gt.trace", (size_t)sh.W * N);
-  const size_t trace_scr = kind == KIND_G1 ? g1_trace_scratch_words(n) : kind == KIND_G2 ? g2_trace_scratch_words(n) : fq_trace_scratch_words(n);
-  u64* d_scr = c->words("gt.scratch", trace_scr);
+  u64* d_scr = c->words("gt.scratch", sk.trace_scratch_words(n));
   u64* d_out = c->words("gt.out", n * PW + 8);
   if (!d_in || !d_trace || !d_scr || !d_out) return BN254S_E_OOM;
   int* d_err = (int*)(d_out + n * PW);
-  u64 *d_sc = d_in, *d_x = d_in + 4 * n, *d_off = d_x + (size_t)PW * n;
   HIP_TRY(c, hipMemsetAsync(d_err, 0, 4, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(d_sc, scalars, n * 32, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(d_x, x, n * (size_t)PW * 8, hipMemcpyHostToDevice, c->stream));
-  if (kind != KIND_FQ) HIP_TRY(c, hipMemcpyAsync(d_off, off, n * (size_t)PW * 8, hipMemcpyHostToDevice, c->stream));
-  int trc = kind == KIND_G1   ? g1_generate_trace_device(d_sc, d_x, d_off, n, d_trace, N, d_scr, d_out, d_err, c->stream)
-            : kind == KIND_G2 ? g2_generate_trace_device(d_sc, d_x, d_off, n, d_trace, N, d_scr, d_out, d_err, c->stream)
-                              : fq_generate_trace_device(d_sc, d_x, n, d_trace, N, d_scr, d_out, d_err, c->stream);
-  if (trc) {
-    c->set_err("trace generation launch failed");
-    return BN254S_E_HIP;
+  std::string err;
+  if (int rc = upload_and_generate(sk, scalars, x, off, n, d_in, d_trace, N, d_scr, d_out, d_err, c->stream, true, err)) {
+    c->set_err(err);
+    return rc;
   }
   int h_err = 0;
   HIP_TRY(c, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, c->stream));

@@ -31,7 +31,7 @@ struct View {  // offsets into the word layout
 };
 
 bool make_view(int kind, const bn254s_params& P, int degree_bits, View& v) {
-  StarkShape sh = shape_for(kind);
+  const StarkShape& sh = stark_kind(kind).shape;
   v.W = sh.W;
   v.A = sh.n_aux();
   v.log_n = degree_bits;
@@ -149,7 +149,7 @@ int vanishing_on_gpu(bn254s_ctx* c, int kind, const StarkShape& sh, const u64* w
   }
   std::vector<u64> hW, hmzt;
   const int* mz_e0 = nullptr;
-  int nblk = kind == KIND_G1 ? g1_quotient_mz_blocks(&mz_e0) : kind == KIND_G2 ? g2_quotient_mz_blocks(&mz_e0) : fq_quotient_mz_blocks(&mz_e0);
+  int nblk = stark_kind(kind).mz_blocks(&mz_e0);
   quotient_host_tables(K, alphas, mz_e0, nblk, hW, hmzt);
 
   u64* d_tl = c->words("vf_tl", tl.size());
@@ -178,9 +178,7 @@ int vanishing_on_gpu(bn254s_ctx* c, int kind, const StarkShape& sh, const u64* w
   quotient_fill_args(QA, sh, d_tl, d_al, d_W, d_mzt, pt, betas, gammas, VLOG, d_out, d_part);
   QA.zh_inv[0] = QA.zh_inv[1] = 1;  // no division by Z_H
   QA.w_inv = 0;                     // transition selector = the x table itself
-  if (kind == KIND_G1) g1_quotient_launch(QA, sh, st);
-  else if (kind == KIND_G2) g2_quotient_launch(QA, sh, st);
-  else fq_quotient_launch(QA, sh, st);
+  stark_kind(kind).quotient_launch(QA, sh, st);
   std::vector<u64> ho(4 * N);
   VCHK(hipMemcpyAsync(ho.data(), d_out, ho.size() * 8, hipMemcpyDeviceToHost, st));
   VCHK(hipStreamSynchronize(st));
@@ -223,7 +221,7 @@ void limbs16(const u64* words4, u64* out) {
 }
 void ctl_rows(int kind, const u64* scalars, const u64* x, const u64* off, const u64* outputs, size_t k, std::vector<u64>& in,
               std::vector<u64>& out) {
-  const int PW = point_words(kind), PL = 4 * PW;  // 16-bit limbs per point
+  const int PW = stark_kind(kind).point_words, PL = 4 * PW;  // 16-bit limbs per point
   in.assign((kind == KIND_FQ ? PL : 2 * PL) + 17, 0);
   out.assign(PL + 1, 0);
   size_t m = 0;
@@ -245,7 +243,7 @@ int verify_impl(bn254s_ctx* c, int kind, const bn254s_params& P, int degree_bits
     err = "bad proof shape";
     return BN254S_E_VERIFY;
   }
-  const StarkShape sh = shape_for(kind);
+  const StarkShape& sh = stark_kind(kind).shape;
   const size_t N = (size_t)1 << degree_bits, M2 = (size_t)1 << v.log_m2;
   const int W = v.W, A = v.A, NQ = v.NQ;
   for (size_t i = 0; i < n_words; i++)

@@ -111,6 +111,9 @@ def load_library():
     lib.bn254s_selftest_fq.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
     if hasattr(lib, "bn254s_selftest_logup"):   # (an older build loaded through BN254S_LIB for an A/B run has no such entry)
         lib.bn254s_selftest_logup.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    if hasattr(lib, "bn254s_selftest_proof_plan"):   # (likewise)
+        lib.bn254s_selftest_proof_plan.argtypes = [C.c_int, C.c_size_t, C.POINTER(Params), C.c_uint64, C.c_int, C.c_int, C.c_int,
+                                                   C.c_int, vp, C.c_char_p, C.c_size_t]
     lib.bn254s_bench_copy.argtypes = [vp, C.c_size_t, C.c_int]
     lib.bn254s_bench_leafhash.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]
     lib.bn254s_g1_generate_trace.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]
@@ -729,6 +732,35 @@ def verify_host(kind, words, degree_bits, scalars, x, offset, outputs, params: O
         raise VerifyError(buf.value.decode())
     if rc != 0:
         raise RuntimeError(f"bn254s_verify_host failed with {rc}: {buf.value.decode()}")
+
+
+PLAN_BUFFERS = ("in", "tvals", "tcoef", "hist", "tmp", "ldechunk", "sponge", "comb", "tlde", "trees", "avals", "acoef", "alde",
+                "scratch", "quot", "tabs", "open", "fri", "fritrees", "qout", "win")
+_PLAN_HEAD = ("kind", "n", "W", "A", "K", "point_words", "N", "log_n", "log_s", "log_r", "R", "NH", "NSPL", "stream", "lowmem",
+              "log_bk", "BK", "WROWS", "L")
+_PLAN_TAIL = ("wpq", "tree_words", "fri_words", "fri_tree_words", "in_words")
+
+
+def proof_plan(kind, n, dev_total_bytes, force_split=False, force_lowmem=False, force_stream=False, stream_win_log=None,
+               params: Optional[Params] = None) -> dict:
+    """bn254s_selftest_proof_plan: what the prover decides before it touches memory, without a context or a GPU.  The scalar fields
+    by name, "arities" (a list of L), "words" (a dict over PLAN_BUFFERS; 0 = no buffer of that name) and "pinned_bytes".  The
+    keyword arguments stand for the BN254S_FORCE_* / BN254S_STREAM_WIN_LOG overrides.  Raises RuntimeError(code and reason)."""
+    lib = load_library()
+    params = params or default_params()
+    out = np.zeros(54, np.uint64)
+    buf = C.create_string_buffer(256)
+    rc = lib.bn254s_selftest_proof_plan(kind, n, C.byref(params), dev_total_bytes, int(force_split), int(force_lowmem), int(force_stream),
+                                        -1 if stream_win_log is None else stream_win_log, _ptr(out), buf, 256)
+    if rc != 0:
+        raise RuntimeError(f"bn254s_selftest_proof_plan failed with {rc}: {buf.value.decode()}")
+    v = [int(w) for w in out]
+    plan = dict(zip(_PLAN_HEAD, v[:19]))
+    plan["arities"] = v[19:19 + plan["L"]]
+    plan.update(zip(_PLAN_TAIL, v[27:32]))
+    plan["words"] = dict(zip(PLAN_BUFFERS, v[32:53]))
+    plan["pinned_bytes"] = v[53]
+    return plan
 
 
 def _proof_slices(tag, proofs, n, per_proof, w):

@@ -83,6 +83,30 @@ def test_streaming_workspace_matches_oracle(gpu_ctx, oracle, monkeypatch, kind, 
     assert np.array_equal(pr2.words, ref)
 
 
+def test_workspaces_take_turns_on_one_slot(monkeypatch):
+    """A slot carries its buffers from one proof to the next, and every workspace drops or reuses what another one left: plain,
+    streaming, compact, streaming, plain in one context, single-proof calls (all on slot 0), Fq-exp at 2^17 rows - the smallest
+    height the three layouts accept.  The five proofs are the same words."""
+    import plonky2_bn254_amd as pk
+    s, x = synth.fq_inputs(130, seed=38)
+    modes = {"plain": {}, "stream": {"BN254S_FORCE_STREAM": "1", "BN254S_STREAM_WIN_LOG": "16"}, "compact": {"BN254S_FORCE_LOWMEM": "1"}}
+    ctx = pk.Context(0)
+    got = []
+    for mode in ("plain", "stream", "compact", "stream", "plain"):
+        with monkeypatch.context() as m:
+            for k, v in modes[mode].items():
+                m.setenv(k, v)
+            pr = ctx.prove_fq_exp(s, x)
+        assert pr.degree_bits == 17
+        got.append((mode, pr.words.copy(), pr.outputs.copy()))
+    ctx.close()
+    for mode, words, outs in got[1:]:
+        assert np.array_equal(words, got[0][1]), mode
+        assert np.array_equal(outs, got[0][2]), mode
+    for k in (0, 77, 129):
+        assert synth.words_to_int(got[0][2].reshape(-1, 4)[k]) == pow(synth.words_to_int(x[k]), synth.words_to_int(s[k]), synth.P)
+
+
 def test_g1_tall_proof_2pow17(gpu_ctx, oracle):
     s, x, o = synth.g1_inputs(150, seed=32)         # 76800 rows -> N = 2^17
     ref, ref_out, _, degree_bits = oracle_lib.prove(oracle, 0, s, x, o)
