@@ -518,6 +518,40 @@ int bn254s_selftest_fq(bn254s_ctx* ctx, int group, const uint64_t* in, size_t n,
  * BN254S_E_INTERNAL: a range-checked or table value above 65535 (found on the device; `out` is not meaningful then). */
 int bn254s_selftest_logup(bn254s_ctx* ctx, const uint64_t* trace, size_t rows, int ncols, int rc_begin, int n_rc, int table_col,
                           int freq_col, const uint64_t betas[2], uint64_t* out);
+/* Debug: the openings / FRI kernels (csrc/fri.hip) and the un-reduced accumulators of csrc/quotient_common.h on caller data,
+ * through the launchers the provers run (csrc/fri_selftest.hip).  All buffers are host memory; every field word must be canonical
+ * (below p = 2^64 - 2^32 + 1) and an extension element is two words (c0, c1).  BN254S_E_INVALID_ARG: a NULL argument, a size
+ * outside what is stated below, a word of p or more; nothing is launched then.
+ *
+ * bn254s_selftest_acc: values[rows][T], weights[T] -> out[rows][2] = sum_t values[r][t] weights[t] mod p by Acc (acc_mad / acc_red)
+ *   and by Acc3 (acc3_mad on the 22-bit limbs / acc3_red), one accumulator of each kind and one GPU lane per row.
+ *   1 <= T <= 2^17 (the documented capacity of Acc3), 1 <= rows <= 4096.
+ * bn254s_selftest_openings: coeffs[npolys][N], N = 2^(16 + log_r) in the transposed layout of the provers (coefficient
+ *   k1 + R k2 at position k1 2^16 + k2, R = 2^log_r), 0 <= log_r <= 2, 1 <= npolys <= 64 -> out[npolys][R][5] = the partial
+ *   evaluations {S_k1(zeta^R).c0, .c1, S_k1(zeta_next^R).c0, .c1, sum of the block's coefficients} as the device writes them
+ *   (fri_opening_tables, fri_openings); P(z) = sum_k1 z^k1 S_k1(z^R).
+ * bn254s_selftest_fri_combine, for a synthetic shape of trace width W (1 .. 4096), n_rc range-checked columns (1 .. W) and n_ctl
+ *   cross-table lookups (0 or 2), i.e. A = 2 (ceil(n_rc / 2) + 1) + 2 n_ctl auxiliary columns of which the last 2 n_ctl are the Z's:
+ *   mode 0 (fri_combine_coeffs): cols[W + A + 4][n] = trace | auxiliary | quotient columns, 1 <= n <= 2^16 (any n: stride and
+ *     bound), aux_in = W + A + 4 weights as extension elements, points unused (may be NULL) -> out = comb[6][n]: rows 0,1 =
+ *     sum over trace and auxiliary columns, rows 2,3 = sum over the quotient columns, rows 4,5 = sum over the Z columns with the
+ *     FIRST 2 n_ctl weights (components c0 / c1 each).
+ *   mode 1 (fri_combine_final): cols = cl[6][n], 1 <= n <= 2^20, aux_in = xs[n], points[12] = zeta, zeta_next, r0, r1, r2, alpha
+ *     -> out[n][2] = alpha^(W + A + 2 n_ctl) (f0 - r0) / (x - zeta) + alpha^(2 n_ctl) (f1 - r1) / (x - zeta_next) + (f2 - r2) / (x - 1)
+ *     with f1 = (cl0, cl1), f0 = f1 + (cl2, cl3), f2 = (cl4, cl5) and 1 / 0 := 0.
+ * bn254s_selftest_fri_fold: in[2^log_m][2] extension values in bit-reversed order on shift <w_(2^log_m)>, 5 <= log_m <= 20, shift
+ *   != 0 -> out[2^(log_m - 4)][2], the arity-16 fold at beta (fri_fold with inv16 = 1 / 16).
+ * bn254s_selftest_fri_rows: lde[ncols][2^(log_n + 1)] (leaf order: coset h at h 2^log_n + bitrev(k)), 1 <= log_n <= 20, 1 <= ncols <=
+ *   4096 -> window[ncols][rows] = rows k0 .. k0 + rows - 1 (mod 2^log_n) of coset h in {0, 1} (fri_extract_window; k0 < 2^log_n,
+ *   1 <= rows <= 2^20) and gathered[ncols][nq] = lde[c][indices[q]] (fri_gather_rows; 1 <= nq <= 4096, indices < 2^(log_n + 1)). */
+int bn254s_selftest_acc(bn254s_ctx* ctx, const uint64_t* values, const uint64_t* weights, size_t T, size_t rows, uint64_t* out);
+int bn254s_selftest_openings(bn254s_ctx* ctx, const uint64_t* coeffs, int npolys, int log_r, const uint64_t zeta[2],
+                             const uint64_t zeta_next[2], uint64_t* out);
+int bn254s_selftest_fri_combine(bn254s_ctx* ctx, int mode, int W, int n_rc, int n_ctl, size_t n, const uint64_t* cols,
+                                const uint64_t* aux_in, const uint64_t* points, uint64_t* out);
+int bn254s_selftest_fri_fold(bn254s_ctx* ctx, const uint64_t* in, int log_m, uint64_t shift, const uint64_t beta[2], uint64_t* out);
+int bn254s_selftest_fri_rows(bn254s_ctx* ctx, const uint64_t* lde, int ncols, int log_n, int h, size_t k0, size_t rows,
+                             const uint32_t* indices, int nq, uint64_t* window, uint64_t* gathered);
 /* Debug: the plan of one proof - what the prover decides before it touches memory, the workspace layout above all - for a proof of n
  * instances of `kind` on a device with dev_total_bytes of memory (0 = unknown: the streaming workspace is then never chosen on
  * account of the size).  Host arithmetic only: no context, no GPU.  force_split / force_lowmem / force_stream / stream_win_log stand

@@ -17,6 +17,13 @@ void fri_openings(const u64* d_coeffs, size_t N, unsigned log_r, int npolys, con
 // d_out[2N][2]: sum_b alpha^(k_b) (F_b(x) - F_b(z_b)) / (x - z_b) on the LDE domain, bit-reversed order, in two steps from the
 // coefficient vectors (no resident LDE needed): comb[6][N] = the three alpha-weighted sums (f1, quotient part of f0, f2; c0 / c1
 // each) formed on the coefficients; after the ordinary LDE of those six columns fri_combine_final applies the point-wise part.
+// One record of the weight table d_apow that fri_combine_coeffs reads (8 u32 per polynomial, in the order trace | aux | quotient):
+// the two components of the weight cut in 22-bit limbs (quotient_common.h W3) = (c0: w0 w1 w2 0, c1: w0 w1 w2 0).
+inline void fri_weight_record(u32* e /* 8 u32 */, gl2 w) {
+  const W3 s0 = w3_split(w.c0), s1 = w3_split(w.c1);
+  e[0] = s0.w0; e[1] = s0.w1; e[2] = s0.w2; e[3] = 0;
+  e[4] = s1.w0; e[5] = s1.w1; e[6] = s1.w2; e[7] = 0;
+}
 void fri_combine_coeffs(const StarkShape& sh, const u64* d_tcoef, const u64* d_acoef, const u64* d_qcoef, const u64* d_apow, size_t N,
                         u64* d_comb, hipStream_t st);
 void fri_combine_final(const StarkShape& sh, const u64* d_comb_lde, const u64* d_xs, gl2 zeta, gl2 zeta_next, gl2 r0, gl2 r1, gl2 r2,

@@ -679,10 +679,7 @@ static FriAlphaPowers fri_alpha_powers(const Openings& op, gl2 fri_alpha) {
   gl2 ap = gl2_make(1, 0);
   f.r0 = f.r1 = f.r2 = gl2_make(0, 0);
   for (int p = 0; p < W + A + NQ; p++) {
-    const W3 s0 = w3_split(ap.c0), s1 = w3_split(ap.c1);
-    u32* e = &f.apow[8 * (size_t)p];
-    e[0] = s0.w0; e[1] = s0.w1; e[2] = s0.w2;
-    e[4] = s1.w0; e[5] = s1.w1; e[6] = s1.w2;
+    fri_weight_record(&f.apow[8 * (size_t)p], ap);
     f.r0 = gl2_add(f.r0, gl2_mul(ap, gl2_make(op(p, 0), op(p, 1))));
     if (p < W + A) f.r1 = gl2_add(f.r1, gl2_mul(ap, gl2_make(op(p, 2), op(p, 3))));
     if (p < n_ctlz) f.r2 = gl2_add(f.r2, gl2_mul_base(ap, op.ctl_z_first(p)));

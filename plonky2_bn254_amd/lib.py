@@ -111,6 +111,12 @@ def load_library():
     lib.bn254s_selftest_fq.argtypes = [vp, C.c_int, vp, C.c_size_t, vp]
     if hasattr(lib, "bn254s_selftest_logup"):   # (an older build loaded through BN254S_LIB for an A/B run has no such entry)
         lib.bn254s_selftest_logup.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    if hasattr(lib, "bn254s_selftest_fri_fold"):   # (likewise; the five entry points of csrc/fri_selftest.hip come together)
+        lib.bn254s_selftest_acc.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+        lib.bn254s_selftest_openings.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
+        lib.bn254s_selftest_fri_combine.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp]
+        lib.bn254s_selftest_fri_fold.argtypes = [vp, vp, C.c_int, C.c_uint64, vp, vp]
+        lib.bn254s_selftest_fri_rows.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, vp, C.c_int, vp, vp]
     if hasattr(lib, "bn254s_selftest_proof_plan"):   # (likewise)
         lib.bn254s_selftest_proof_plan.argtypes = [C.c_int, C.c_size_t, C.POINTER(Params), C.c_uint64, C.c_int, C.c_int, C.c_int,
                                                    C.c_int, vp, C.c_char_p, C.c_size_t]
@@ -689,6 +695,84 @@ class Context:
         self._check(self._lib.bn254s_selftest_logup(self._h, _ptr(trace), rows, ncols, rc_begin, n_rc, table_col, freq_col, _ptr(b),
                                                     _ptr(out)), "bn254s_selftest_logup")
         return out
+
+    # The openings / FRI kernels and the un-reduced accumulators on caller data (csrc/fri_selftest.hip; include/bn254_stark.h has
+    # the layouts).  Extension elements are (c0, c1) pairs of Python integers or two-word arrays.
+    def selftest_acc(self, values: np.ndarray, weights: np.ndarray) -> np.ndarray:
+        """Debug: values[rows][T], weights[T] -> out[rows][2] = sum_t values[r][t] weights[t] mod p by Acc and by Acc3, one
+        accumulator per row (bn254s_selftest_acc)."""
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+        weights = np.ascontiguousarray(weights, dtype=np.uint64)
+        rows, t = values.shape
+        assert weights.shape == (t,)
+        out = np.zeros((rows, 2), np.uint64)
+        self._check(self._lib.bn254s_selftest_acc(self._h, _ptr(values), _ptr(weights), t, rows, _ptr(out)), "bn254s_selftest_acc")
+        return out
+
+    def selftest_openings(self, coeffs: np.ndarray, log_r: int, zeta, zeta_next) -> np.ndarray:
+        """Debug: coeffs[npolys][2^(16 + log_r)] in the provers' transposed layout -> the partial evaluations
+        out[npolys][2^log_r][5] of fri_openings at (zeta, zeta_next) (bn254s_selftest_openings)."""
+        coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+        npolys, n = coeffs.shape
+        assert n == 1 << (16 + log_r), (n, log_r)
+        z0 = np.array([int(v) for v in zeta], dtype=np.uint64)
+        z1 = np.array([int(v) for v in zeta_next], dtype=np.uint64)
+        out = np.zeros((npolys, 1 << log_r, 5), np.uint64)
+        self._check(self._lib.bn254s_selftest_openings(self._h, _ptr(coeffs), npolys, log_r, _ptr(z0), _ptr(z1), _ptr(out)),
+                    "bn254s_selftest_openings")
+        return out
+
+    def selftest_fri_combine_coeffs(self, cols: np.ndarray, w: int, n_rc: int, n_ctl: int, weights: np.ndarray) -> np.ndarray:
+        """Debug: cols[W + A + 4][n] (trace | auxiliary | quotient), weights[W + A + 4][2] -> comb[6][n] of fri_combine_coeffs
+        (bn254s_selftest_fri_combine, mode 0)."""
+        cols = np.ascontiguousarray(cols, dtype=np.uint64)
+        weights = np.ascontiguousarray(weights, dtype=np.uint64)
+        n_polys, n = cols.shape
+        assert n_polys == w + 2 * ((n_rc + 1) // 2 + 1) + 2 * n_ctl + 4 and weights.shape == (n_polys, 2), (cols.shape, weights.shape)
+        out = np.zeros((6, n), np.uint64)
+        self._check(self._lib.bn254s_selftest_fri_combine(self._h, 0, w, n_rc, n_ctl, n, _ptr(cols), _ptr(weights), None, _ptr(out)),
+                    "bn254s_selftest_fri_combine")
+        return out
+
+    def selftest_fri_combine_final(self, cl: np.ndarray, xs: np.ndarray, w: int, n_rc: int, n_ctl: int, zeta, zeta_next, r0, r1, r2,
+                                   alpha) -> np.ndarray:
+        """Debug: cl[6][m], xs[m] -> out[m][2], the point-wise part of the batched quotient by fri_combine_final
+        (bn254s_selftest_fri_combine, mode 1)."""
+        cl = np.ascontiguousarray(cl, dtype=np.uint64)
+        xs = np.ascontiguousarray(xs, dtype=np.uint64)
+        m = xs.shape[0]
+        assert cl.shape == (6, m)
+        pts = np.array([int(v) for e in (zeta, zeta_next, r0, r1, r2, alpha) for v in e], dtype=np.uint64)
+        out = np.zeros((m, 2), np.uint64)
+        self._check(self._lib.bn254s_selftest_fri_combine(self._h, 1, w, n_rc, n_ctl, m, _ptr(cl), _ptr(xs), _ptr(pts), _ptr(out)),
+                    "bn254s_selftest_fri_combine")
+        return out
+
+    def selftest_fri_fold(self, vals: np.ndarray, shift: int, beta) -> np.ndarray:
+        """Debug: vals[2^log_m][2] (bit-reversed order on shift <w>) -> the arity-16 fold at beta, out[2^(log_m - 4)][2]
+        (bn254s_selftest_fri_fold)."""
+        vals = np.ascontiguousarray(vals, dtype=np.uint64)
+        m = vals.shape[0]
+        assert vals.shape == (m, 2) and m >= 16 and m & (m - 1) == 0
+        b = np.array([int(beta[0]), int(beta[1])], dtype=np.uint64)
+        out = np.zeros((m >> 4, 2), np.uint64)
+        self._check(self._lib.bn254s_selftest_fri_fold(self._h, _ptr(vals), m.bit_length() - 1, int(shift), _ptr(b), _ptr(out)),
+                    "bn254s_selftest_fri_fold")
+        return out
+
+    def selftest_fri_rows(self, lde: np.ndarray, h: int, k0: int, rows: int, indices):
+        """Debug: lde[ncols][2 N] in leaf order -> (window[ncols][rows] of coset h from row k0 on, wrapping at N;
+        gathered[ncols][nq] = lde[:, indices]) by fri_extract_window and fri_gather_rows (bn254s_selftest_fri_rows)."""
+        lde = np.ascontiguousarray(lde, dtype=np.uint64)
+        ncols, m2 = lde.shape
+        assert m2 >= 4 and m2 & (m2 - 1) == 0
+        idx = np.ascontiguousarray(indices, dtype=np.uint32)
+        win = np.zeros((ncols, rows), np.uint64)
+        gat = np.zeros((ncols, idx.shape[0]), np.uint64)
+        self._check(self._lib.bn254s_selftest_fri_rows(self._h, _ptr(lde), ncols, m2.bit_length() - 2, h, k0, rows,
+                                                       idx.ctypes.data_as(C.c_void_p), idx.shape[0], _ptr(win), _ptr(gat)),
+                    "bn254s_selftest_fri_rows")
+        return win, gat
 
     def poseidon_permute(self, states: np.ndarray) -> np.ndarray:
         st = np.ascontiguousarray(states, dtype=np.uint64).copy()
