@@ -35,7 +35,8 @@
  * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x /
  * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor / bn254s_job_outputs / bn254s_map_to_g1) queues
  * behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its own, so it can never share
- * device state with a proof of the open batch; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
+ * device state with a proof of the open batch; bn254s_verify_batch uses the context's own stream and device memory that it allocates
+ * and frees itself, so it is independent of open batches too; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
  * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch,
  * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch, bn254s_job_outputs_batch,
  * bn254s_hash_to_fq_batch, bn254s_map_to_g1_batch, bn254s_hash_to_g1_batch and the front-end halves of bn254s_g1_recover_from_x,
@@ -199,6 +200,28 @@ int bn254s_verify(bn254s_ctx* ctx, int kind, const bn254s_params* params, uint32
 int bn254s_verify_host(int kind, const bn254s_params* params, uint32_t degree_bits, const uint64_t* words, size_t n_words,
                        const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, const uint64_t* outputs, size_t n,
                        char* err_buf, size_t err_cap);
+
+/* The same verifier for n_proofs proofs of ONE kind, parameter set and height (callers group their proofs): words[i] points to
+ * the n_words words of proof i; the job arrays (scalars, x, offset, outputs) hold the jobs of all proofs one after the other in
+ * proof order, n_jobs[i] of them for proof i.  Same argument rules as bn254s_verify (num_challenges = 2, rate_bits = 1,
+ * degree_bits 7..30).
+ *
+ * Per proof, in this order: the front (shape, transcript, the AIR at zeta on the host as in bn254s_verify_host, proof of work);
+ * the FRI query rounds; the cross-table-lookup check.  The fronts and the CTL checks of different proofs run on min(16, n_proofs)
+ * host threads.  With a context the query rounds of every proof that passed its front run on the device (csrc/verify_batch.hip:
+ * Merkle paths one lane per (proof, query, tree), FRI arithmetic one lane per (proof, query); proof words go up in chunks of at
+ * most 256 MiB, device memory is allocated and freed by the call, all work goes on the context's stream, and the call may run
+ * while a batch of bn254s_prove_batch_begin is open).  ctx = NULL: the query rounds run on the host threads too, no GPU.
+ *
+ * status[i] (and err + i * err_stride, NUL-terminated, at most err_stride bytes; err may be NULL) are what bn254s_verify_host
+ * returns for proof i alone: BN254S_OK and "", or BN254S_E_VERIFY and the reference verifier's text.
+ * Returns BN254S_OK: every proof accepted.  BN254S_E_VERIFY: at least one proof rejected, status and err filled for every proof
+ * and bn254s_last_error reads "proof i: text" for the lowest rejected i.  Any other code: the call itself failed
+ * (BN254S_E_INVALID_ARG: a NULL array or words[i], n_proofs = 0, some n_jobs[i] = 0, err given with err_stride = 0, a kind outside
+ * 0..2, a params->struct_size mismatch; BN254S_E_HIP / BN254S_E_OOM from the device: status holds that code for every proof). */
+int bn254s_verify_batch(bn254s_ctx* ctx, int kind, const bn254s_params* params, uint32_t degree_bits, const uint64_t* const* words,
+                        size_t n_words, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, const uint64_t* outputs,
+                        const size_t* n_jobs, size_t n_proofs, int32_t* status, char* err, size_t err_stride);
 
 /* The extra looking values of the two cross-table lookups (reference g1_generate_ctl_values, scalar_mul_ctl.rs:57-80; G2 twin;
  * fq_generate_ctl_values, exp_ctl.rs:54-75), i.e. what run_once hands to set_ctl_values_target (stark_proof.rs:174-178):
@@ -552,6 +575,29 @@ int bn254s_selftest_fri_combine(bn254s_ctx* ctx, int mode, int W, int n_rc, int 
 int bn254s_selftest_fri_fold(bn254s_ctx* ctx, const uint64_t* in, int log_m, uint64_t shift, const uint64_t beta[2], uint64_t* out);
 int bn254s_selftest_fri_rows(bn254s_ctx* ctx, const uint64_t* lde, int ncols, int log_n, int h, size_t k0, size_t rows,
                              const uint32_t* indices, int nq, uint64_t* window, uint64_t* gathered);
+/* Debug: the parts of bn254s_verify_batch on caller data (csrc/verify_batch.hip, csrc/verify_query.h).
+ * The FRONT RECORD of a proof is BN254S_VERIFY_RECORD_HEAD + num_queries words: fri_alpha (2 words: c0, c1), reduced[3] (6),
+ * alpha_len[3] (6), zeta (2), g zeta (2), fri_betas[8] (16, zero past the last layer), then the query indices.
+ * The CODE of a query is the first failing check in the verifier's order (L = FRI layers): 0 pass; 1, 2, 3 Merkle path of the
+ * trace / auxiliary / quotient tree; 4 + 2l consistency at layer l; 5 + 2l Merkle path of layer l; 4 + 2L final polynomial.
+ * bn254s_selftest_verify_front: host only.  Runs the front of one proof, writes its record (record_cap words available; too few:
+ *   BN254S_E_INVALID_ARG) and returns the front's status (BN254S_OK, BN254S_E_VERIFY, ...); the record is complete only on BN254S_OK.
+ * bn254s_selftest_query_round: the query rounds of n_proofs proofs on the caller's records (records[n_proofs][record words]) ->
+ *   codes_out[n_proofs][num_queries], every code and not only the first.  ctx = NULL: on the host.  chunk_proofs: proofs per upload
+ *   (0 = by size, 256 MiB).  BN254S_E_INVALID_ARG: a NULL argument, n_words that is not the size of such a proof, a record word of
+ *   p or more, a query index of 2^(degree_bits + rate_bits) or more; nothing is launched then.
+ * bn254s_selftest_query_text: the reference verifier's error text of a code for a proof of n_layers FRI layers ("" for 0; NULL for
+ *   a code or a layer count that does not exist): the text bn254s_verify_batch reports for a proof whose first failing query has it.
+ * bn254s_selftest_verify_batch_ms: the times of the context's latest bn254s_verify_batch in ms: front (wall), upload, k_vb_merkle,
+ *   k_vb_fri (device events), CTL (wall). */
+#define BN254S_VERIFY_RECORD_HEAD 34
+int bn254s_selftest_verify_front(int kind, const bn254s_params* params, uint32_t degree_bits, const uint64_t* words, size_t n_words,
+                                 uint64_t* record_out, size_t record_cap);
+int bn254s_selftest_query_round(bn254s_ctx* ctx, int kind, const bn254s_params* params, uint32_t degree_bits,
+                                const uint64_t* const* words, size_t n_words, const uint64_t* records, size_t n_proofs,
+                                size_t chunk_proofs, int32_t* codes_out);
+const char* bn254s_selftest_query_text(int n_layers, int code);
+int bn254s_selftest_verify_batch_ms(bn254s_ctx* ctx, float ms_out[5]);
 /* Debug: the plan of one proof - what the prover decides before it touches memory, the workspace layout above all - for a proof of n
  * instances of `kind` on a device with dev_total_bytes of memory (0 = unknown: the streaming workspace is then never chosen on
  * account of the size).  Host arithmetic only: no context, no GPU.  force_split / force_lowmem / force_stream / stream_win_log stand

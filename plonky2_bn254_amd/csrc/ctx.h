@@ -262,6 +262,7 @@ struct bn254s_ctx : BufPool {
   // vector never reallocates (capacity reserved in the constructor, BN254S_SLOTS is clamped to MAX_SLOTS) and grows under slots_mu.
   static constexpr size_t MAX_SLOTS = 64;
   std::mutex slots_mu, err_mu;
+  float vb_ms[5] = {0, 0, 0, 0, 0};  // the latest bn254s_verify_batch: front | upload | k_vb_merkle | k_vb_fri | CTL (under err_mu)
   bn254s_ctx() { slots.reserve(MAX_SLOTS); }
   void set_err(const std::string& e) {
     std::lock_guard<std::mutex> lk(err_mu);

@@ -13,6 +13,9 @@
 // the degree bound), once per selector class (plain / transition / first row / last row, chosen through custom point
 // tables), the cubic is interpolated and X^2 = 7 substituted.  Prover and verifier therefore share one statement of the
 // AIR; the independent restatement lives in oracle/ and is what the tests compare against.
+//
+// The verifier is cut in three parts - verify_front, the query rounds (verify_query.h: host/device functions, one query at a
+// time), verify_ctl - which verify_impl runs in that order for one proof and bn254s_verify_batch (verify_batch.hip) for many.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -21,85 +24,12 @@
 #include "quotient.h"
 #include "transcript.h"
 #include "verify_air_host.h"
+#include "verify_query.h"
 
 namespace {
 
-struct View {  // offsets into the word layout
-  int W, A, NQ = 4, NCTLZ = 4, L, log_n, log_m2, cap_h, P;
-  std::vector<int> layer_path;
-  size_t caps, local, next, aux, aux_next, ctlz, quot, fri_caps, queries, wpq, final_poly, final_len, pow, init, total;
-};
-
-bool make_view(int kind, const bn254s_params& P, int degree_bits, View& v) {
-  const StarkShape& sh = stark_kind(kind).shape;
-  v.W = sh.W;
-  v.A = sh.n_aux();
-  v.log_n = degree_bits;
-  v.log_m2 = degree_bits + P.rate_bits;
-  v.cap_h = P.cap_height;
-  v.P = v.log_m2 - v.cap_h;
-  std::vector<int> ar = fri_arities(P, degree_bits);
-  v.L = (int)ar.size();
-  size_t o = 0;
-  v.caps = o; o += 3 * 64;
-  v.local = o; o += 2 * (size_t)v.W;
-  v.next = o; o += 2 * (size_t)v.W;
-  v.aux = o; o += 2 * (size_t)v.A;
-  v.aux_next = o; o += 2 * (size_t)v.A;
-  v.ctlz = o; o += v.NCTLZ;
-  v.quot = o; o += 2 * (size_t)v.NQ;
-  v.fri_caps = o; o += (size_t)v.L * 64;
-  v.queries = o;
-  v.wpq = (size_t)(v.W + v.A + v.NQ) + 3 * (size_t)v.P * 4;
-  int bits = v.log_m2, sum = 0;
-  v.layer_path.clear();
-  for (int l = 0; l < v.L; l++) {
-    bits -= ar[l];
-    sum += ar[l];
-    int pl = bits - v.cap_h;
-    if (pl < 0) return false;
-    v.layer_path.push_back(pl);
-    v.wpq += 2 * ((size_t)1 << ar[l]) + (size_t)pl * 4;
-  }
-  o += v.wpq * P.num_queries;
-  v.final_len = (size_t)1 << (degree_bits - sum);
-  v.final_poly = o; o += 2 * v.final_len;
-  v.pow = o; o += 1;
-  v.init = o; o += 12;
-  v.total = o;
-  return true;
-}
-
-// ---- host hashing (PoseidonHash::hash_or_noop / two_to_one, MerkleProof verification) ------------------------------
-void hash_or_noop(const u64* in, size_t n, u64 out[4]) {
-  if (n <= 4) {
-    for (size_t i = 0; i < 4; i++) out[i] = i < n ? in[i] : 0;
-    return;
-  }
-  u64 st[12] = {0};
-  for (size_t i = 0; i < n; i += 8) {
-    size_t m = n - i < 8 ? n - i : 8;
-    for (size_t k = 0; k < m; k++) st[k] = in[i + k];
-    poseidon_permute(st);
-  }
-  memcpy(out, st, 32);
-}
-bool merkle_ok(const u64* leaf, size_t leaf_len, size_t index, const u64* cap, const u64* path, int path_len) {
-  u64 cur[4];
-  hash_or_noop(leaf, leaf_len, cur);
-  for (int i = 0; i < path_len; i++) {
-    u64 nxt[4];
-    if (index & 1) poseidon_two_to_one(path + 4 * i, cur, nxt);
-    else poseidon_two_to_one(cur, path + 4 * i, nxt);
-    memcpy(cur, nxt, 32);
-    index >>= 1;
-  }
-  return memcmp(cur, cap + 4 * index, 32) == 0;
-}
-
 inline gl2 ext(const u64* w) { return gl2_make(w[0], w[1]); }
 inline gl2 base(u64 x) { return gl2_make(x, 0); }
-u32 rev_bits(u32 x, int bits) { return bits ? bitrev32(x, bits) : 0; }
 
 // ---- vanishing sum through the quotient kernels (see the header comment) -------------------------------------------
 constexpr unsigned VLOG = 7;  // synthetic domain: N = 128, 2N = 256 points = one workgroup
@@ -236,9 +166,14 @@ void ctl_rows(int kind, const u64* scalars, const u64* x, const u64* off, const 
   out[m] = k;
 }
 
-int verify_impl(bn254s_ctx* c, int kind, const bn254s_params& P, int degree_bits, const u64* w, size_t n_words, const u64* scalars,
-                const u64* x, const u64* off, const u64* outputs, size_t n, std::string& err) {
-  View v;
+}  // namespace
+
+// ---- the verifier in three parts (declared in verify_query.h; bn254s_verify_batch runs them for many proofs) -----------
+// Part 1: the shape, the transcript, the vanishing polynomial at zeta and the proof of work.  Leaves the front record of the
+// query round (verify_query.h) and the CTL challenges.  c == nullptr: the AIR at zeta on the host (pure host code, no shared
+// state: safe on any thread); with a context the quotient kernels evaluate it (named buffers of the context: one call at a time).
+int verify_front(bn254s_ctx* c, int kind, const bn254s_params& P, int degree_bits, const u64* w, size_t n_words, View& v, u64* rec,
+                 u64 ctl_ch[4], std::string& err) {
   if (!make_view(kind, P, degree_bits, v) || v.total != n_words) {
     err = "bad proof shape";
     return BN254S_E_VERIFY;
@@ -259,6 +194,7 @@ int verify_impl(bn254s_ctx* c, int kind, const bn254s_params& P, int degree_bits
     betas[i] = ch.challenge();
     gammas[i] = ch.challenge();
   }
+  ctl_ch[0] = betas[0], ctl_ch[1] = betas[1], ctl_ch[2] = gammas[0], ctl_ch[3] = gammas[1];
   u64 st12[12];
   ch.compact(st12);
   if (memcmp(st12, w + v.init, sizeof(st12))) {
@@ -279,17 +215,17 @@ int verify_impl(bn254s_ctx* c, int kind, const bn254s_params& P, int degree_bits
     ch.observe(0);
   }
   gl2 fri_alpha = ch.challenge_ext();
-  const std::vector<int> arities = fri_arities(P, degree_bits);
-  std::vector<gl2> fri_betas;
+  for (size_t i = 0; i < vq_record_words(P.num_queries); i++) rec[i] = 0;
   for (int l = 0; l < v.L; l++) {
     ch.observe_n(w + v.fri_caps + 64 * (size_t)l, 64);
-    fri_betas.push_back(ch.challenge_ext());
+    gl2 b = ch.challenge_ext();
+    rec[VQ_REC_BETAS + 2 * l] = b.c0;
+    rec[VQ_REC_BETAS + 2 * l + 1] = b.c1;
   }
   ch.observe_n(w + v.final_poly, 2 * v.final_len);
   ch.observe(w[v.pow]);
   u64 pow_response = ch.challenge();
-  std::vector<size_t> qidx(P.num_queries);
-  for (auto& q : qidx) q = (size_t)(ch.challenge() % M2);
+  for (uint32_t q = 0; q < P.num_queries; q++) rec[VQ_REC_QUERIES + q] = ch.challenge() % M2;
 
   // ---- vanishing polynomial at zeta --------------------------------------------------------------------------------
   const u64 g = gl_root_of_unity(degree_bits);
@@ -322,106 +258,44 @@ int verify_impl(bn254s_ctx* c, int kind, const bn254s_params& P, int degree_bits
     }
   }
 
-  // ---- verify_fri_proof -----------------------------------------------------------------------------------------------
+  // ---- verify_fri_proof: proof of work, then what the query rounds need of the openings --------------------------------
   if (pow_response >> (64 - P.pow_bits)) {
     err = "Invalid proof of work witness";
     return BN254S_E_VERIFY;
   }
   // batches of fri_instance: zeta (trace | aux | quotient), g zeta (trace | aux), 1 (CTL Z columns of the aux oracle)
-  const int num_lookup = sh.n_lookup_cols();
-  struct PolyRef {
-    int oracle, col;
-  };
-  std::vector<PolyRef> batch[3];
   std::vector<gl2> opened[3];
-  for (int p = 0; p < W; p++) { batch[0].push_back({0, p}); opened[0].push_back(ext(w + v.local + 2 * (size_t)p)); }
-  for (int p = 0; p < A; p++) { batch[0].push_back({1, p}); opened[0].push_back(ext(w + v.aux + 2 * (size_t)p)); }
-  for (int p = 0; p < NQ; p++) { batch[0].push_back({2, p}); opened[0].push_back(ext(w + v.quot + 2 * (size_t)p)); }
-  for (int p = 0; p < W; p++) { batch[1].push_back({0, p}); opened[1].push_back(ext(w + v.next + 2 * (size_t)p)); }
-  for (int p = 0; p < A; p++) { batch[1].push_back({1, p}); opened[1].push_back(ext(w + v.aux_next + 2 * (size_t)p)); }
-  for (int p = 0; p < v.NCTLZ; p++) { batch[2].push_back({1, num_lookup + p}); opened[2].push_back(base(w[v.ctlz + p])); }
-  const gl2 points[3] = {zeta, gl2_mul_base(zeta, g), one};
-  gl2 reduced[3], alpha_len[3];
+  for (int p = 0; p < W; p++) opened[0].push_back(ext(w + v.local + 2 * (size_t)p));
+  for (int p = 0; p < A; p++) opened[0].push_back(ext(w + v.aux + 2 * (size_t)p));
+  for (int p = 0; p < NQ; p++) opened[0].push_back(ext(w + v.quot + 2 * (size_t)p));
+  for (int p = 0; p < W; p++) opened[1].push_back(ext(w + v.next + 2 * (size_t)p));
+  for (int p = 0; p < A; p++) opened[1].push_back(ext(w + v.aux_next + 2 * (size_t)p));
+  for (int p = 0; p < v.NCTLZ; p++) opened[2].push_back(base(w[v.ctlz + p]));
+  auto put = [&](int at, gl2 x) { rec[at] = x.c0, rec[at + 1] = x.c1; };
+  put(VQ_REC_ALPHA, fri_alpha);
+  put(VQ_REC_ZETA, zeta);
+  put(VQ_REC_ZETA_NEXT, gl2_mul_base(zeta, g));
   for (int b = 0; b < 3; b++) {
     gl2 acc = gl2_make(0, 0);
     for (size_t j = opened[b].size(); j-- > 0;) acc = gl2_add(gl2_mul(acc, fri_alpha), opened[b][j]);
-    reduced[b] = acc;
-    alpha_len[b] = gl2_pow(fri_alpha, batch[b].size());
+    put(VQ_REC_REDUCED + 2 * b, acc);
+    put(VQ_REC_ALPHA_LEN + 2 * b, gl2_pow(fri_alpha, opened[b].size()));
   }
-  const int widths[3] = {W, A, NQ};
-  const u64 w_lde = gl_root_of_unity(v.log_m2);
-  for (uint32_t q = 0; q < P.num_queries; q++) {
-    const u64* r = w + v.queries + v.wpq * q;
-    const size_t x_index = qidx[q];
-    const u64* leaf[3];
-    for (int t = 0; t < 3; t++) {
-      leaf[t] = r;
-      const u64* path = r + widths[t];
-      if (!merkle_ok(leaf[t], widths[t], x_index, w + v.caps + 64 * (size_t)t, path, v.P)) {
-        err = "Invalid Merkle proof (initial tree)";
-        return BN254S_E_VERIFY;
-      }
-      r = path + 4 * (size_t)v.P;
-    }
-    u64 subgroup_x = gl_mul(GL_GEN, gl_pow(w_lde, rev_bits((u32)x_index, v.log_m2)));
-    gl2 sum = gl2_make(0, 0);  // fri_combine_initial
-    for (int b = 0; b < 3; b++) {
-      gl2 acc = gl2_make(0, 0);
-      for (size_t j = batch[b].size(); j-- > 0;)
-        acc = gl2_add(gl2_mul(acc, fri_alpha), base(leaf[batch[b][j].oracle][batch[b][j].col]));
-      gl2 num = gl2_sub(acc, reduced[b]);
-      gl2 den = gl2_sub(base(subgroup_x), points[b]);
-      sum = gl2_add(gl2_mul(sum, alpha_len[b]), gl2_mul(num, gl2_inv(den)));
-    }
-    gl2 old_eval = sum;
-    size_t xi = x_index;
-    for (int l = 0; l < v.L; l++) {
-      const int ab = arities[l];
-      const size_t arity = (size_t)1 << ab;
-      const u64* evals = r;
-      const u64* path = r + 2 * arity;
-      r = path + 4 * (size_t)v.layer_path[l];
-      const size_t coset_index = xi >> ab, within = xi & (arity - 1);
-      if (!gl2_eq(ext(evals + 2 * within), old_eval)) {
-        err = "FRI consistency check failed";
-        return BN254S_E_VERIFY;
-      }
-      // compute_evaluation: interpolate {(x gg^i, P(x gg^i))} at beta
-      const u64 gg = gl_root_of_unity(ab);
-      std::vector<gl2> ev(arity);
-      for (size_t i = 0; i < arity; i++) ev[rev_bits((u32)i, ab)] = ext(evals + 2 * i);
-      const size_t rev_within = rev_bits((u32)within, ab);
-      std::vector<u64> pts(arity);
-      pts[0] = gl_mul(subgroup_x, gl_pow(gg, arity - rev_within));
-      for (size_t i = 1; i < arity; i++) pts[i] = gl_mul(pts[i - 1], gg);
-      gl2 res = gl2_make(0, 0);
-      for (size_t i = 0; i < arity; i++) {
-        gl2 num = one;
-        u64 den = 1;
-        for (size_t k = 0; k < arity; k++)
-          if (k != i) {
-            num = gl2_mul(num, gl2_sub(fri_betas[l], base(pts[k])));
-            den = gl_mul(den, gl_sub(pts[i], pts[k]));
-          }
-        res = gl2_add(res, gl2_mul(ev[i], gl2_mul_base(num, gl_inv(den))));
-      }
-      old_eval = res;
-      if (!merkle_ok(evals, 2 * arity, coset_index, w + v.fri_caps + 64 * (size_t)l, path, v.layer_path[l])) {
-        err = "Invalid Merkle proof (FRI layer)";
-        return BN254S_E_VERIFY;
-      }
-      for (int k = 0; k < ab; k++) subgroup_x = gl_mul(subgroup_x, subgroup_x);
-      xi = coset_index;
-    }
-    gl2 fin = gl2_make(0, 0);
-    for (size_t i = v.final_len; i-- > 0;) fin = gl2_add(gl2_mul_base(fin, subgroup_x), ext(w + v.final_poly + 2 * i));
-    if (!gl2_eq(fin, old_eval)) {
-      err = "Final polynomial evaluation is invalid";
-      return BN254S_E_VERIFY;
-    }
-  }
+  return BN254S_OK;
+}
 
-  // ---- cross-table lookups against the claimed inputs / outputs (ctl_values.rs:28-47) -------------------------------
+// Part 2 on the host: the code of query q (verify_query.h).  The checks run in the verifier's order and stop at the first failure.
+int verify_query_host(const View& v, const u64* w, const u64* rec, uint32_t q) {
+  for (int t = 0; t < 3; t++)
+    if (!vq_merkle_check(v, w, rec, q, t)) return 1 + t;
+  const int fri = vq_fri_round(v, w, rec, q);
+  return vq_merge_code(v.L, [&](int which) { return which < 3 || vq_merkle_check(v, w, rec, q, which); }, fri);
+}
+
+// Part 3: cross-table lookups against the claimed inputs / outputs (ctl_values.rs:28-47)
+int verify_ctl(int kind, const View& v, const u64* w, const u64 ctl_ch[4], const u64* scalars, const u64* x, const u64* off,
+               const u64* outputs, size_t n, std::string& err) {
+  const u64 *betas = ctl_ch, *gammas = ctl_ch + 2;
   u64 sums[2][2] = {{0, 0}, {0, 0}};
   std::vector<u64> in, out;
   for (size_t k = 0; k < n; k++) {
@@ -448,7 +322,22 @@ int verify_impl(bn254s_ctx* c, int kind, const bn254s_params& P, int degree_bits
   return BN254S_OK;
 }
 
-}  // namespace
+static int verify_impl(bn254s_ctx* c, int kind, const bn254s_params& P, int degree_bits, const u64* w, size_t n_words,
+                       const u64* scalars, const u64* x, const u64* off, const u64* outputs, size_t n, std::string& err) {
+  View v;
+  u64 ctl_ch[4];
+  std::vector<u64> rec(vq_record_words(P.num_queries));
+  int rc = verify_front(c, kind, P, degree_bits, w, n_words, v, rec.data(), ctl_ch, err);
+  if (rc != BN254S_OK) return rc;
+  for (uint32_t q = 0; q < P.num_queries; q++) {
+    const int code = verify_query_host(v, w, rec.data(), q);
+    if (code) {
+      err = vq_code_text(v.L, code);
+      return BN254S_E_VERIFY;
+    }
+  }
+  return verify_ctl(kind, v, w, ctl_ch, scalars, x, off, outputs, n, err);
+}
 
 extern "C" int bn254s_ctl_values(int kind, const uint64_t* scalars, const uint64_t* x, const uint64_t* off, const uint64_t* outputs,
                                  size_t n, uint64_t* in_rows, uint64_t* out_rows) {

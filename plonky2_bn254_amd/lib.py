@@ -73,6 +73,15 @@ def load_library():
     lib.bn254s_verify.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t]
     lib.bn254s_verify_host.argtypes = [C.c_int, C.POINTER(Params), C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t, C.c_char_p,
                                        C.c_size_t]
+    if hasattr(lib, "bn254s_verify_batch"):  # (absent from a library built before the batch verifier existed)
+        lib.bn254s_verify_batch.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_uint32, vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_size_t,
+                                            vp, vp, C.c_size_t]
+        lib.bn254s_selftest_verify_front.argtypes = [C.c_int, C.POINTER(Params), C.c_uint32, vp, C.c_size_t, vp, C.c_size_t]
+        lib.bn254s_selftest_query_round.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_uint32, vp, C.c_size_t, vp, C.c_size_t,
+                                                    C.c_size_t, vp]
+        lib.bn254s_selftest_verify_batch_ms.argtypes = [vp, vp]
+        lib.bn254s_selftest_query_text.argtypes = [C.c_int, C.c_int]
+        lib.bn254s_selftest_query_text.restype = C.c_char_p
     lib.bn254s_map_to_g2.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     lib.bn254s_hash_to_fq2.argtypes = [vp, C.c_size_t, vp]
     lib.bn254s_g1_msm_chain.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, vp]
@@ -318,6 +327,24 @@ class Context:
         if rc == -8:
             raise VerifyError(self._lib.bn254s_last_error(self._h).decode())
         self._check(rc, "bn254s_verify")
+
+    def verify_batch(self, kind, proofs, scalars, x, offset, n_jobs=None, params: Optional[Params] = None, degree_bits=None):
+        """bn254s_verify_batch: many proofs of one kind, parameter set and height at once, the FRI query rounds on the device.
+        `proofs`: a list of Proof or of (words, outputs); the job arrays hold the jobs of all proofs in proof order, n_jobs[i] of
+        them for proof i (default: as many as proof i has outputs).  Returns a list with None for an accepted proof and the
+        reference verifier's text for a rejected one - what verify_host raises for that proof alone."""
+        return _verify_batch(self._lib, self._h, kind, proofs, scalars, x, offset, n_jobs, params, degree_bits)
+
+    def verify_batch_ms(self) -> dict:
+        """The split of the latest verify_batch of this context in ms: front and ctl are wall times of the host threads, upload,
+        k_vb_merkle and k_vb_fri come from device events."""
+        ms = (C.c_float * 5)()
+        self._check(self._lib.bn254s_selftest_verify_batch_ms(self._h, ms), "bn254s_selftest_verify_batch_ms")
+        return dict(zip(("front", "upload", "k_vb_merkle", "k_vb_fri", "ctl"), (float(v) for v in ms)))
+
+    def query_round(self, kind, words, degree_bits, records, chunk_proofs=0, params: Optional[Params] = None) -> np.ndarray:
+        """bn254s_selftest_query_round on the device: see the module-level query_round."""
+        return query_round(kind, words, degree_bits, records, chunk_proofs, params, _ctx=self)
 
     def map_to_g2(self, u, offsets, params: Optional[Params] = None):
         """u [n,8], offsets [n,16] -> (points [n,16], fq_jobs [2n,8], g2_jobs [n,20], fq proofs, g2 proofs): the config-5
@@ -816,6 +843,129 @@ def verify_host(kind, words, degree_bits, scalars, x, offset, outputs, params: O
         raise VerifyError(buf.value.decode())
     if rc != 0:
         raise RuntimeError(f"bn254s_verify_host failed with {rc}: {buf.value.decode()}")
+
+
+_POINT_WORDS = (8, 16, 4)
+VERIFY_RECORD_HEAD = 34  # BN254S_VERIFY_RECORD_HEAD: words of a front record before the query indices
+
+
+def proof_words(kind, degree_bits, params: Optional[Params] = None) -> int:
+    """Words of a proof of 2^degree_bits rows in the layout of include/bn254_stark.h (make_view of csrc/verify_query.h)."""
+    params = params or default_params()
+    plan = proof_plan(kind, 1, 0)
+    w, a = plan["W"], plan["A"]
+    log_m2 = degree_bits + params.rate_bits
+    path = log_m2 - params.cap_height
+    wpq = w + a + 4 + 12 * path
+    d, bits, layers = degree_bits, log_m2, 0
+    while d > params.final_poly_bits and d + params.rate_bits - params.arity_bits >= params.cap_height:
+        d -= params.arity_bits
+        bits -= params.arity_bits
+        layers += 1
+        wpq += (2 << params.arity_bits) + 4 * (bits - params.cap_height)
+    return 192 + 4 * w + 4 * a + 4 + 8 + 64 * layers + params.num_queries * wpq + (2 << d) + 1 + 12
+
+
+def _word_arrays(word_list):
+    """Contiguous uint64 arrays (kept alive by the caller) and the pointer table the batch entry points take."""
+    arrs = [np.ascontiguousarray(w, dtype=np.uint64).reshape(-1) for w in word_list]
+    table = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    return arrs, table
+
+
+def _verify_batch(lib, handle, kind, proofs, scalars, x, offset, n_jobs, params, degree_bits):
+    params = params or default_params()
+    pw = _POINT_WORDS[kind]
+    words, outs = [], []
+    for pr in proofs:
+        if isinstance(pr, (tuple, list)):
+            w, o = pr
+        else:
+            w, o = pr.words, pr.outputs
+            degree_bits = pr.degree_bits if degree_bits is None else degree_bits
+        words.append(np.ascontiguousarray(w, dtype=np.uint64).reshape(-1))
+        outs.append(np.ascontiguousarray(o, dtype=np.uint64).reshape(-1))
+    n = len(words)
+    if n == 0:
+        raise ValueError("verify_batch: no proofs")
+    if degree_bits is None:  # the height whose proof has as many words as one of these
+        sizes = {proof_words(kind, d, params): d for d in range(7, 31)}
+        degree_bits = next((sizes[w.size] for w in words if w.size in sizes), None)
+        if degree_bits is None:
+            raise ValueError("verify_batch: cannot tell degree_bits from the proof sizes, pass it")
+    if n_jobs is None:
+        n_jobs = [o.size // pw for o in outs]
+    n_jobs = [int(k) for k in n_jobs]
+    lo = np.concatenate(([0], np.cumsum(n_jobs)))
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+    x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, pw)
+    offset = None if offset is None else np.ascontiguousarray(offset, dtype=np.uint64).reshape(-1, pw)
+    verdicts = [None] * n
+    # one size per call in the C interface: proofs of different sizes (a truncated one beside whole ones) go in one call per size
+    groups = {}
+    for i, w in enumerate(words):
+        groups.setdefault(w.size, []).append(i)
+    for n_words, idx in groups.items():
+        rows = np.concatenate([np.arange(lo[i], lo[i + 1]) for i in idx]).astype(np.int64)
+        whole = len(groups) == 1
+        s_, x_ = (scalars, x) if whole else (np.ascontiguousarray(scalars[rows]), np.ascontiguousarray(x[rows]))
+        o_ = offset if whole or offset is None else np.ascontiguousarray(offset[rows])
+        outputs = np.ascontiguousarray(np.concatenate([outs[i] for i in idx]))
+        arrs, table = _word_arrays([words[i] for i in idx])
+        m = len(idx)
+        nj = (C.c_size_t * m)(*[n_jobs[i] for i in idx])
+        status = np.zeros(m, dtype=np.int32)
+        stride = 128
+        err = C.create_string_buffer(m * stride)
+        rc = lib.bn254s_verify_batch(handle, kind, C.byref(params), degree_bits, table, n_words, _ptr(s_), _ptr(x_), _ptr(o_),
+                                     _ptr(outputs), nj, m, status.ctypes.data_as(C.c_void_p), err, stride)
+        if rc not in (0, -8):
+            why = lib.bn254s_last_error(handle).decode() if handle else ""
+            raise RuntimeError(f"bn254s_verify_batch failed with {rc}: {why}")
+        for k, i in enumerate(idx):
+            if status[k] != 0:
+                verdicts[i] = err.raw[k * stride:(k + 1) * stride].split(b"\0", 1)[0].decode()
+    return verdicts
+
+
+def verify_batch_host(kind, proofs, scalars, x, offset, n_jobs=None, params: Optional[Params] = None, degree_bits=None):
+    """bn254s_verify_batch without a context: the same verdicts as Context.verify_batch, every part on host threads, no GPU."""
+    return _verify_batch(load_library(), None, kind, proofs, scalars, x, offset, n_jobs, params, degree_bits)
+
+
+def verify_front(kind, words, degree_bits, params: Optional[Params] = None):
+    """bn254s_selftest_verify_front: (status, record) of one proof - the host part of the verifier up to and including the proof of
+    work, and the front record the query rounds read (layout: include/bn254_stark.h).  Host only."""
+    lib = load_library()
+    params = params or default_params()
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    rec = np.zeros(VERIFY_RECORD_HEAD + params.num_queries, dtype=np.uint64)
+    rc = lib.bn254s_selftest_verify_front(kind, C.byref(params), degree_bits, _ptr(words), words.size, _ptr(rec), rec.size)
+    return rc, rec
+
+
+def query_round(kind, words, degree_bits, records, chunk_proofs=0, params: Optional[Params] = None, _ctx=None) -> np.ndarray:
+    """bn254s_selftest_query_round on the host: the code of every query of every proof, [n_proofs, num_queries] int32, for the
+    proofs `words` (a list of word arrays of one size) and their front records [n_proofs, record words]."""
+    lib = load_library()
+    params = params or default_params()
+    arrs, table = _word_arrays(words)
+    records = np.ascontiguousarray(records, dtype=np.uint64).reshape(len(arrs), -1)
+    if records.shape[1] != VERIFY_RECORD_HEAD + params.num_queries:
+        raise ValueError("query_round: records of the wrong length")
+    codes = np.full((len(arrs), params.num_queries), -1, dtype=np.int32)
+    rc = lib.bn254s_selftest_query_round(_ctx._h if _ctx is not None else None, kind, C.byref(params), degree_bits, table,
+                                         arrs[0].size, _ptr(records), len(arrs), chunk_proofs, codes.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        why = lib.bn254s_last_error(_ctx._h).decode() if _ctx is not None else ""
+        raise RuntimeError(f"bn254s_selftest_query_round failed with {rc}: {why}")
+    return codes
+
+
+def query_text(n_layers, code):
+    """bn254s_selftest_query_text: the verifier's text of a query code ("" for 0, None for a code that does not exist)."""
+    t = load_library().bn254s_selftest_query_text(n_layers, code)
+    return None if t is None else t.decode()
 
 
 PLAN_BUFFERS = ("in", "tvals", "tcoef", "hist", "tmp", "ldechunk", "sponge", "comb", "tlde", "trees", "avals", "acoef", "alde",
