@@ -4,7 +4,7 @@
 #include <cstring>
 #include "proven_jobs.h"  // fq_below_p
 #include "merkle.h"
-#include "trace_g1.h"
+#include "trace.h"
 #include "fq_selftest.h"
 #include "aux.h"
 #include "poseidon_dev.h"
@@ -18,6 +18,7 @@ void quotient_g1_module_warm();
 void quotient_g2fq_module_warm();
 void trace_g1_module_warm();
 void trace_g2fq_module_warm();
+void trace_shared_module_warm();
 void prover_module_warm();
 
 extern "C" {
@@ -94,6 +95,7 @@ int bn254s_ctx_create(int device_id, bn254s_ctx** out) {
   quotient_g2fq_module_warm();
   trace_g1_module_warm();
   trace_g2fq_module_warm();
+  trace_shared_module_warm();
   prover_module_warm();
   *out = c;
   return BN254S_OK;

@@ -27,8 +27,9 @@
 // of phase A is used instead because it is already tuned (four lanes per input on G1, 3 products of latency per doubling) and
 // the 256-lane reduction after it is 8 additions deep, where a fused loop is 256 dependent doublings plus additions per input.
 //
-// What differs between the curves is in the traits G1 / G2 below; the coordinate field is reached through the fe_* overloads
-// (fq_dev.h, trace_common.h) and the points through the pt_* / lds_* overloads (chain_scan.h).
+// What differs between the curves is in the traits G1 / G2 below (on top of CurveG1 / CurveG2, trace_common.h); the coordinate
+// field is reached through the fe_* overloads (fq_dev.h, trace_common.h), the points through the pt_* / lds_* overloads
+// (chain_scan.h) and their SoA arrays through pa_load / pa_store (trace_common.h).
 #include <climits>
 #include <cstring>
 #include <string>
@@ -36,17 +37,13 @@
 #include <vector>
 #include "proven_jobs.h"
 #include "trace_common.h"
-#include "chain_scan.h"
-#include "trace_g1.h"
-#include "trace_g2fq.h"
+#include "trace.h"
 #include "../../include/bn254_stark.h"
 
 namespace {
 
-struct G1 {
-  using P = g1j;  // point
-  using F = fq;   // coordinate field
-  static constexpr int FW = 4, KIND = 0;  // words of a coordinate; job kind of bn254s_prove_batch
+struct G1 : CurveG1 {
+  static constexpr int KIND = 0;  // job kind of bn254s_prove_batch
   static constexpr size_t CHUNK = 16384;  // inputs per product launch: 3 x 4 x NPTS words = 49 KB of D_k per input, 808 MB at most
   static constexpr const char *TAG = "g1_msm", *LARGEST = "G1 proof", *POOL = "msm", *POOL_PTS = "msm.pts";
   static constexpr size_t pts_words(size_t pcnt) { return 3 * 4 * pcnt; }
@@ -57,10 +54,8 @@ struct G1 {
     launch_g1_dbl_chain(d_x, m, pts, pts + 4 * cnt, pts + 8 * cnt, st);
   }
 };
-struct G2 {
-  using P = g2j;
-  using F = fq2;
-  static constexpr int FW = 8, KIND = 1;
+struct G2 : CurveG2 {
+  static constexpr int KIND = 1;
   // D_k (3 x 2 x 4 x NPTS words) and the chain's znorm (4 x NPTS words) are 28 x 514 x 8 B = 115 KB per input, 943 MB for a chunk
   static constexpr size_t CHUNK = 8192;
   static constexpr const char *TAG = "g2_msm", *LARGEST = "G2 proof", *POOL = "g2msm", *POOL_PTS = "g2msm.pts";
@@ -71,28 +66,7 @@ struct G2 {
   }
 };
 
-// a^-1 from the batched inverse of norm(a); the norm of an Fq element is the element itself
-__device__ __forceinline__ fq fe_inv_from_norm_inv(const fq&, const fq& ninv) { return ninv; }
-__device__ __forceinline__ fq2 fe_inv_from_norm_inv(const fq2& a, const fq& ninv) { return fq2_inv_from_norm_inv(a, ninv); }
-
-// A level of the scan: cnt points in SoA form, coordinate c (0 = X, 1 = Y, 2 = Z) at b + FW c cnt; inside it, word l of Fq
-// component j (G2: c0, c1) of element e at [(4 j + l) cnt + e] (fe_ld / fe_st).  The doubling chains' arrays have the same layout.
-template <class P>
-__device__ __forceinline__ P pa_load(const u64* b, size_t cnt, size_t e) {
-  constexpr size_t FW = sizeof(P) / sizeof(fq) / 3 * 4;
-  P p;
-  fe_ld(b, cnt, e, p.x);
-  fe_ld(b + FW * cnt, cnt, e, p.y);
-  fe_ld(b + 2 * FW * cnt, cnt, e, p.z);
-  return p;
-}
-template <class P>
-__device__ __forceinline__ void pa_store(u64* b, size_t cnt, size_t e, const P& p) {
-  constexpr size_t FW = sizeof(P) / sizeof(fq) / 3 * 4;
-  fe_st(b, cnt, e, p.x);
-  fe_st(b + FW * cnt, cnt, e, p.y);
-  fe_st(b + 2 * FW * cnt, cnt, e, p.z);
-}
+// A level of the scan is cnt points in the SoA form of pa_load / pa_store (trace_common.h), like the doubling chains' arrays.
 
 // F_0 = R (canonical affine words -> Jacobian, Montgomery)
 template <class C>

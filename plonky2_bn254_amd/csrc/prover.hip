@@ -18,8 +18,7 @@
 #include <cstring>
 #include <thread>
 #include "ctx.h"
-#include "trace_g1.h"
-#include "trace_g2fq.h"
+#include "trace.h"
 #include "aux.h"
 #include "merkle.h"
 #include "quotient.h"

@@ -12,7 +12,6 @@
 //   sum_i w_i*constr_i = qsign * sum_j quot_j * M_j  +  sum_d (lo_d*u_d + hi_d*B*u_d) - off*sum u_d  -  sum_i w_i*input_i
 // with M_j = sum_t w_{j+t} m_t and u_d = w_{d+1} - B*w_d depending on alpha only (host-precomputed).
 #include "quotient_sched.h"
-#include "trace_g1.h"
 #include "quotient.h"
 
 static constexpr int G1_K_AIR = 1111;
@@ -31,15 +30,15 @@ __device__ __forceinline__ void g1_add_part(const QArgs& A, size_t j) {
   const qc32 W3 = QCONST(u32, A.W + 2 * (size_t)A.K);  // cut weights (accw_mad)
   u64 tot0 = 0, tot1 = 0;
   int e = 0;
-  const int AUX = G1_COL_AUX;
-  const u64 filter = TL(G1_COL_FILTER);
+  const int AUX = G1L::AUX;
+  const u64 filter = TL(G1L::FILTER);
   const u64 is_x_eq_filter = TL(AUX + G1_AUX_IS_X_EQ_FILTER);
   u64 ax[16], lam[16], t16[16], u16[16];
-  ld16(tl, M2, j, G1_COL_A, ax);
+  ld16(tl, M2, j, G1L::A, ax);
   if constexpr (part == 0) {
     // block 0: delta_x * inv - 1 + is_x_eq (eval_is_modulus_zero), then filter*is_x_eq*delta_x[i], then e = 49
     const u64 is_x_eq = TL(AUX + G1_AUX_IS_X_EQ);
-    ld16(tl, M2, j, G1_COL_B, u16);
+    ld16(tl, M2, j, G1L::B, u16);
 #pragma unroll
     for (int i = 0; i < 16; i++) u16[i] = gl_sub(u16[i], ax[i]);  // delta_x
     ld16(tl, M2, j, AUX + G1_AUX_IS_X_EQ_AUX, t16);               // inv limbs
@@ -59,11 +58,11 @@ __device__ __forceinline__ void g1_add_part(const QArgs& A, size_t j) {
   } else if constexpr (part == 1) {
     // block 1: lambda*delta_x - (b.y - a.y) under filter - is_x_eq_filter
     ld16(tl, M2, j, AUX + G1_AUX_LAMBDA, lam);
-    ld16(tl, M2, j, G1_COL_B, u16);
+    ld16(tl, M2, j, G1L::B, u16);
 #pragma unroll
     for (int i = 0; i < 16; i++) u16[i] = gl_sub(u16[i], ax[i]);  // delta_x
-    ld16(tl, M2, j, G1_COL_B + 16, t16);                          // b.y
-    ld16(tl, M2, j, G1_COL_A + 16, ax);                           // a.y (a.x no longer needed)
+    ld16(tl, M2, j, G1L::B + 16, t16);                          // b.y
+    ld16(tl, M2, j, G1L::A + 16, ax);                           // a.y (a.x no longer needed)
 #pragma unroll
     for (int i = 0; i < 16; i++) t16[i] = gl_sub(t16[i], ax[i]);  // b.y - a.y, formed here: three arrays live in the block, not four
     mz_block<true>(tl, M2, j, AUX + G1_AUX_LAMBDA_AUX, A, G1_MZ_E0[1], 1,
@@ -76,7 +75,7 @@ __device__ __forceinline__ void g1_add_part(const QArgs& A, size_t j) {
   } else if constexpr (part == 2) {
     // block 2: 2*lambda*a.y - 3*a.x^2 under is_x_eq_filter, then a.y == b.y (e = 116..131)
     ld16(tl, M2, j, AUX + G1_AUX_LAMBDA, lam);
-    ld16(tl, M2, j, G1_COL_A + 16, u16);  // a.y
+    ld16(tl, M2, j, G1L::A + 16, u16);  // a.y
     mz_block<true>(tl, M2, j, AUX + G1_AUX_LAMBDA_AUX, A, G1_MZ_E0[2], 2,
              is_x_eq_filter,
              [&](int i) __attribute__((always_inline)) {
@@ -85,7 +84,7 @@ __device__ __forceinline__ void g1_add_part(const QArgs& A, size_t j) {
              },
              tot0, tot1);
     e = 116;
-    ld16(tl, M2, j, G1_COL_B + 16, t16);
+    ld16(tl, M2, j, G1L::B + 16, t16);
     AccW g;
     accw_init(g);
 #pragma unroll
@@ -95,8 +94,8 @@ __device__ __forceinline__ void g1_add_part(const QArgs& A, size_t j) {
   } else if constexpr (part == 3) {
     // block 3: lambda^2 - (a.x + b.x + c.x)
     ld16(tl, M2, j, AUX + G1_AUX_LAMBDA, lam);
-    ld16(tl, M2, j, G1_COL_B, t16);
-    ld16(tl, M2, j, G1_COL_C, u16);
+    ld16(tl, M2, j, G1L::B, t16);
+    ld16(tl, M2, j, G1L::C, u16);
 #pragma unroll
     for (int i = 0; i < 16; i++) ax[i] = gl_add(gl_add(ax[i], t16[i]), u16[i]);  // a.x + b.x + c.x: two arrays live in the block
     mz_block<true>(tl, M2, j, AUX + G1_AUX_X_AUX, A, G1_MZ_E0[3], 3, filter,
@@ -108,11 +107,11 @@ __device__ __forceinline__ void g1_add_part(const QArgs& A, size_t j) {
   } else {
     // block 4: lambda*(c.x - a.x) + c.y + a.y
     ld16(tl, M2, j, AUX + G1_AUX_LAMBDA, lam);
-    ld16(tl, M2, j, G1_COL_C, u16);
+    ld16(tl, M2, j, G1L::C, u16);
 #pragma unroll
     for (int i = 0; i < 16; i++) u16[i] = gl_sub(u16[i], ax[i]);  // c.x - a.x
-    ld16(tl, M2, j, G1_COL_C + 16, t16);                          // c.y
-    ld16(tl, M2, j, G1_COL_A + 16, ax);                           // a.y
+    ld16(tl, M2, j, G1L::C + 16, t16);                          // c.y
+    ld16(tl, M2, j, G1L::A + 16, ax);                           // a.y
 #pragma unroll
     for (int i = 0; i < 16; i++) t16[i] = gl_add(t16[i], ax[i]);  // c.y + a.y
     mz_block<true>(tl, M2, j, AUX + G1_AUX_Y_AUX, A, G1_MZ_E0[4], 4, filter,

@@ -1,8 +1,11 @@
-// Shared device helpers of the three trace generators (G1 / G2 / Fq exp): SoA Fq vectors, batched inversion,
-// limb conversion, generate_modulus_zero (reference src/starks/modular/modulus_zero.rs:77-123), round-flag
-// table, and the range-check columns (generate_range_checks).
+// Shared device helpers of the three trace generators (G1 / G2 / Fq exp) and of msm.hip: SoA vectors of field elements and
+// points, the curve-generic kernels of phase A (doubling chain on one lane, running sums, outputs), limb conversion,
+// generate_modulus_zero (reference src/starks/modular/modulus_zero.rs:77-123) and the frame of a row kernel (position of a
+// row in the double-and-add schedule, packed limbs, the schedule columns).  The kernels all three share are in
+// trace_shared.hip (trace.h).
 #pragma once
 #include "fq_dev.h"
+#include "chain_scan.h"
 #include "../../include/bn254_stark.h"
 
 static constexpr int NPTS = 514;  // per instance: 0 = offset | one, 1+k = C_k (k<256), 257+k = D_k (k<=256)
@@ -32,6 +35,63 @@ __device__ __forceinline__ void fe_st(u64* base, size_t count, size_t e, const f
   st_fq(base + 4 * count, count, e, v.c1);
 }
 
+// What differs between the curves: point, coordinate field, 64-bit words of a coordinate.
+struct CurveG1 {
+  using P = g1j;
+  using F = fq;
+  static constexpr int FW = 4;
+};
+struct CurveG2 {
+  using P = g2j;
+  using F = fq2;
+  static constexpr int FW = 8;
+};
+// cnt points in SoA form, coordinate c (0 = X, 1 = Y, 2 = Z) at b + FW c cnt; inside it, word l of Fq component j (G2: c0, c1)
+// of element e at [(4 j + l) cnt + e] (fe_ld / fe_st).  The trace scratch and the levels of the msm scan have this layout.
+template <class P>
+__device__ __forceinline__ P pa_load(const u64* b, size_t cnt, size_t e) {
+  constexpr size_t FW = sizeof(P) / sizeof(fq) / 3 * 4;
+  P p;
+  fe_ld(b, cnt, e, p.x);
+  fe_ld(b + FW * cnt, cnt, e, p.y);
+  fe_ld(b + 2 * FW * cnt, cnt, e, p.z);
+  return p;
+}
+template <class P>
+__device__ __forceinline__ void pa_store(u64* b, size_t cnt, size_t e, const P& p) {
+  constexpr size_t FW = sizeof(P) / sizeof(fq) / 3 * 4;
+  fe_st(b, cnt, e, p.x);
+  fe_st(b + FW * cnt, cnt, e, p.y);
+  fe_st(b + 2 * FW * cnt, cnt, e, p.z);
+}
+// a^-1 from the batched inverse of norm(a); the norm of an Fq element is the element itself
+__device__ __forceinline__ fq fe_inv_from_norm_inv(const fq&, const fq& ninv) { return ninv; }
+__device__ __forceinline__ fq2 fe_inv_from_norm_inv(const fq2& a, const fq& ninv) { return fq2_inv_from_norm_inv(a, ninv); }
+// G2 keeps norm(Z) of every point beside it, the input of the batched inversion; G1 inverts Z itself
+__device__ __forceinline__ void st_znorm(u64*, size_t, size_t, const fq&) {}
+__device__ __forceinline__ void st_znorm(u64* znorm, size_t cnt, size_t e, const fq2& z) { st_fq(znorm, cnt, e, fq2_norm(z)); }
+
+// Affine coordinates (Montgomery) of point e of pts; zinv = the batched inverses of Z (G1) or of norm(Z) (G2).  (On G1 the
+// inverse is zinv itself and Z is not loaded.)
+template <class P>
+struct AffPt {
+  decltype(P::x) x, y;
+};
+template <class P>
+__device__ __forceinline__ AffPt<P> affine_pt(const u64* pts, const u64* zinv, size_t cnt, size_t e) {
+  using F = decltype(P::x);
+  constexpr size_t FW = sizeof(F) / sizeof(fq) * 4;
+  F x, y, z;
+  fe_ld(pts + 2 * FW * cnt, cnt, e, z);
+  const F zi = fe_inv_from_norm_inv(z, ld_fq(zinv, cnt, e)), z2 = fe_sqr(zi);
+  fe_ld(pts, cnt, e, x);
+  fe_ld(pts + FW * cnt, cnt, e, y);
+  AffPt<P> r;
+  r.x = fe_mul(x, z2);
+  r.y = fe_mul(fe_mul(y, z2), zi);
+  return r;
+}
+
 // index of the highest set bit of s below position k, or -1
 __device__ __forceinline__ int last_set_below(const u64 s[4], int k) {
   for (int w = 3; w >= 0; w--) {
@@ -47,6 +107,79 @@ __device__ __forceinline__ int last_set_below(const u64 s[4], int k) {
 __device__ __forceinline__ int sum_point(const u64 s[4], int k) {
   int j = last_set_below(s, k);
   return j < 0 ? 0 : 1 + j;
+}
+
+// ---- phase A and the outputs, for either curve (C = CurveG1 / CurveG2; znorm is used on G2 only) -------------------------------
+// The doubling chain on one lane per instance: D_k = 2^k x at point 257 + k.  The drivers use the cooperative chains
+// (chain_coop.h), which store the same values bit for bit; this one is kept for A/B measurements.
+template <class C>
+__global__ __launch_bounds__(64) void k_dbl_chain_one_lane(const u64* __restrict__ xs, int n, u64* __restrict__ pts,
+                                                           u64* __restrict__ znorm) {
+  LATENCY_KERNEL_PRIO();
+  int inst = blockIdx.x * blockDim.x + threadIdx.x;
+  if (inst >= n) return;
+  size_t cnt = (size_t)NPTS * n;
+  typename C::P D;
+  fe_from_canonical(xs + 2 * C::FW * inst, D.x);
+  fe_from_canonical(xs + 2 * C::FW * inst + C::FW, D.y);
+  fe_one(D.z);
+#pragma unroll 1
+  for (int k = 0; k <= 256; k++) {
+    size_t e = (size_t)(257 + k) * n + inst;
+    pa_store(pts, cnt, e, D);
+    st_znorm(znorm, cnt, e, D.z);
+    if (k < 256) D = pt_double(D);
+  }
+}
+
+// one workgroup per instance, lane k: S_k = offset + sum_{j<k, bit_j} D_j, then C_k = S_k + D_k
+template <class C>
+__global__ __launch_bounds__(256) void k_sum_scan(const u64* __restrict__ scalars, const u64* __restrict__ offs, int n,
+                                                  u64* __restrict__ pts, u64* __restrict__ znorm, int* __restrict__ err) {
+  using P = typename C::P;
+  LATENCY_KERNEL_PRIO();
+  __shared__ u64 sh[3 * C::FW * 256];
+  const int inst = blockIdx.x, k = threadIdx.x;
+  const size_t cnt = (size_t)NPTS * n;
+  auto load = [&](int pt) { return pa_load<P>(pts, cnt, (size_t)pt * n + inst); };
+  auto store = [&](int pt, const P& p) {
+    size_t e = (size_t)pt * n + inst;
+    pa_store(pts, cnt, e, p);
+    st_znorm(znorm, cnt, e, p.z);
+  };
+  P f;
+  if (k == 0) {
+    fe_from_canonical(offs + 2 * C::FW * inst, f.x);
+    fe_from_canonical(offs + 2 * C::FW * inst + C::FW, f.y);
+    fe_one(f.z);
+    store(0, f);
+  } else {
+    const int j = k - 1;
+    const bool bit = (scalars[4 * inst + (j >> 6)] >> (j & 63)) & 1;
+    f = bit ? load(257 + j) : pt_infinity((const P*)nullptr);
+  }
+  pt_scan256(f, sh, k);
+  P d = load(257 + k), c;
+  if (pt_inf(f)) {
+    c = d;  // only after an S_j = -D_j further down, which is reported there
+  } else if (pt_add(f, d, c) == 2) {
+    atomicCAS(err, 0, BN254S_E_INVALID_POINT);
+  }
+  store(1 + k, c);
+}
+
+// final outputs: s*x + offset = S_255 in canonical affine form, 2 FW words per instance
+template <class C>
+__global__ void k_outputs(const u64* __restrict__ scalars, int n, const u64* __restrict__ pts, const u64* __restrict__ zinv,
+                          u64* __restrict__ out) {
+  LATENCY_KERNEL_PRIO();
+  int inst = blockIdx.x * blockDim.x + threadIdx.x;
+  if (inst >= n) return;
+  u64 s[4];
+  for (int i = 0; i < 4; i++) s[i] = scalars[4 * inst + i];
+  const auto p = affine_pt<typename C::P>(pts, zinv, (size_t)NPTS * n, (size_t)sum_point(s, 256) * n + inst);
+  fe_store_canonical(out + 2 * C::FW * inst, p.x);
+  fe_store_canonical(out + 2 * C::FW * inst + C::FW, p.y);
 }
 
 __device__ __forceinline__ void fq_to_limbs(const fq& mont, int limbs[16]) {
@@ -236,10 +369,72 @@ __device__ __forceinline__ void pol_mul16(const int* a, const int* b, long long*
     for (int j = 0; j < 16; j++) out[i + j] += (long long)a[i] * b[j];
 }
 
+// ---- the frame of a row kernel ---------------------------------------------------------------------------------------------------
+// Trace row r is row `row` of instance `inst`: step k of the double-and-add walk, an adding (Fq exp: multiplying) row when even,
+// a doubling (squaring) row when odd.  s = the scalar.
+// The row kernels sit at the register ceiling, and two things here decide whether they stay there.  The flags are functions,
+// not members: a bool that goes through a member reaches the kernel as 8-bit arithmetic, which changes the allocation of
+// k_g1_rows.  And s is indexed by constants only: one variable index into a member keeps the whole struct in scratch memory,
+// so code that needs one indexes a local copy of the array.
+struct RowPos {
+  int inst, row, k;
+  u64 s[4];
+  __device__ __forceinline__ bool adding() const { return (row & 1) == 0; }
+  __device__ __forceinline__ bool bitk() const {  // bit k of the scalar
+    const u64 w[4] = {s[0], s[1], s[2], s[3]};
+    return (w[k >> 6] >> (k & 63)) & 1;
+  }
+};
+__device__ __forceinline__ RowPos row_pos(size_t r, const u64* scalars) {
+  RowPos p;
+  p.inst = (int)(r >> 9);
+  p.row = (int)(r & 511);
+  p.k = p.row >> 1;
+  for (int i = 0; i < 4; i++) p.s[i] = scalars[4 * p.inst + i];
+  return p;
+}
+// the sixteen limbs of a packed coordinate to columns col .. col + 15 of row r
+__device__ __forceinline__ void p16_put(u64* trace, size_t N, size_t r, int col, const P16& p) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    trace[(size_t)(col + 2 * i) * N + r] = (u64)(p.w[i] & 0xFFFF);
+    trace[(size_t)(col + 2 * i + 1) * N + r] = (u64)(p.w[i] >> 16);
+  }
+}
+__device__ __forceinline__ P16 p16_sel(bool first, const P16& x, const P16& y) {
+  P16 o;
+#pragma unroll
+  for (int i = 0; i < 8; i++) o.w[i] = first ? x.w[i] : y.w[i];
+  return o;
+}
+// the schedule columns of layout L: bits rotated left by k (scalar_mul_stark.rs:163-167), round flags, bookkeeping
+template <class L>
+__device__ __forceinline__ void put_schedule(u64* trace, size_t N, size_t r, const RowPos& pos, const u64* rf_tbl) {
+  auto put = [&](int col, u64 v) { trace[(size_t)col * N + r] = v; };
+  const int row = pos.row;
+  const u64 s[4] = {pos.s[0], pos.s[1], pos.s[2], pos.s[3]};
+  for (int i = 0; i < 256; i++) {
+    int src = (i + pos.k) & 255;
+    put(L::BITS + i, (s[src >> 6] >> (src & 63)) & 1);
+  }
+  put(L::FLAGS + 0, row == 0);
+  put(L::FLAGS + 1, row == 511);
+  put(L::FLAGS + 2, (u64)row);
+  put(L::FLAGS + 3, rf_tbl[row]);
+  put(L::FLAGS + 4, rf_tbl[512 + row]);
+  put(L::TIMESTAMP, (u64)pos.inst);
+  put(L::IS_ADDING, pos.adding() ? 1 : 0);
+  put(L::IDNL, pos.adding() ? 0 : (row == 511 ? 0 : 1));
+  put(L::FILTER, 1);
+}
 
-// shared kernels live in trace_g1.hip
-void launch_fq_batch_inv(const u64* in, u64* out, size_t count, hipStream_t st);
-void launch_round_flag_table(u64* tbl, hipStream_t st);
-// histogram of columns [rc_begin, rc_end) -> frequency column, and the range counter column
-void launch_range_columns(u64* trace, size_t N, int rc_begin, int rc_end, int freq_col, int range_col, u32* hist, int* err,
-                          hipStream_t st);
+// ---- scratch of a driver: word offsets taken one after the other; `words` is the size the driver asks its caller for ----------------
+struct ScratchCarve {
+  static constexpr size_t RF_WORDS = 1024 /* round-flag table */, HIST_WORDS = 65536 / 2 /* histogram, 65536 u32 */;
+  size_t words = 0;
+  size_t take(size_t w) {
+    const size_t at = words;
+    words += w;
+    return at;
+  }
+};

@@ -7,173 +7,19 @@
 //   generate_is_modulus_zero (src/starks/modular/is_modulus_zero.rs:36-66),
 //   generate_modulus_zero (src/starks/modular/modulus_zero.rs:77-123, incl. pol_remove_root_2exp),
 //   generate_round_flags (src/starks/common/round_flags.rs:21-44), generate_range_checks (:71-87).
-// Column layout: src/starks/curves/g1/scalar_mul_view.rs:34-49 (see trace_g1.h).
+// Column layout: src/starks/curves/g1/scalar_mul_view.rs:34-49 (G1L, layout.h).
 //
 // Phase A (no inversions, Jacobian coordinates): the 256 doublings D_k = 2^k x are the only sequential part (one lane per
 // instance); the running sums S_k and C_k = S_k + D_k come from a 256-lane prefix scan per instance (chain_scan.h).
-// Every intermediate point (offset, C_k, D_k) is stored.  Phase A': all Z are inverted with Montgomery's batch trick.  Phase B (one thread per trace row): affine a, b, c, lambda and the limb /
-// quotient / carry witnesses; the exact division by p is a multiplication by p^-1 mod 2^288.
+// Every intermediate point (offset, C_k, D_k) is stored.  Phase A': all Z are inverted with Montgomery's batch trick
+// (trace_shared.hip).  Phase B (one thread per trace row): affine a, b, c, lambda and the limb / quotient / carry witnesses;
+// the exact division by p is a multiplication by p^-1 mod 2^288.
 // The trace is written column-major (trace[c*N + row]), so consecutive lanes write consecutive words.
 #include "trace_common.h"
-#include "chain_scan.h"
 #include "chain_coop.h"
-#include "trace_g1.h"
+#include "trace.h"
 
-#ifndef BN254S_BATCH_INV_CH
-#define BN254S_BATCH_INV_CH 4
-#endif
-// ---- batched field inversion ------------------------------------------------------------------------------
-// out[e] = in[e]^-1 (0 -> 0); each thread owns CH elements strided by the grid size.
-// (The backward pass is unrolled by template recursion: the unroller refuses a body of two inlined products "as too large" even
-// under a pragma, and a rolled loop would index v[] / pre[] dynamically, i.e. keep them in scratch memory.)
-template <int J, int CH>
-__device__ __forceinline__ void batch_inv_back(const fq (&v)[CH], const fq (&pre)[CH], fq& inv, u64* __restrict__ out, size_t count,
-                                               size_t tid, size_t T) {
-  if constexpr (J >= 0) {
-    const size_t e = tid + J * T;
-    if (e < count) {
-      if (fq_is_zero(v[J])) {
-        st_fq(out, count, e, fq_zero());
-      } else {
-        st_fq(out, count, e, fq_mul(inv, pre[J]));
-        if constexpr (J > 0) inv = fq_mul(inv, v[J]);
-      }
-    }
-    batch_inv_back<J - 1, CH>(v, pre, inv, out, count, tid, T);
-  }
-}
-template <int CH>
-__global__ __launch_bounds__(64) void k_fq_batch_inv(const u64* __restrict__ in, u64* __restrict__ out, size_t count) {
-  LATENCY_KERNEL_PRIO();
-  size_t T = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  fq v[CH], pre[CH];
-  fq acc = fq_one();
-#pragma unroll
-  for (int j = 0; j < CH; j++) {
-    size_t e = tid + j * T;
-    v[j] = e < count ? ld_fq(in, count, e) : fq_zero();
-    pre[j] = acc;
-    if (!fq_is_zero(v[j])) acc = fq_mul(acc, v[j]);
-  }
-  fq inv = fq_inv(acc);
-  batch_inv_back<CH - 1, CH>(v, pre, inv, out, count, tid, T);
-}
-
-// Goldilocks inverses of counter and counter-511 for counter in [0,512): computed once per context.
-__global__ void k_round_flag_table(u64* tbl /* [2][512] */) {
-  LATENCY_KERNEL_PRIO();
-  int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= 512) return;
-  tbl[c] = c == 0 ? 0 : gl_inv((u64)c);
-  u64 cp = gl_sub((u64)c, 511);
-  tbl[512 + c] = cp == 0 ? 0 : gl_inv(cp);
-}
-
-// ---- range-check columns (generate_range_checks, scalar_mul_stark.rs:71-87) ----------------------------
-// LDS-privatised histogram.  blockIdx.y selects the half of the 2^16 bins kept in LDS (32768 u32 = 128 KB);
-// every block sweeps its slice of the range-checked columns once per half.  The witness columns are far from
-// uniform (aux_hi limbs sit at 2^13 +- 1, many flags are 0/1), so before touching LDS each wave peels off up to
-// two "leader" values with ballots and adds their multiplicity with one atomic.
-__global__ __launch_bounds__(1024) void k_histogram(const u64* __restrict__ trace, size_t N, int col_begin, int col_end,
-                                                    u32* __restrict__ hist, int* __restrict__ err) {
-  __shared__ u32 h[32768];
-  const u32 half = blockIdx.y;
-  for (int b = threadIdx.x; b < 32768; b += blockDim.x) h[b] = 0;
-  __syncthreads();
-  const size_t total = (size_t)(col_end - col_begin) * N;
-  const size_t per = (total + gridDim.x - 1) / gridDim.x;
-  const size_t lo = (size_t)blockIdx.x * per, hi = min(total, lo + per);
-  const u64* src = trace + (size_t)col_begin * N;
-  const int lane = threadIdx.x & 63;
-  for (size_t base = lo; base < hi; base += blockDim.x) {
-    size_t i = base + threadIdx.x;
-    u64 v = i < hi ? src[i] : ~0ULL;
-    if (i < hi && v >= 65536) atomicCAS(err, 0, BN254S_E_INTERNAL);
-    bool active = i < hi && (v >> 15) == half;
-    u32 bin = (u32)v & 32767;
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-      unsigned long long m = __ballot(active);
-      if (m == 0) break;
-      int leader = __ffsll((long long)m) - 1;
-      u32 lv = __shfl(bin, leader);
-      bool same = active && bin == lv;
-      unsigned long long ms = __ballot(same);
-      if (lane == leader) atomicAdd(&h[lv], (u32)__popcll(ms));
-      active = active && !same;
-    }
-    if (active) atomicAdd(&h[bin], 1u);
-  }
-  __syncthreads();
-  for (int b = threadIdx.x; b < 32768; b += blockDim.x) {
-    u32 cnt = h[b];
-    if (cnt) atomicAdd(&hist[half * 32768 + b], cnt);
-  }
-}
-__global__ __launch_bounds__(256) void k_range_columns(u64* __restrict__ trace, size_t N, int freq_col, int range_col,
-                                                       const u32* __restrict__ hist) {
-  LATENCY_KERNEL_PRIO();
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  trace[(size_t)range_col * N + i] = i < 65536 ? i : 65535;
-  trace[(size_t)freq_col * N + i] = i < 65536 ? (u64)hist[i] : 0;
-}
-
-
-// Debug / parity: out[i] = in[i]^-1 mod p on canonical words (0 -> 0), one lane per element, by divsteps (fq_inv) and by Fermat
-// (fq_inv_fermat): out[n][8] = the two results.
-__global__ __launch_bounds__(64) void k_fq_inv_selftest(const u64* __restrict__ in, u64* __restrict__ out, size_t n) {
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const fq a = fq_from_canonical(in + 4 * i);
-  const bool z = fq_is_zero(a);
-  const fqw r0 = fq_to_canonical(z ? a : fq_inv(a)), r1 = fq_to_canonical(z ? a : fq_inv_fermat(a));
-  for (int k = 0; k < 4; k++) {
-    out[8 * i + k] = r0.l[k];
-    out[8 * i + 4 + k] = r1.l[k];
-  }
-}
-void launch_fq_inv_selftest(const u64* in, u64* out, size_t n, hipStream_t st) {
-  k_fq_inv_selftest<<<(unsigned)((n + 63) / 64), 64, 0, st>>>(in, out, n);
-}
-
-void launch_fq_batch_inv(const u64* in, u64* out, size_t count, hipStream_t st) {
-  // one divstep inversion (~12 k instructions) per CH elements plus three products (~1 k) per element: CH = 4 keeps the arrays in
-  // registers (no scratch) and puts 4x as many waves on the GPU as the CH = 8 of the Fermat days
-  const int CH = BN254S_BATCH_INV_CH;
-  size_t threads = (count + CH - 1) / CH;
-  k_fq_batch_inv<CH><<<(unsigned)((threads + 63) / 64), 64, 0, st>>>(in, out, count);
-}
-void launch_round_flag_table(u64* tbl, hipStream_t st) { k_round_flag_table<<<2, 256, 0, st>>>(tbl); }
-void launch_range_columns(u64* trace, size_t N, int rc_begin, int rc_end, int freq_col, int range_col, u32* hist, int* err,
-                          hipStream_t st) {
-  hipMemsetAsync(hist, 0, 65536 * 4, st);
-  k_histogram<<<dim3(128, 2), 1024, 0, st>>>(trace, N, rc_begin, rc_end, hist, err);
-  k_range_columns<<<(unsigned)((N + 255) / 256), 256, 0, st>>>(trace, N, freq_col, range_col, hist);
-}
-
-
-// ---- phase A: doubling chain (sequential) + running sums (parallel scan, chain_scan.h) -----------------------------
-__global__ __launch_bounds__(64) void k_g1_dbl_chain(const u64* __restrict__ xs, int n, u64* __restrict__ px, u64* __restrict__ py,
-                                                     u64* __restrict__ pz) {
-  LATENCY_KERNEL_PRIO();
-  int inst = blockIdx.x * blockDim.x + threadIdx.x;
-  if (inst >= n) return;
-  size_t cnt = (size_t)NPTS * n;
-  g1j D;
-  D.x = fq_from_canonical(xs + 8 * inst);
-  D.y = fq_from_canonical(xs + 8 * inst + 4);
-  D.z = fq_one();
-#pragma unroll 1
-  for (int k = 0; k <= 256; k++) {
-    size_t e = (size_t)(257 + k) * n + inst;
-    st_fq(px, cnt, e, D.x);
-    st_fq(py, cnt, e, D.y);
-    st_fq(pz, cnt, e, D.z);
-    if (k < 256) D = g1_double(D);
-  }
-}
-
+// ---- phase A: doubling chain (sequential); the running sums are k_sum_scan<CurveG1> (trace_common.h) ----------------
 // Cooperative form of the chain: four lanes per instance, lane p computes the p-th product of a level, the sums between the
 // products are integer combinations with one reduction each (chain_coop.h), values travel through LDS:
 //   level 1   a = X^2            b = Y^2              Z' = (2Y) Z
@@ -181,7 +27,7 @@ __global__ __launch_bounds__(64) void k_g1_dbl_chain(const u64* __restrict__ xs,
 //   combine   X' = f + 4a + 4c - 4s                   w = 6s - 6a - 6c - f          (= d - X' with d = 2 (s - a - c))
 //   level 3   m = (3a) w
 //   combine   Y' = m - 8c
-// Same formulas as g1_double, every stored value canonical: the points are bit for bit those of k_g1_dbl_chain, in 3 products
+// Same formulas as g1_double, every stored value canonical: the points are bit for bit those of k_dbl_chain_one_lane, in 3 products
 // + 2 reductions of latency per doubling instead of 7 products + 13 additions.
 namespace g1coop {
 using namespace chain_coop;
@@ -246,127 +92,58 @@ __global__ __launch_bounds__(64) void k_g1_dbl_chain_coop(const u64* __restrict_
   }
 }
 
-// one workgroup per instance, lane k: S_k = offset + sum_{j<k, bit_j} D_j, then C_k = S_k + D_k
-__global__ __launch_bounds__(256) void k_g1_sum_scan(const u64* __restrict__ scalars, const u64* __restrict__ offs, int n,
-                                                     u64* __restrict__ px, u64* __restrict__ py, u64* __restrict__ pz,
-                                                     int* __restrict__ err) {
-  LATENCY_KERNEL_PRIO();
-  __shared__ u64 sh[12 * 256];
-  const int inst = blockIdx.x, k = threadIdx.x;
-  const size_t cnt = (size_t)NPTS * n;
-  auto load = [&](int pt) {
-    size_t e = (size_t)pt * n + inst;
-    g1j p;
-    p.x = ld_fq(px, cnt, e);
-    p.y = ld_fq(py, cnt, e);
-    p.z = ld_fq(pz, cnt, e);
-    return p;
-  };
-  auto store = [&](int pt, const g1j& p) {
-    size_t e = (size_t)pt * n + inst;
-    st_fq(px, cnt, e, p.x);
-    st_fq(py, cnt, e, p.y);
-    st_fq(pz, cnt, e, p.z);
-  };
-  g1j f;
-  if (k == 0) {
-    f.x = fq_from_canonical(offs + 8 * inst);
-    f.y = fq_from_canonical(offs + 8 * inst + 4);
-    f.z = fq_one();
-    store(0, f);
-  } else {
-    const int j = k - 1;
-    const bool bit = (scalars[4 * inst + (j >> 6)] >> (j & 63)) & 1;
-    f = bit ? load(257 + j) : pt_infinity((const g1j*)nullptr);
-  }
-  pt_scan256(f, sh, k);
-  g1j d = load(257 + k), c;
-  if (pt_inf(f)) {
-    c = d;  // only after an S_j = -D_j further down, which is reported there
-  } else if (g1_add(f, d, c) == 2) {
-    atomicCAS(err, 0, BN254S_E_INVALID_POINT);
-  }
-  store(1 + k, c);
-}
-
-// ---- phase B helpers ------------------------------------------------------------------------------------------
-struct AffPt {
-  fq x, y;
-};
-__device__ __forceinline__ AffPt affine_pt(const u64* px, const u64* py, const u64* zi, size_t cnt, size_t e) {
-  fq z = ld_fq(zi, cnt, e);
-  fq z2 = fq_sqr(z);
-  AffPt r;
-  r.x = fq_mul(ld_fq(px, cnt, e), z2);
-  r.y = fq_mul(fq_mul(ld_fq(py, cnt, e), z2), z);
-  return r;
-}
+// ---- phase B ------------------------------------------------------------------------------------------------
 // denominators: add row: b.x - a.x (or 2 a.y when the x coincide); doubling row: 2 a.y
-__global__ __launch_bounds__(64) void k_g1_row_den(const u64* __restrict__ scalars, int n, const u64* __restrict__ px,
-                                                   const u64* __restrict__ py, const u64* __restrict__ zi,
-                                                   u64* __restrict__ den) {
+__global__ __launch_bounds__(64) void k_g1_row_den(const u64* __restrict__ scalars, int n, const u64* __restrict__ pts,
+                                                   const u64* __restrict__ zi, u64* __restrict__ den) {
   LATENCY_KERNEL_PRIO();
   size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t nrows = (size_t)n * 512;
   if (r >= nrows) return;
-  int inst = (int)(r >> 9), row = (int)(r & 511), k = row >> 1;
+  const RowPos pos = row_pos(r, scalars);
+  const int inst = pos.inst, k = pos.k;
   size_t cnt = (size_t)NPTS * n;
-  u64 s[4];
-  for (int i = 0; i < 4; i++) s[i] = scalars[4 * inst + i];
   fq d;
-  if ((row & 1) == 0) {
-    AffPt a = affine_pt(px, py, zi, cnt, (size_t)sum_point(s, k) * n + inst);
-    AffPt b = affine_pt(px, py, zi, cnt, (size_t)(257 + k) * n + inst);
+  if (pos.adding()) {
+    AffPt<g1j> a = affine_pt<g1j>(pts, zi, cnt, (size_t)sum_point(pos.s, k) * n + inst);
+    AffPt<g1j> b = affine_pt<g1j>(pts, zi, cnt, (size_t)(257 + k) * n + inst);
     d = fq_sub(b.x, a.x);
     if (fq_is_zero(d)) d = fq_dbl(a.y);
   } else {
-    AffPt a = affine_pt(px, py, zi, cnt, (size_t)(257 + k) * n + inst);
+    AffPt<g1j> a = affine_pt<g1j>(pts, zi, cnt, (size_t)(257 + k) * n + inst);
     d = fq_dbl(a.y);
   }
   st_fq(den, nrows, r, d);
 }
 
-// ---- phase B: one thread per trace row ----------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_g1_rows(const u64* __restrict__ scalars, int n, const u64* __restrict__ px,
-                                                const u64* __restrict__ py, const u64* __restrict__ zi,
-                                                const u64* __restrict__ deninv, const u64* __restrict__ rf_tbl,
-                                                u64* __restrict__ trace, size_t N, int* __restrict__ err) {
+// one thread per trace row
+__global__ __launch_bounds__(64) void k_g1_rows(const u64* __restrict__ scalars, int n, const u64* __restrict__ pts,
+                                                const u64* __restrict__ zi, const u64* __restrict__ deninv,
+                                                const u64* __restrict__ rf_tbl, u64* __restrict__ trace, size_t N,
+                                                int* __restrict__ err) {
   LATENCY_KERNEL_PRIO();
+  typedef G1L L;
   size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t nrows = (size_t)n * 512;
   if (r >= nrows) return;
-  const int inst = (int)(r >> 9), row = (int)(r & 511), k = row >> 1;
-  const bool adding = (row & 1) == 0;
+  const RowPos pos = row_pos(r, scalars);
+  const int inst = pos.inst, k = pos.k;
+  const bool adding = pos.adding(), bitk = pos.bitk();
   const size_t cnt = (size_t)NPTS * n;
-  u64 s[4];
-  for (int i = 0; i < 4; i++) s[i] = scalars[4 * inst + i];
-  const bool bitk = (s[k >> 6] >> (k & 63)) & 1;
 
   // Three affine points per row, one after the other (packed into limbs at once, trace_common.h):  P1 = the running sum S (S_(k-1) on
   // an adding row, S_k on a doubling row), P2 = D_k, P3 = C_k (adding) or D_(k+1) (doubling).   adding: a = P1, b = P2, c = P3,
   // double = P2, sum = bit ? P3 : P1;   doubling: a = b = P2, c = P3, double = P3, sum = P1.
   auto put = [&](int col, u64 v) { trace[(size_t)col * N + r] = v; };
-  auto put_p = [&](int col, const P16& p) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      put(col + 2 * i, (u64)(p.w[i] & 0xFFFF));
-      put(col + 2 * i + 1, (u64)(p.w[i] >> 16));
-    }
-  };
-  auto sel = [&](bool first, const P16& x, const P16& y) {
-    P16 o;
-#pragma unroll
-    for (int i = 0; i < 8; i++) o.w[i] = first ? x.w[i] : y.w[i];
-    return o;
-  };
+  auto put_p = [&](int col, const P16& p) { p16_put(trace, N, r, col, p); };
   P16 ax, ay, bx, by, lam, invl, s1x, s1y;
   bool x_eq;
   {
-    const AffPt p1 = affine_pt(px, py, zi, cnt, (size_t)sum_point(s, adding ? k : k + 1) * n + inst);
-    const AffPt p2 = affine_pt(px, py, zi, cnt, (size_t)(257 + k) * n + inst);
-    AffPt a = p2;
+    const AffPt<g1j> p1 = affine_pt<g1j>(pts, zi, cnt, (size_t)sum_point(pos.s, adding ? k : k + 1) * n + inst);
+    const AffPt<g1j> p2 = affine_pt<g1j>(pts, zi, cnt, (size_t)(257 + k) * n + inst);
+    AffPt<g1j> a = p2;
     if (adding) a = p1;
-    const AffPt& b = p2;
+    const AffPt<g1j>& b = p2;
     const fq di = ld_fq(deninv, nrows, r);
     x_eq = fq_eq(a.x, b.x);
     fq lambda, inv;
@@ -382,23 +159,23 @@ __global__ __launch_bounds__(64) void k_g1_rows(const u64* __restrict__ scalars,
     lam = p16_pack(lambda); invl = p16_pack(inv);
     s1x = p16_pack(p1.x); s1y = p16_pack(p1.y);
   }
-  put_p(G1_COL_A, ax); put_p(G1_COL_A + 16, ay);
-  put_p(G1_COL_B, bx); put_p(G1_COL_B + 16, by);
-  put_p(G1_COL_AUX + G1_AUX_LAMBDA, lam);
-  put_p(G1_COL_AUX + G1_AUX_IS_X_EQ_AUX, invl);
+  put_p(L::A, ax); put_p(L::A + 16, ay);
+  put_p(L::B, bx); put_p(L::B + 16, by);
+  put_p(L::AUX + G1_AUX_LAMBDA, lam);
+  put_p(L::AUX + G1_AUX_IS_X_EQ_AUX, invl);
   P16 cx, cy;
   {
-    const AffPt p3 = affine_pt(px, py, zi, cnt, (size_t)(adding ? 1 + k : 258 + k) * n + inst);
+    const AffPt<g1j> p3 = affine_pt<g1j>(pts, zi, cnt, (size_t)(adding ? 1 + k : 258 + k) * n + inst);
     cx = p16_pack(p3.x);
     cy = p16_pack(p3.y);
   }
-  put_p(G1_COL_C, cx); put_p(G1_COL_C + 16, cy);
-  put_p(G1_COL_DOUBLE, sel(adding, bx, cx)); put_p(G1_COL_DOUBLE + 16, sel(adding, by, cy));
+  put_p(L::C, cx); put_p(L::C + 16, cy);
+  put_p(L::DOUBLE, p16_sel(adding, bx, cx)); put_p(L::DOUBLE + 16, p16_sel(adding, by, cy));
   const bool sum_is_c = adding && bitk;
-  put_p(G1_COL_SUM, sel(sum_is_c, cx, s1x)); put_p(G1_COL_SUM + 16, sel(sum_is_c, cy, s1y));
+  put_p(L::SUM, p16_sel(sum_is_c, cx, s1x)); put_p(L::SUM + 16, p16_sel(sum_is_c, cy, s1y));
   const u64 is_x_eq = x_eq ? 1 : 0;
-  put(G1_COL_AUX + G1_AUX_IS_X_EQ, is_x_eq);
-  put(G1_COL_AUX + G1_AUX_IS_X_EQ_FILTER, is_x_eq);
+  put(L::AUX + G1_AUX_IS_X_EQ, is_x_eq);
+  put(L::AUX + G1_AUX_IS_X_EQ_FILTER, is_x_eq);
 
   __shared__ long long mz_buf[31][MZ_LANES];  // the polynomial of the current witness block (trace_common.h)
   mz_lds_t* const slots = (mz_lds_t*)&mz_buf[0][threadIdx.x];
@@ -410,7 +187,7 @@ __global__ __launch_bounds__(64) void k_g1_rows(const u64* __restrict__ scalars,
   zero_lds(slots);
   mac(1, bx, &ax, invl, nullptr);
   slots[0] += (long long)is_x_eq - 1;
-  emit(G1_COL_AUX + G1_AUX_IS_X_EQ_AUX + 16);
+  emit(L::AUX + G1_AUX_IS_X_EQ_AUX + 16);
   // lambda witness
   zero_lds(slots);
   if (!x_eq) {  // lambda*(b.x-a.x) - (b.y-a.y)
@@ -421,85 +198,59 @@ __global__ __launch_bounds__(64) void k_g1_rows(const u64* __restrict__ scalars,
     mac(2, lam, nullptr, ay, nullptr);
     mac(-3, ax, nullptr, ax, nullptr);
   }
-  emit(G1_COL_AUX + G1_AUX_LAMBDA_AUX);
+  emit(L::AUX + G1_AUX_LAMBDA_AUX);
   // x witness: lambda^2 - (a.x + b.x + c.x)
   zero_lds(slots);
   mac(1, lam, nullptr, lam, nullptr);
   lin_lds(slots, -1, ax);
   lin_lds(slots, -1, bx);
   lin_lds(slots, -1, cx);
-  emit(G1_COL_AUX + G1_AUX_X_AUX);
+  emit(L::AUX + G1_AUX_X_AUX);
   // y witness: lambda*(c.x - a.x) + c.y + a.y
   zero_lds(slots);
   mac(1, lam, nullptr, cx, &ax);
   lin_lds(slots, 1, cy);
   lin_lds(slots, 1, ay);
-  emit(G1_COL_AUX + G1_AUX_Y_AUX);
+  emit(L::AUX + G1_AUX_Y_AUX);
 
-  // bits rotated left by k (scalar_mul_stark.rs:163-167), flags and bookkeeping columns
-  for (int i = 0; i < 256; i++) {
-    int src = (i + k) & 255;
-    put(G1_COL_BITS + i, (s[src >> 6] >> (src & 63)) & 1);
-  }
-  put(G1_COL_FLAGS + 0, row == 0);
-  put(G1_COL_FLAGS + 1, row == 511);
-  put(G1_COL_FLAGS + 2, (u64)row);
-  put(G1_COL_FLAGS + 3, rf_tbl[row]);
-  put(G1_COL_FLAGS + 4, rf_tbl[512 + row]);
-  put(G1_COL_TIMESTAMP, (u64)inst);
-  put(G1_COL_IS_ADDING, adding ? 1 : 0);
-  put(G1_COL_IDNL, adding ? 0 : (row == 511 ? 0 : 1));
-  put(G1_COL_FILTER, 1);
-}
-
-// ---- final outputs: s*x + offset = S_255 in canonical affine form ------------------------------------------
-__global__ void k_g1_outputs(const u64* __restrict__ scalars, int n, const u64* __restrict__ px, const u64* __restrict__ py,
-                             const u64* __restrict__ zi, u64* __restrict__ out8) {
-  LATENCY_KERNEL_PRIO();
-  int inst = blockIdx.x * blockDim.x + threadIdx.x;
-  if (inst >= n) return;
-  u64 s[4];
-  for (int i = 0; i < 4; i++) s[i] = scalars[4 * inst + i];
-  AffPt p = affine_pt(px, py, zi, (size_t)NPTS * n, (size_t)sum_point(s, 256) * n + inst);
-  const fqw x = fq_to_canonical(p.x), y = fq_to_canonical(p.y);
-  for (int i = 0; i < 4; i++) {
-    out8[8 * inst + i] = x.l[i];
-    out8[8 * inst + 4 + i] = y.l[i];
-  }
+  put_schedule<L>(trace, N, r, pos, rf_tbl);
 }
 
 // ---- host driver ------------------------------------------------------------------------------------------------
-size_t g1_trace_scratch_words(size_t n) {
-  size_t cnt = (size_t)NPTS * n, nrows = n * 512;
-  return 4 * cnt * 4 /* px py pz zi */ + 2 * 4 * nrows /* den, deninv */ + 1024 /* rf table */ + 65536 / 2 /* hist */;
-}
+// word offsets of the arrays in the scratch buffer: the points (X, Y, Z: pa_load), the inverses of Z, the row denominators
+// and their inverses, then the tail all kinds have
+struct G1Scratch : ScratchCarve {
+  size_t pts, zi, den, deninv, rf, hist;
+  explicit G1Scratch(size_t n) {
+    const size_t cnt = (size_t)NPTS * n, nrows = n * 512;
+    pts = take(3 * 4 * cnt), zi = take(4 * cnt), den = take(4 * nrows), deninv = take(4 * nrows);
+    rf = take(RF_WORDS), hist = take(HIST_WORDS);
+  }
+};
+size_t g1_trace_scratch_words(size_t n) { return G1Scratch(n).words; }
 
 int g1_generate_trace_device(const u64* d_scalars, const u64* d_x, const u64* d_off, size_t n, u64* d_trace, size_t N,
                              u64* d_scratch, u64* d_outputs, int* d_err, hipStream_t st, bool with_range) {
-  size_t cnt = (size_t)NPTS * n, nrows = n * 512;
-  u64* px = d_scratch;
-  u64* py = px + 4 * cnt;
-  u64* pz = py + 4 * cnt;
-  u64* zi = pz + 4 * cnt;
-  u64* den = zi + 4 * cnt;
-  u64* deninv = den + 4 * nrows;
-  u64* rf = deninv + 4 * nrows;
-  u32* hist = (u32*)(rf + 1024);
-  if (nrows < N) hipMemsetAsync(d_trace, 0, (size_t)G1_W * N * 8, st);
+  typedef G1L L;
+  const size_t cnt = (size_t)NPTS * n, nrows = n * 512;
+  const G1Scratch sc(n);
+  u64 *pts = d_scratch + sc.pts, *zi = d_scratch + sc.zi, *den = d_scratch + sc.den, *deninv = d_scratch + sc.deninv;
+  u64* rf = d_scratch + sc.rf;
+  u32* hist = (u32*)(d_scratch + sc.hist);
+  if (nrows < N) hipMemsetAsync(d_trace, 0, (size_t)L::W * N * 8, st);
   launch_round_flag_table(rf, st);
   static const bool one_lane_chain = getenv("BN254S_G1_CHAIN_ONE_LANE") != nullptr;  // A/B measurements
   if (one_lane_chain)
-    k_g1_dbl_chain<<<(unsigned)((n + 63) / 64), 64, 0, st>>>(d_x, (int)n, px, py, pz);
+    k_dbl_chain_one_lane<CurveG1><<<(unsigned)((n + 63) / 64), 64, 0, st>>>(d_x, (int)n, pts, nullptr);
   else
-    k_g1_dbl_chain_coop<<<(unsigned)((n + 15) / 16), 64, 0, st>>>(d_x, (int)n, px, py, pz);
-  k_g1_sum_scan<<<(unsigned)n, 256, 0, st>>>(d_scalars, d_off, (int)n, px, py, pz, d_err);
-  launch_fq_batch_inv(pz, zi, cnt, st);
-  k_g1_row_den<<<(unsigned)((nrows + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, px, py, zi, den);
+    launch_g1_dbl_chain(d_x, (int)n, pts, pts + 4 * cnt, pts + 8 * cnt, st);
+  k_sum_scan<CurveG1><<<(unsigned)n, 256, 0, st>>>(d_scalars, d_off, (int)n, pts, nullptr, d_err);
+  launch_fq_batch_inv(pts + 8 * cnt, zi, cnt, st);
+  k_g1_row_den<<<(unsigned)((nrows + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, pts, zi, den);
   launch_fq_batch_inv(den, deninv, nrows, st);
-  k_g1_rows<<<(unsigned)((nrows + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, px, py, zi, deninv, rf, d_trace, N, d_err);
-  if (with_range)
-    launch_range_columns(d_trace, N, G1_RC_BEGIN, G1_RC_END, G1_COL_FREQ, G1_COL_RANGE, hist, d_err, st);
-  if (d_outputs) k_g1_outputs<<<(unsigned)((n + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, px, py, zi, d_outputs);
+  k_g1_rows<<<(unsigned)((nrows + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, pts, zi, deninv, rf, d_trace, N, d_err);
+  if (with_range) launch_range_columns(d_trace, N, L::RC_BEGIN, L::RC_END, L::FREQ, L::RANGE, hist, d_err, st);
+  if (d_outputs) k_outputs<CurveG1><<<(unsigned)((n + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, pts, zi, d_outputs);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -510,5 +261,5 @@ void launch_g1_dbl_chain(const u64* d_x, int n, u64* px, u64* py, u64* pz, hipSt
 // loads this translation unit's code object (the HIP runtime defers that to the first launch otherwise)
 void trace_g1_module_warm() {
   hipFuncAttributes a;
-  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_range_columns));
+  (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_g1_rows));
 }

@@ -7,49 +7,14 @@
 // for Fq exp: FqExpStark::generate_trace / generate_one_set (src/starks/fields/exp_stark.rs:53-206) and
 // generate_fq_mul (src/starks/fields/mul.rs:22-40).
 // Same structure as trace_g1.hip: a sequential inversion-free chain per instance, Montgomery batch inversion,
-// then one lane per trace row.
+// then one lane per trace row.  The points are six SoA Fq vectors one after the other, X.c0, X.c1, Y.c0, Y.c1, Z.c0, Z.c1
+// (pa_load, trace_common.h); the batched inversion works on Fq, so the norm of every Z is kept beside them (znorm).
 #include "trace_common.h"
-#include "chain_scan.h"
 #include "chain_coop.h"
-#include "trace_g2fq.h"
+#include "trace.h"
 
 // ======================================== G2 ==================================================================
-struct Soa2 {  // an Fq2 SoA vector = two Fq SoA vectors
-  u64 *c0, *c1;
-};
-__device__ __forceinline__ fq2 ld_fq2(const Soa2& v, size_t cnt, size_t e) {
-  fq2 r;
-  r.c0 = ld_fq(v.c0, cnt, e);
-  r.c1 = ld_fq(v.c1, cnt, e);
-  return r;
-}
-__device__ __forceinline__ void st_fq2(const Soa2& v, size_t cnt, size_t e, const fq2& x) {
-  st_fq(v.c0, cnt, e, x.c0);
-  st_fq(v.c1, cnt, e, x.c1);
-}
-
-// phase A as in trace_g1.hip: sequential doubling chain, then the running sums by a parallel scan (chain_scan.h)
-__global__ __launch_bounds__(64) void k_g2_dbl_chain(const u64* __restrict__ xs, int n, Soa2 px, Soa2 py, Soa2 pz,
-                                                     u64* __restrict__ znorm) {
-  LATENCY_KERNEL_PRIO();
-  int inst = blockIdx.x * blockDim.x + threadIdx.x;
-  if (inst >= n) return;
-  size_t cnt = (size_t)NPTS * n;
-  g2j D;
-  D.x = fq2_from_canonical(xs + 16 * inst);
-  D.y = fq2_from_canonical(xs + 16 * inst + 8);
-  D.z = fq2_one();
-#pragma unroll 1
-  for (int k = 0; k <= 256; k++) {
-    size_t e = (size_t)(257 + k) * n + inst;
-    st_fq2(px, cnt, e, D.x);
-    st_fq2(py, cnt, e, D.y);
-    st_fq2(pz, cnt, e, D.z);
-    st_fq(znorm, cnt, e, fq2_norm(D.z));
-    if (k < 256) D = g2_double(D);
-  }
-}
-
+// phase A as in trace_g1.hip: sequential doubling chain, then the running sums by a parallel scan (k_sum_scan<CurveG2>)
 // ---- cooperative doubling chain: eight lanes per instance ----------------------------------------------------------
 // The chain is 256 dependent doublings; one lane per instance leaves 2 waves running 6.7 k instructions per doubling.  Here
 // lane (p, c) of an instance's group of eight computes component c of the p-th Fq2 product of a level (a component is ONE
@@ -60,7 +25,7 @@ __global__ __launch_bounds__(64) void k_g2_dbl_chain(const u64* __restrict__ xs,
 //   combine   X' = f + 4a + 4c - 4s                   w = 6s - 6a - 6c - f          (= d - X' with d = 2 (s - a - c))
 //   level 3   m = (3a) w
 //   combine   Y' = m - 8c
-// Same formulas as g2_double, every stored value canonical: the chain's points are bit for bit those of k_g2_dbl_chain.
+// Same formulas as g2_double, every stored value canonical: the chain's points are bit for bit those of k_dbl_chain_one_lane.
 namespace g2coop {
 using namespace chain_coop;
 enum { SX, SY, SZ, SA, SB, SC, SS, SF, SWW, SM, NSLOT };
@@ -68,7 +33,13 @@ constexpr int INST_W = NSLOT * 2 * SLOT_W;  // dwords per instance
 // (product: chain_coop.h)
 }  // namespace g2coop
 
-__global__ __launch_bounds__(64) void k_g2_dbl_chain_coop(const u64* __restrict__ xs, int n, Soa2 px, Soa2 py, Soa2 pz,
+// The c0 and c1 vectors of a coordinate reach the chain as a pair passed by value, as they always have.  (Measured at 128
+// instances: with six pointer arguments, or one base pointer and the vector chosen by arithmetic, the same loop takes 1.16 ms
+// instead of 1.10 ms, profiles/trace_refactor_times.txt.)
+struct VecPair {
+  u64 *c0, *c1;
+};
+__global__ __launch_bounds__(64) void k_g2_dbl_chain_coop(const u64* __restrict__ xs, int n, VecPair px, VecPair py, VecPair pz,
                                                           u64* __restrict__ znorm) {
   using namespace g2coop;
   LATENCY_KERNEL_PRIO();
@@ -128,79 +99,24 @@ __global__ __launch_bounds__(64) void k_g2_dbl_chain_coop(const u64* __restrict_
   }
 }
 
-__global__ __launch_bounds__(256) void k_g2_sum_scan(const u64* __restrict__ scalars, const u64* __restrict__ offs, int n, Soa2 px,
-                                                     Soa2 py, Soa2 pz, u64* __restrict__ znorm, int* __restrict__ err) {
-  LATENCY_KERNEL_PRIO();
-  __shared__ u64 sh[24 * 256];
-  const int inst = blockIdx.x, k = threadIdx.x;
-  const size_t cnt = (size_t)NPTS * n;
-  auto load = [&](int pt) {
-    size_t e = (size_t)pt * n + inst;
-    g2j p;
-    p.x = ld_fq2(px, cnt, e);
-    p.y = ld_fq2(py, cnt, e);
-    p.z = ld_fq2(pz, cnt, e);
-    return p;
-  };
-  auto store = [&](int pt, const g2j& p) {
-    size_t e = (size_t)pt * n + inst;
-    st_fq2(px, cnt, e, p.x);
-    st_fq2(py, cnt, e, p.y);
-    st_fq2(pz, cnt, e, p.z);
-    st_fq(znorm, cnt, e, fq2_norm(p.z));
-  };
-  g2j f;
-  if (k == 0) {
-    f.x = fq2_from_canonical(offs + 16 * inst);
-    f.y = fq2_from_canonical(offs + 16 * inst + 8);
-    f.z = fq2_one();
-    store(0, f);
-  } else {
-    const int j = k - 1;
-    const bool bit = (scalars[4 * inst + (j >> 6)] >> (j & 63)) & 1;
-    f = bit ? load(257 + j) : pt_infinity((const g2j*)nullptr);
-  }
-  pt_scan256(f, sh, k);
-  g2j d = load(257 + k), c;
-  if (pt_inf(f)) {
-    c = d;
-  } else if (g2_add(f, d, c) == 2) {
-    atomicCAS(err, 0, BN254S_E_INVALID_POINT);
-  }
-  store(1 + k, c);
-}
-
-struct Aff2 {
-  fq2 x, y;
-};
-__device__ __forceinline__ Aff2 affine_pt2(const Soa2& px, const Soa2& py, const Soa2& pz, const u64* zni, size_t cnt, size_t e) {
-  fq2 zi = fq2_inv_from_norm_inv(ld_fq2(pz, cnt, e), ld_fq(zni, cnt, e));
-  fq2 z2 = fq2_sqr(zi);
-  Aff2 r;
-  r.x = fq2_mul(ld_fq2(px, cnt, e), z2);
-  r.y = fq2_mul(fq2_mul(ld_fq2(py, cnt, e), z2), zi);
-  return r;
-}
-
 // per row: inv-input slots [0] = norm(den), [1] = dx.c0, [2] = dx.c1  (each an Fq SoA vector of nrows)
-__global__ __launch_bounds__(64) void k_g2_row_den(const u64* __restrict__ scalars, int n, Soa2 px, Soa2 py, Soa2 pz,
+__global__ __launch_bounds__(64) void k_g2_row_den(const u64* __restrict__ scalars, int n, const u64* __restrict__ pts,
                                                    const u64* __restrict__ zni, u64* __restrict__ inv_in) {
   LATENCY_KERNEL_PRIO();
   size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t nrows = (size_t)n * 512;
   if (r >= nrows) return;
-  int inst = (int)(r >> 9), row = (int)(r & 511), k = row >> 1;
+  const RowPos pos = row_pos(r, scalars);
+  const int inst = pos.inst, k = pos.k;
   size_t cnt = (size_t)NPTS * n;
-  u64 s[4];
-  for (int i = 0; i < 4; i++) s[i] = scalars[4 * inst + i];
   fq2 den, dx = fq2_zero();
-  if ((row & 1) == 0) {
-    Aff2 a = affine_pt2(px, py, pz, zni, cnt, (size_t)sum_point(s, k) * n + inst);
-    Aff2 b = affine_pt2(px, py, pz, zni, cnt, (size_t)(257 + k) * n + inst);
+  if (pos.adding()) {
+    AffPt<g2j> a = affine_pt<g2j>(pts, zni, cnt, (size_t)sum_point(pos.s, k) * n + inst);
+    AffPt<g2j> b = affine_pt<g2j>(pts, zni, cnt, (size_t)(257 + k) * n + inst);
     dx = fq2_sub(b.x, a.x);
     den = fq2_is_zero(dx) ? fq2_dbl(a.y) : dx;
   } else {
-    Aff2 a = affine_pt2(px, py, pz, zni, cnt, (size_t)(257 + k) * n + inst);
+    AffPt<g2j> a = affine_pt<g2j>(pts, zni, cnt, (size_t)(257 + k) * n + inst);
     den = fq2_dbl(a.y);
   }
   st_fq(inv_in, 3 * nrows, r, fq2_norm(den));
@@ -208,23 +124,7 @@ __global__ __launch_bounds__(64) void k_g2_row_den(const u64* __restrict__ scala
   st_fq(inv_in, 3 * nrows, 2 * nrows + r, dx.c1);
 }
 
-// out[i] = coefficient polynomials of the Fq2 limb product (g2/ext/mul.rs:14-32)
-__device__ __forceinline__ void ext_mul_c0(const int* x0, const int* x1, const int* y0, const int* y1, long long* out) {
-  long long t[31];
-  pol_mul16(x0, y0, out);
-  pol_mul16(x1, y1, t);
-#pragma unroll
-  for (int i = 0; i < 31; i++) out[i] -= t[i];
-}
-__device__ __forceinline__ void ext_mul_c1(const int* x0, const int* x1, const int* y0, const int* y1, long long* out) {
-  long long t[31];
-  pol_mul16(x0, y1, out);
-  pol_mul16(x1, y0, t);
-#pragma unroll
-  for (int i = 0; i < 31; i++) out[i] += t[i];
-}
-
-__global__ __launch_bounds__(64) void k_g2_rows(const u64* __restrict__ scalars, int n, Soa2 px, Soa2 py, Soa2 pz,
+__global__ __launch_bounds__(64) void k_g2_rows(const u64* __restrict__ scalars, int n, const u64* __restrict__ pts,
                                                 const u64* __restrict__ zni, const u64* __restrict__ inv_out,
                                                 const u64* __restrict__ rf_tbl, u64* __restrict__ trace, size_t N,
                                                 int* __restrict__ err) {
@@ -233,38 +133,24 @@ __global__ __launch_bounds__(64) void k_g2_rows(const u64* __restrict__ scalars,
   size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t nrows = (size_t)n * 512;
   if (r >= nrows) return;
-  const int inst = (int)(r >> 9), row = (int)(r & 511), k = row >> 1;
-  const bool adding = (row & 1) == 0;
+  const RowPos pos = row_pos(r, scalars);
+  const int inst = pos.inst, k = pos.k;
+  const bool adding = pos.adding(), bitk = pos.bitk();
   const size_t cnt = (size_t)NPTS * n;
-  u64 s[4];
-  for (int i = 0; i < 4; i++) s[i] = scalars[4 * inst + i];
-  const bool bitk = (s[k >> 6] >> (k & 63)) & 1;
   // Three affine points per row, one after the other (the field elements of a point are packed into limbs and dropped before the
   // next conversion starts):  P1 = the running sum S (S_(k-1) on an adding row, S_k on a doubling row), P2 = D_k, P3 = C_k (adding)
   // or D_(k+1) (doubling).   adding: a = P1, b = P2, c = P3, double = P2, sum = bit ? P3 : P1;   doubling: a = b = P2, c = P3,
   // double = P3, sum = P1.
   auto put = [&](int col, u64 v) { trace[(size_t)col * N + r] = v; };
-  auto put_p = [&](int col, const P16& p) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      put(col + 2 * i, (u64)(p.w[i] & 0xFFFF));
-      put(col + 2 * i + 1, (u64)(p.w[i] >> 16));
-    }
-  };
-  auto sel = [&](bool first, const P16& x, const P16& y) {
-    P16 o;
-#pragma unroll
-    for (int i = 0; i < 8; i++) o.w[i] = first ? x.w[i] : y.w[i];
-    return o;
-  };
+  auto put_p = [&](int col, const P16& p) { p16_put(trace, N, r, col, p); };
   P16 ax0, ax1, ay0, ay1, bx0, bx1, by0, by1, l0, l1, s1x0, s1x1, s1y0, s1y1;
   bool z0, z1, x_eq;
   {
-    const Aff2 p1 = affine_pt2(px, py, pz, zni, cnt, (size_t)sum_point(s, adding ? k : k + 1) * n + inst);
-    const Aff2 p2 = affine_pt2(px, py, pz, zni, cnt, (size_t)(257 + k) * n + inst);
-    Aff2 a = p2;
+    const AffPt<g2j> p1 = affine_pt<g2j>(pts, zni, cnt, (size_t)sum_point(pos.s, adding ? k : k + 1) * n + inst);
+    const AffPt<g2j> p2 = affine_pt<g2j>(pts, zni, cnt, (size_t)(257 + k) * n + inst);
+    AffPt<g2j> a = p2;
     if (adding) a = p1;
-    const Aff2& b = p2;
+    const AffPt<g2j>& b = p2;
     const fq2 dxm = fq2_sub(b.x, a.x);
     z0 = fq_is_zero(dxm.c0);
     z1 = fq_is_zero(dxm.c1);
@@ -288,16 +174,16 @@ __global__ __launch_bounds__(64) void k_g2_rows(const u64* __restrict__ scalars,
   put_p(L::AUX + G2_AUX_LAMBDA, l0); put_p(L::AUX + G2_AUX_LAMBDA + 16, l1);
   P16 cx0, cx1, cy0, cy1;
   {
-    const Aff2 p3 = affine_pt2(px, py, pz, zni, cnt, (size_t)(adding ? 1 + k : 258 + k) * n + inst);
+    const AffPt<g2j> p3 = affine_pt<g2j>(pts, zni, cnt, (size_t)(adding ? 1 + k : 258 + k) * n + inst);
     cx0 = p16_pack(p3.x.c0); cx1 = p16_pack(p3.x.c1); cy0 = p16_pack(p3.y.c0); cy1 = p16_pack(p3.y.c1);
   }
   put_p(L::C, cx0); put_p(L::C + 16, cx1); put_p(L::C + 32, cy0); put_p(L::C + 48, cy1);
   // double = adding ? b : c;  sum = adding ? (bit ? c : a (= P1)) : P1
-  put_p(L::DOUBLE, sel(adding, bx0, cx0)); put_p(L::DOUBLE + 16, sel(adding, bx1, cx1));
-  put_p(L::DOUBLE + 32, sel(adding, by0, cy0)); put_p(L::DOUBLE + 48, sel(adding, by1, cy1));
+  put_p(L::DOUBLE, p16_sel(adding, bx0, cx0)); put_p(L::DOUBLE + 16, p16_sel(adding, bx1, cx1));
+  put_p(L::DOUBLE + 32, p16_sel(adding, by0, cy0)); put_p(L::DOUBLE + 48, p16_sel(adding, by1, cy1));
   const bool sum_is_c = adding && bitk;
-  put_p(L::SUM, sel(sum_is_c, cx0, s1x0)); put_p(L::SUM + 16, sel(sum_is_c, cx1, s1x1));
-  put_p(L::SUM + 32, sel(sum_is_c, cy0, s1y0)); put_p(L::SUM + 48, sel(sum_is_c, cy1, s1y1));
+  put_p(L::SUM, p16_sel(sum_is_c, cx0, s1x0)); put_p(L::SUM + 16, p16_sel(sum_is_c, cx1, s1x1));
+  put_p(L::SUM + 32, p16_sel(sum_is_c, cy0, s1y0)); put_p(L::SUM + 48, p16_sel(sum_is_c, cy1, s1y1));
   put(L::AUX + G2_AUX_IS_X_EQ, x_eq);
   put(L::AUX + G2_AUX_IS_C0_ZERO, z0);
   put(L::AUX + G2_AUX_IS_C1_ZERO, z1);
@@ -381,76 +267,49 @@ __global__ __launch_bounds__(64) void k_g2_rows(const u64* __restrict__ scalars,
   lin_lds(slots, 1, ay1);
   emit(L::AUX + G2_AUX_Y_AUX + 80);
 
-  for (int i = 0; i < 256; i++) {
-    int src = (i + k) & 255;
-    put(L::BITS + i, (s[src >> 6] >> (src & 63)) & 1);
+  put_schedule<L>(trace, N, r, pos, rf_tbl);
+}
+
+// word offsets of the arrays in the scratch buffer: the points, the norms of Z and their inverses, the three inversion inputs
+// per row (k_g2_row_den) and their inverses, then the tail all kinds have
+struct G2Scratch : ScratchCarve {
+  size_t pts, znorm, zni, inv_in, inv_out, rf, hist;
+  explicit G2Scratch(size_t n) {
+    const size_t cnt = (size_t)NPTS * n, nrows = n * 512;
+    pts = take(3 * 8 * cnt), znorm = take(4 * cnt), zni = take(4 * cnt), inv_in = take(4 * 3 * nrows), inv_out = take(4 * 3 * nrows);
+    rf = take(RF_WORDS), hist = take(HIST_WORDS);
   }
-  put(L::FLAGS + 0, row == 0);
-  put(L::FLAGS + 1, row == 511);
-  put(L::FLAGS + 2, (u64)row);
-  put(L::FLAGS + 3, rf_tbl[row]);
-  put(L::FLAGS + 4, rf_tbl[512 + row]);
-  put(L::TIMESTAMP, (u64)inst);
-  put(L::IS_ADDING, adding ? 1 : 0);
-  put(L::IDNL, adding ? 0 : (row == 511 ? 0 : 1));
-  put(L::FILTER, 1);
-}
-
-__global__ void k_g2_outputs(const u64* __restrict__ scalars, int n, Soa2 px, Soa2 py, Soa2 pz, const u64* __restrict__ zni,
-                             u64* __restrict__ out16) {
-  LATENCY_KERNEL_PRIO();
-  int inst = blockIdx.x * blockDim.x + threadIdx.x;
-  if (inst >= n) return;
-  u64 s[4];
-  for (int i = 0; i < 4; i++) s[i] = scalars[4 * inst + i];
-  Aff2 p = affine_pt2(px, py, pz, zni, (size_t)NPTS * n, (size_t)sum_point(s, 256) * n + inst);
-  const fqw v[4] = {fq_to_canonical(p.x.c0), fq_to_canonical(p.x.c1), fq_to_canonical(p.y.c0), fq_to_canonical(p.y.c1)};
-  for (int j = 0; j < 4; j++)
-    for (int i = 0; i < 4; i++) out16[16 * inst + 4 * j + i] = v[j].l[i];
-}
-
-size_t g2_trace_scratch_words(size_t n) {
-  size_t cnt = (size_t)NPTS * n, nrows = n * 512;
-  return 4 * cnt * 8 /* px py pz (2 each) + znorm + zni */ + 2 * 4 * 3 * nrows /* inv in/out */ + 1024 + 65536 / 2;
-}
+};
+size_t g2_trace_scratch_words(size_t n) { return G2Scratch(n).words; }
 
 int g2_generate_trace_device(const u64* d_scalars, const u64* d_x, const u64* d_off, size_t n, u64* d_trace, size_t N,
                              u64* d_scratch, u64* d_outputs, int* d_err, hipStream_t st, bool with_range) {
-  size_t cnt = (size_t)NPTS * n, nrows = n * 512;
-  u64* p = d_scratch;
-  auto take = [&](size_t words) {
-    u64* r = p;
-    p += words;
-    return r;
-  };
-  Soa2 px{take(4 * cnt), take(4 * cnt)}, py{take(4 * cnt), take(4 * cnt)}, pz{take(4 * cnt), take(4 * cnt)};
-  u64* znorm = take(4 * cnt);
-  u64* zni = take(4 * cnt);
-  u64* inv_in = take(4 * 3 * nrows);
-  u64* inv_out = take(4 * 3 * nrows);
-  u64* rf = take(1024);
-  u32* hist = (u32*)take(65536 / 2);
-  if (nrows < N) hipMemsetAsync(d_trace, 0, (size_t)G2L::W * N * 8, st);
+  typedef G2L L;
+  const size_t cnt = (size_t)NPTS * n, nrows = n * 512;
+  const G2Scratch sc(n);
+  u64 *pts = d_scratch + sc.pts, *znorm = d_scratch + sc.znorm, *zni = d_scratch + sc.zni;
+  u64 *inv_in = d_scratch + sc.inv_in, *inv_out = d_scratch + sc.inv_out, *rf = d_scratch + sc.rf;
+  u32* hist = (u32*)(d_scratch + sc.hist);
+  if (nrows < N) hipMemsetAsync(d_trace, 0, (size_t)L::W * N * 8, st);
   launch_round_flag_table(rf, st);
   static const bool one_lane_chain = getenv("BN254S_G2_CHAIN_ONE_LANE") != nullptr;  // A/B measurements
   if (one_lane_chain)
-    k_g2_dbl_chain<<<(unsigned)((n + 63) / 64), 64, 0, st>>>(d_x, (int)n, px, py, pz, znorm);
+    k_dbl_chain_one_lane<CurveG2><<<(unsigned)((n + 63) / 64), 64, 0, st>>>(d_x, (int)n, pts, znorm);
   else
-    k_g2_dbl_chain_coop<<<(unsigned)((n + 7) / 8), 64, 0, st>>>(d_x, (int)n, px, py, pz, znorm);
-  k_g2_sum_scan<<<(unsigned)n, 256, 0, st>>>(d_scalars, d_off, (int)n, px, py, pz, znorm, d_err);
+    launch_g2_dbl_chain(d_x, (int)n, pts, znorm, st);
+  k_sum_scan<CurveG2><<<(unsigned)n, 256, 0, st>>>(d_scalars, d_off, (int)n, pts, znorm, d_err);
   launch_fq_batch_inv(znorm, zni, cnt, st);
-  k_g2_row_den<<<(unsigned)((nrows + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, px, py, pz, zni, inv_in);
+  k_g2_row_den<<<(unsigned)((nrows + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, pts, zni, inv_in);
   launch_fq_batch_inv(inv_in, inv_out, 3 * nrows, st);
-  k_g2_rows<<<(unsigned)((nrows + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, px, py, pz, zni, inv_out, rf, d_trace, N, d_err);
-  if (with_range)
-    launch_range_columns(d_trace, N, G2L::RC_BEGIN, G2L::RC_END, G2L::FREQ, G2L::RANGE, hist, d_err, st);
-  if (d_outputs) k_g2_outputs<<<(unsigned)((n + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, px, py, pz, zni, d_outputs);
+  k_g2_rows<<<(unsigned)((nrows + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, pts, zni, inv_out, rf, d_trace, N, d_err);
+  if (with_range) launch_range_columns(d_trace, N, L::RC_BEGIN, L::RC_END, L::FREQ, L::RANGE, hist, d_err, st);
+  if (d_outputs) k_outputs<CurveG2><<<(unsigned)((n + 63) / 64), 64, 0, st>>>(d_scalars, (int)n, pts, zni, d_outputs);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 void launch_g2_dbl_chain(const u64* d_x, int n, u64* pts, u64* znorm, hipStream_t st) {
   const size_t v = 4 * (size_t)NPTS * n;
-  Soa2 px{pts, pts + v}, py{pts + 2 * v, pts + 3 * v}, pz{pts + 4 * v, pts + 5 * v};
+  VecPair px{pts, pts + v}, py{pts + 2 * v, pts + 3 * v}, pz{pts + 4 * v, pts + 5 * v};
   k_g2_dbl_chain_coop<<<(unsigned)((n + 7) / 8), 64, 0, st>>>(d_x, n, px, py, pz, znorm);
 }
 
@@ -484,15 +343,13 @@ __global__ __launch_bounds__(64) void k_fq_rows(const u64* __restrict__ scalars,
   size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t nrows = (size_t)n * 512;
   if (r >= nrows) return;
-  const int inst = (int)(r >> 9), row = (int)(r & 511), k = row >> 1;
-  const bool mul_step = (row & 1) == 0;
+  const RowPos pos = row_pos(r, scalars);
+  const int inst = pos.inst, k = pos.k;
+  const bool mul_step = pos.adding(), bitk = pos.bitk();
   const size_t cnt = (size_t)NPTS * n;
-  u64 s[4];
-  for (int i = 0; i < 4; i++) s[i] = scalars[4 * inst + i];
-  const bool bitk = (s[k >> 6] >> (k & 63)) & 1;
   fq a, b, c, square, product;
   if (mul_step) {
-    a = ld_fq(tab, cnt, (size_t)sum_point(s, k) * n + inst);
+    a = ld_fq(tab, cnt, (size_t)sum_point(pos.s, k) * n + inst);
     b = ld_fq(tab, cnt, (size_t)(257 + k) * n + inst);
     c = ld_fq(tab, cnt, (size_t)(1 + k) * n + inst);
     square = b;
@@ -502,7 +359,7 @@ __global__ __launch_bounds__(64) void k_fq_rows(const u64* __restrict__ scalars,
     b = a;
     c = ld_fq(tab, cnt, (size_t)(258 + k) * n + inst);
     square = c;
-    product = ld_fq(tab, cnt, (size_t)sum_point(s, k + 1) * n + inst);
+    product = ld_fq(tab, cnt, (size_t)sum_point(pos.s, k + 1) * n + inst);
   }
   auto put = [&](int col, u64 v) { trace[(size_t)col * N + r] = v; };
   int al[16], bl[16], cl[16], t[16];
@@ -528,19 +385,7 @@ __global__ __launch_bounds__(64) void k_fq_rows(const u64* __restrict__ scalars,
 #pragma unroll
   for (int i = 0; i < 16; i++) diff[i] -= (long long)cl[i];
   gen_modulus_zero(diff, mz_slots, trace, N, r, L::AUX, err);
-  for (int i = 0; i < 256; i++) {
-    int src = (i + k) & 255;
-    put(L::BITS + i, (s[src >> 6] >> (src & 63)) & 1);
-  }
-  put(L::FLAGS + 0, row == 0);
-  put(L::FLAGS + 1, row == 511);
-  put(L::FLAGS + 2, (u64)row);
-  put(L::FLAGS + 3, rf_tbl[row]);
-  put(L::FLAGS + 4, rf_tbl[512 + row]);
-  put(L::TIMESTAMP, (u64)inst);
-  put(L::IS_ADDING, mul_step ? 1 : 0);
-  put(L::IDNL, mul_step ? 0 : (row == 511 ? 0 : 1));
-  put(L::FILTER, 1);
+  put_schedule<L>(trace, N, r, pos, rf_tbl);
 }
 
 __global__ void k_fq_outputs(const u64* __restrict__ scalars, int n, const u64* __restrict__ tab, u64* __restrict__ out4) {
@@ -553,14 +398,19 @@ __global__ void k_fq_outputs(const u64* __restrict__ scalars, int n, const u64* 
   for (int i = 0; i < 4; i++) out4[4 * inst + i] = v.l[i];
 }
 
-size_t fq_trace_scratch_words(size_t n) { return 4 * (size_t)NPTS * n + 1024 + 65536 / 2; }
+// word offsets of the arrays in the scratch buffer: the table of k_fq_chain, then the tail all kinds have
+struct FqScratch : ScratchCarve {
+  size_t tab, rf, hist;
+  explicit FqScratch(size_t n) { tab = take(4 * (size_t)NPTS * n), rf = take(RF_WORDS), hist = take(HIST_WORDS); }
+};
+size_t fq_trace_scratch_words(size_t n) { return FqScratch(n).words; }
 
 int fq_generate_trace_device(const u64* d_scalars, const u64* d_x, size_t n, u64* d_trace, size_t N, u64* d_scratch,
                              u64* d_outputs, int* d_err, hipStream_t st, bool with_range) {
-  size_t cnt = (size_t)NPTS * n, nrows = n * 512;
-  u64* tab = d_scratch;
-  u64* rf = tab + 4 * cnt;
-  u32* hist = (u32*)(rf + 1024);
+  const size_t nrows = n * 512;
+  const FqScratch sc(n);
+  u64 *tab = d_scratch + sc.tab, *rf = d_scratch + sc.rf;
+  u32* hist = (u32*)(d_scratch + sc.hist);
   if (nrows < N) hipMemsetAsync(d_trace, 0, (size_t)FQL::W * N * 8, st);
   launch_round_flag_table(rf, st);
   k_fq_chain<<<(unsigned)((n + 63) / 64), 64, 0, st>>>(d_scalars, d_x, (int)n, tab);

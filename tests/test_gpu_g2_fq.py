@@ -71,6 +71,25 @@ def test_g2_trace_matches_oracle(gpu_ctx, oracle):
         assert synth.g2_from_words(got_out[i]) == exp
 
 
+def test_g2_trace_rejects_opposite_points(gpu_ctx, oracle):
+    """The G2 twin of test_trace_rejects_opposite_points: offset == -x makes the first addition of instance 1 hit the point
+    at infinity, which the reference cannot prove (g2/add.rs); the running-sum scan both curves share reports
+    BN254S_E_INVALID_POINT.  The context stays usable: the same two instances with a valid offset match the oracle cell by
+    cell.  (n = 2 also leaves six of the eight lane groups of the cooperative G2 doubling chain idle.)"""
+    s, x, o = synth.g2_inputs(2, seed=5)
+    good = o.copy()
+    o[1, :8] = x[1, :8]
+    for c in (8, 12):                  # -y = (p - y.c0, p - y.c1)
+        o[1, c:c + 4] = synth._to_words((synth.P - synth.words_to_int(x[1, c:c + 4])) % synth.P)
+    with pytest.raises(RuntimeError, match="-4"):
+        gpu_ctx.generate_trace(1, s, x, o)
+    ref, ref_out = oracle_lib.generate_trace(oracle, 1, s, x, good)
+    got, got_out = gpu_ctx.generate_trace(1, s, x, good)
+    bad = np.argwhere(got != ref)
+    assert bad.size == 0, f"first mismatches (col,row): {bad[:10].tolist()}"
+    assert np.array_equal(got_out, ref_out)
+
+
 def test_fq_trace_matches_oracle(gpu_ctx, oracle):
     s, x = fq_edge_inputs()
     ref, ref_out = oracle_lib.generate_trace(oracle, 2, s, x)
