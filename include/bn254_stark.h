@@ -575,6 +575,34 @@ int bn254s_selftest_fri_combine(bn254s_ctx* ctx, int mode, int W, int n_rc, int 
 int bn254s_selftest_fri_fold(bn254s_ctx* ctx, const uint64_t* in, int log_m, uint64_t shift, const uint64_t beta[2], uint64_t* out);
 int bn254s_selftest_fri_rows(bn254s_ctx* ctx, const uint64_t* lde, int ncols, int log_n, int h, size_t k0, size_t rows,
                              const uint32_t* indices, int nq, uint64_t* window, uint64_t* gathered);
+/* Debug: the NTT / LDE stage at every supported height on caller data (csrc/ntt_selftest.hip).  All buffers are host memory and
+ * every word must be canonical.  BN254S_E_INVALID_ARG: a NULL argument, a size or combination outside what is stated below, a word
+ * of p or more; nothing is launched then.
+ *
+ * bn254s_selftest_transforms runs the transform dispatch of the provers (csrc/transforms.h) with the plan of a proof of 2^log_n
+ *   rows, 16 <= log_n <= 23, on ncols columns (1 .. 64).  flags: bit 0 = the radix-2 split level above the tall transforms
+ *   (18 <= log_n <= 23; log_n = 23 exists only with it), bit 1 = the compact workspace (column chunks of 16; log_n >= 17).
+ *   N = 2^log_n.  Coefficients are in the STORED layout of that plan: natural order at 2^16 rows; tall (R = N / 2^16 > 1):
+ *   coefficient k1 + R k2 at position k1 2^16 + k2; split: a column is [Pe | Po], the even and the odd coefficients, each in the
+ *   tall layout of N / 2 words.  An LDE column is 2 N words in leaf order: coset h (shift g w_2N^h) at h N + bitrev(k).
+ *     op 0  commit_ntt: in = values[ncols][N] -> out0 = coeffs[ncols][N], out1 = lde[ncols][2 N]
+ *     op 1  lde: in = coeffs[ncols][N] -> out0 = lde[ncols][2 N] (out1 unused, as for ops 2 and 3); with the compact flag and
+ *           without the split level ncols <= 16: lde does not work in chunks there and the plan's scratch holds one chunk
+ *     op 2  lde_chunk of the streaming workspace (log_n >= 17, ncols <= 16): as op 1 for the cosets of coset_mask (1, 2 or 3: bit h =
+ *           coset h); the output is filled with the word 2^64 - 1 first, a half that the mask leaves out keeps it
+ *     op 3  quotient_coset_inverse (ncols = 4): in = qv[2][2][N], values of polynomial a on coset h in natural order at [a][h]
+ *           -> out0 = ab[2][2][N], their interpolants' coefficients
+ *   coset_mask is ignored by the other ops.  The transforms run on the context's stream WITHOUT the section that keeps the NTT
+ *   stages of proofs in flight apart, and in scratch of the context: do not call it while proofs run on the same context.
+ * bn254s_selftest_mul_2exp: x[n], 1 <= n <= 2^20 -> out[n][64], out[i][e] = x[i] 2^(3 e) mod p by the shift table of the outer
+ *   passes (mul_2exp3, every e a compile-time constant as in the R-point DFT).
+ * bn254s_selftest_outer_dft: in[n][R], R = 2^log_r, 1 <= log_r <= 6, 1 <= n <= 2^16, inverse in {0, 1} -> out[n][R] = the registers
+ *   of dft_small<log_r, inverse> on each row in register order: register r holds X[bitrev(r)], X[k] = sum_i x[i] w^(i k) with
+ *   w = 2^(192 / R) (inverse: its inverse; no factor 1 / R). */
+int bn254s_selftest_transforms(bn254s_ctx* ctx, int op, int log_n, int flags, int ncols, int coset_mask, const uint64_t* in,
+                               uint64_t* out0, uint64_t* out1);
+int bn254s_selftest_mul_2exp(bn254s_ctx* ctx, const uint64_t* x, size_t n, uint64_t* out);
+int bn254s_selftest_outer_dft(bn254s_ctx* ctx, int log_r, int inverse, const uint64_t* in, size_t n, uint64_t* out);
 /* Debug: the parts of bn254s_verify_batch on caller data (csrc/verify_batch.hip, csrc/verify_query.h).
  * The FRONT RECORD of a proof is BN254S_VERIFY_RECORD_HEAD + num_queries words: fri_alpha (2 words: c0, c1), reduced[3] (6),
  * alpha_len[3] (6), zeta (2), g zeta (2), fri_betas[8] (16, zero past the last layer), then the query indices.

@@ -21,7 +21,6 @@ void ntt_coset_inverse(const NttTables* T, int h, const u64* values, u64* coeffs
 void ntt_lde(const NttTables* T, const u64* coeffs, u64* lde, u64* tmp, int ncols, hipStream_t s);
 // from_values in one go (iNTT + both coset NTTs, middle passes fused): tmp[C][N], tmp2[2][C][N]; values == coeffs allowed
 void ntt_inverse_lde(const NttTables* T, const u64* values, u64* coeffs, u64* lde, u64* tmp, u64* tmp2, int ncols, hipStream_t s);
-void ntt_coset_forward_natural(const NttTables* T, int h, const u64* coeffs, u64* values, u64* tmp, int ncols, hipStream_t s);
 
 // ---- N = R * 2^16 (tall traces) ---------------------------------------------------------------------------------
 struct NttTallTables {
@@ -62,3 +61,6 @@ void ntt_coset_inverse_split(const NttTables* T, const NttTallTables* TT, const 
 // debug: runs the hand-written field sequences of gl_asm.h on n operand pairs (bn254s_selftest_field)
 static constexpr int FIELD_SELFTEST_OUTS = 17;
 void field_selftest(const u64* a, const u64* b, u64* out, size_t n, hipStream_t s);
+// debug: the shift table and the R-point DFT of the outer passes on caller data (bn254s_selftest_mul_2exp, _outer_dft)
+void mul_2exp_selftest(const u64* x, u64* out, size_t n, hipStream_t s);                                   // out[n][64]
+void outer_dft_selftest(int log_r, bool inverse, const u64* in, u64* out, size_t n, hipStream_t s);       // in, out [n][2^log_r], 1 <= log_r <= 6

@@ -380,12 +380,6 @@ void ntt_inverse_lde(const NttTables* T, const u64* values, u64* coeffs, u64* ld
   k_ntt_pass2<false, true><<<grid, block, 0, s>>>(y0, NTT_N, lde, 2 * NTT_N, nullptr, 1, T->tw256_fwd, 0);
   k_ntt_pass2<false, true><<<grid, block, 0, s>>>(y1, NTT_N, lde + NTT_N, 2 * NTT_N, nullptr, 1, T->tw256_fwd, 0);
 }
-// forward coset NTT on coset h, natural output (used for small FRI-side transforms and tests)
-void ntt_coset_forward_natural(const NttTables* T, int h, const u64* coeffs, u64* values, u64* tmp, int ncols, hipStream_t s) {
-  dim3 grid(16, ncols), block(256);
-  k_ntt_pass1<false><<<grid, block, 0, s>>>(coeffs, NTT_N, tmp, NTT_N, T->coset_pow[h], T->twmat_fwd, T->tw256_fwd, 0);
-  k_ntt_pass2<false, false><<<grid, block, 0, s>>>(tmp, NTT_N, values, NTT_N, nullptr, 1, T->tw256_fwd, 0);
-}
 
 
 // ---- traces taller than 2^16 rows: N = R * 2^16, R = 2^log_r <= 64 -----------------------------------------------
@@ -823,6 +817,49 @@ __global__ void k_field_selftest(const u64* __restrict__ a, const u64* __restric
 }
 void field_selftest(const u64* a, const u64* b, u64* out, size_t n, hipStream_t s) {
   k_field_selftest<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(a, b, out, n);
+}
+
+// ---- self tests of the outer passes' building blocks (bn254s_selftest_mul_2exp, _outer_dft) ---------------------------------
+// out[i][e] = mul_2exp3(x[i], e): the loop unrolls, every call site has its constant e as in dft_small
+__global__ __launch_bounds__(256) void k_mul_2exp_selftest(const u64* __restrict__ x, u64* __restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u64 v = x[i];
+  u64* o = out + i * 64;
+#pragma unroll
+  for (int e = 0; e < 64; e++) o[e] = mul_2exp3(v, e);
+}
+void mul_2exp_selftest(const u64* x, u64* out, size_t n, hipStream_t s) {
+  k_mul_2exp_selftest<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(x, out, n);
+}
+// one lane per row of R = 2^LOGR words: dft_small on the row, the registers written out in register order
+template <int LOGR, bool INV>
+__global__ __launch_bounds__(256) void k_outer_dft_selftest(const u64* __restrict__ in, u64* __restrict__ out, size_t n) {
+  constexpr int R = 1 << LOGR;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u64 x[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) x[r] = in[i * R + r];
+  dft_small<LOGR, INV>(x);
+#pragma unroll
+  for (int r = 0; r < R; r++) out[i * R + r] = x[r];
+}
+template <int LOGR>
+static void outer_dft_selftest_launch(bool inverse, const u64* in, u64* out, size_t n, hipStream_t s) {
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  if (inverse) k_outer_dft_selftest<LOGR, true><<<blocks, 256, 0, s>>>(in, out, n);
+  else k_outer_dft_selftest<LOGR, false><<<blocks, 256, 0, s>>>(in, out, n);
+}
+void outer_dft_selftest(int log_r, bool inverse, const u64* in, u64* out, size_t n, hipStream_t s) {
+  switch (log_r) {
+    case 1: outer_dft_selftest_launch<1>(inverse, in, out, n, s); break;
+    case 2: outer_dft_selftest_launch<2>(inverse, in, out, n, s); break;
+    case 3: outer_dft_selftest_launch<3>(inverse, in, out, n, s); break;
+    case 4: outer_dft_selftest_launch<4>(inverse, in, out, n, s); break;
+    case 5: outer_dft_selftest_launch<5>(inverse, in, out, n, s); break;
+    default: outer_dft_selftest_launch<6>(inverse, in, out, n, s); break;
+  }
 }
 
 // loads this translation unit's code object (the HIP runtime defers that to the first launch otherwise)

@@ -86,8 +86,7 @@ int proof_plan(int kind, size_t n, const bn254s_params& P, size_t dev_total_byte
   b.tvals = lowmem && !stream ? std::max((size_t)W * N, (size_t)A * M2) : (size_t)W * N;
   b.tcoef = (size_t)W * N;
   b.hist = 65536 / 2;
-  // [tmp | y0 | y1] for the fused commitment; one tmp for a tall one; [E,O LDEs | tmp] of one column chunk under the split level
-  b.tmp = log_s ? (size_t)3 * CH * N : lowmem ? (size_t)CH * N : (size_t)(log_r ? 1 : 3) * std::max(W, A) * N;
+  b.tmp = pl.ntt_tmp_words(std::max(W, A));
   b.ldechunk = stream ? (size_t)CH * M2 : 0;  // the LDE of one column chunk
   b.sponge = stream ? (size_t)12 * M2 : 0;    // sponge states of the streaming leaf hash
   b.comb = (size_t)6 * N + (size_t)6 * M2;    // FRI batch polynomial: coefficients | LDE

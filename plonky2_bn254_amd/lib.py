@@ -126,6 +126,10 @@ def load_library():
         lib.bn254s_selftest_fri_combine.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp]
         lib.bn254s_selftest_fri_fold.argtypes = [vp, vp, C.c_int, C.c_uint64, vp, vp]
         lib.bn254s_selftest_fri_rows.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, vp, C.c_int, vp, vp]
+    if hasattr(lib, "bn254s_selftest_transforms"):   # (likewise; the three entry points of csrc/ntt_selftest.hip come together)
+        lib.bn254s_selftest_transforms.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+        lib.bn254s_selftest_mul_2exp.argtypes = [vp, vp, C.c_size_t, vp]
+        lib.bn254s_selftest_outer_dft.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, vp]
     if hasattr(lib, "bn254s_selftest_proof_plan"):   # (likewise)
         lib.bn254s_selftest_proof_plan.argtypes = [C.c_int, C.c_size_t, C.POINTER(Params), C.c_uint64, C.c_int, C.c_int, C.c_int,
                                                    C.c_int, vp, C.c_char_p, C.c_size_t]
@@ -800,6 +804,40 @@ class Context:
                                                        idx.ctypes.data_as(C.c_void_p), idx.shape[0], _ptr(win), _ptr(gat)),
                     "bn254s_selftest_fri_rows")
         return win, gat
+
+    # The NTT / LDE stage at every height on caller data (csrc/ntt_selftest.hip; include/bn254_stark.h has the layouts).
+    TRANSFORM_SPLIT, TRANSFORM_COMPACT = 1, 2   # flags of selftest_transforms
+
+    def selftest_transforms(self, op: int, log_n: int, flags: int, data: np.ndarray, coset_mask: int = 3):
+        """Debug: the provers' transform dispatch for a proof of 2^log_n rows on data[ncols][2^log_n]: op 0 values -> (coeffs, lde),
+        1 coeffs -> lde, 2 coeffs -> lde of the cosets in coset_mask (the rest stays 2^64 - 1), 3 qv[4][N] -> ab[4][N]
+        (bn254s_selftest_transforms)."""
+        data = np.ascontiguousarray(data, dtype=np.uint64)
+        ncols, n = data.shape
+        assert n == 1 << log_n, (n, log_n)
+        out0 = np.zeros((ncols, n if op in (0, 3) else 2 * n), np.uint64)
+        out1 = np.zeros((ncols, 2 * n), np.uint64) if op == 0 else None
+        self._check(self._lib.bn254s_selftest_transforms(self._h, op, log_n, flags, ncols, coset_mask, _ptr(data), _ptr(out0),
+                                                         _ptr(out1)), "bn254s_selftest_transforms")
+        return (out0, out1) if op == 0 else out0
+
+    def selftest_mul_2exp(self, x: np.ndarray) -> np.ndarray:
+        """Debug: x[n] -> out[n][64], out[i][e] = x[i] 2^(3 e) mod p by the shift table of the outer NTT passes
+        (bn254s_selftest_mul_2exp)."""
+        x = np.ascontiguousarray(x, dtype=np.uint64)
+        out = np.zeros((x.shape[0], 64), np.uint64)
+        self._check(self._lib.bn254s_selftest_mul_2exp(self._h, _ptr(x), x.shape[0], _ptr(out)), "bn254s_selftest_mul_2exp")
+        return out
+
+    def selftest_outer_dft(self, log_r: int, inverse: bool, rows: np.ndarray) -> np.ndarray:
+        """Debug: rows[n][2^log_r] -> the registers of the outer passes' R-point DFT on each row, in register order
+        (bn254s_selftest_outer_dft)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        assert rows.ndim == 2 and rows.shape[1] == 1 << log_r, (rows.shape, log_r)
+        out = np.zeros_like(rows)
+        self._check(self._lib.bn254s_selftest_outer_dft(self._h, log_r, int(inverse), _ptr(rows), rows.shape[0], _ptr(out)),
+                    "bn254s_selftest_outer_dft")
+        return out
 
     def poseidon_permute(self, states: np.ndarray) -> np.ndarray:
         st = np.ascontiguousarray(states, dtype=np.uint64).copy()
