@@ -74,7 +74,9 @@ int bn254s_ctx_create(int device_id, bn254s_ctx** out) {
     delete c;
     return BN254S_E_HIP;
   }
-  if (ntt_tables_init(&c->ntt) != 0) {
+  if (ntt_tables_init(&c->ntt) != 0 || !c->ntt_plan(16, false)) {
+    ntt_tables_free(&c->ntt);
+    hipStreamDestroy(c->stream);
     delete c;
     return BN254S_E_OOM;
   }
@@ -114,14 +116,7 @@ void bn254s_ctx_destroy(bn254s_ctx* c) {
     hipStreamDestroy(s->st);
     delete s;
   }
-  for (auto& kv : c->tall) {
-    ntt_tall_tables_free(kv.second);
-    delete kv.second;
-  }
-  for (auto& kv : c->split) {
-    ntt_split_tables_free(kv.second);
-    delete kv.second;
-  }
+  for (auto& kv : c->plans) ntt_plan_free(&kv.second);
   c->release();
   ntt_tables_free(&c->ntt);
   hipStreamDestroy(c->stream);
@@ -161,12 +156,12 @@ int bn254s_commit_values(bn254s_ctx* c, const uint64_t* values, size_t ncols, ui
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t N = NTT_N;
   u64* d_vals = c->words("cv.vals", ncols * N);
-  u64* d_tmp = c->words("cv.tmp", 3 * ncols * N);
+  u64* d_tmp = c->words("cv.tmp", ntt_scratch_words(16, false, (int)ncols));
   u64* d_lde = c->words("cv.lde", ncols * 2 * N);
   u64* d_tree = c->words("cv.tree", merkle_tree_digests(17, 4) * 4);
   if (!d_vals || !d_tmp || !d_lde || !d_tree) return BN254S_E_OOM;
   HIP_TRY(c, hipMemcpyAsync(d_vals, values, ncols * N * 8, hipMemcpyHostToDevice, c->stream));
-  ntt_inverse_lde(&c->ntt, d_vals, d_vals, d_lde, d_tmp, d_tmp + ncols * N, (int)ncols, c->stream);
+  ntt_commit(*c->ntt_plan(16, false), d_vals, d_vals, d_lde, 2 * N, d_tmp, (int)ncols, c->stream);
   merkle_build(d_lde, 1, 2 * N, (int)ncols, 17, 4, d_tree, c->stream);
   HIP_TRY(c, hipGetLastError());
   if (coeffs) HIP_TRY(c, hipMemcpyAsync(coeffs, d_vals, ncols * N * 8, hipMemcpyDeviceToHost, c->stream));
@@ -192,7 +187,7 @@ int bn254s_bench_ntt(bn254s_ctx* c, size_t ncols, int iters, float* ms) {
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t N = NTT_N;
   u64* d_vals = c->words("cv.vals", ncols * N);
-  u64* d_tmp = c->words("cv.tmp", 3 * ncols * N);
+  u64* d_tmp = c->words("cv.tmp", ntt_scratch_words(16, false, (int)ncols));
   u64* d_lde = c->words("cv.lde", ncols * 2 * N);
   if (!d_vals || !d_tmp || !d_lde) return BN254S_E_OOM;
   size_t n = ncols * N;
@@ -200,10 +195,11 @@ int bn254s_bench_ntt(bn254s_ctx* c, size_t ncols, int iters, float* ms) {
   hipEvent_t e0, e1;
   HIP_TRY(c, hipEventCreate(&e0));
   HIP_TRY(c, hipEventCreate(&e1));
+  const NttPlan& np = *c->ntt_plan(16, false);
   // warm-up
-  ntt_inverse_lde(&c->ntt, d_vals, d_vals, d_lde, d_tmp, d_tmp + n, (int)ncols, c->stream);
+  ntt_commit(np, d_vals, d_vals, d_lde, 2 * N, d_tmp, (int)ncols, c->stream);
   HIP_TRY(c, hipEventRecord(e0, c->stream));
-  for (int it = 0; it < iters; it++) ntt_inverse_lde(&c->ntt, d_vals, d_vals, d_lde, d_tmp, d_tmp + n, (int)ncols, c->stream);
+  for (int it = 0; it < iters; it++) ntt_commit(np, d_vals, d_vals, d_lde, 2 * N, d_tmp, (int)ncols, c->stream);
   HIP_TRY(c, hipEventRecord(e1, c->stream));
   HIP_TRY(c, hipEventSynchronize(e1));
   float t = 0;

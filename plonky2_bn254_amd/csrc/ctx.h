@@ -177,8 +177,18 @@ struct bn254s_ctx : BufPool {
   NttTables ntt;
   std::vector<Slot*> slots;
   WorkPool workers;
-  std::map<unsigned, NttTallTables*> tall;  // per log_n (+100: halves of a split transform)
-  std::map<unsigned, NttSplitTables*> split;  // per log_n
+  // The transform plan of a trace height (and of its split form), built on first use and kept; nullptr: the tables did not fit.
+  std::mutex plans_mu;
+  std::map<std::pair<unsigned, bool>, NttPlan> plans;  // per (log_n, split); map nodes do not move
+  const NttPlan* ntt_plan(unsigned log_n, bool split) {
+    std::lock_guard<std::mutex> lk(plans_mu);
+    const auto key = std::make_pair(log_n, split);
+    auto it = plans.find(key);
+    if (it != plans.end()) return &it->second;
+    NttPlan p;
+    if (ntt_plan_init(&p, &ntt, log_n, split) != 0) return nullptr;
+    return &(plans[key] = p);
+  }
   // The GPU-filling sections of the proofs in flight take turns through the semaphore below; latency-bound kernels
   // (doubling chain, upper Merkle levels, scans, PoW, FRI folds) run outside it and overlap freely.
   std::mutex big_mu;

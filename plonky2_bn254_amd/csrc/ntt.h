@@ -14,15 +14,10 @@ struct NttTables {
   u64 n_inv = 0;
 };
 
-int ntt_tables_init(NttTables* T);
+int ntt_tables_init(NttTables* T);  // frees what it allocated when it fails
 void ntt_tables_free(NttTables* T);
-void ntt_inverse(const NttTables* T, const u64* values, u64* coeffs, u64* tmp, int ncols, hipStream_t s);
-void ntt_coset_inverse(const NttTables* T, int h, const u64* values, u64* coeffs, u64* tmp, int ncols, hipStream_t s);
-void ntt_lde(const NttTables* T, const u64* coeffs, u64* lde, u64* tmp, int ncols, hipStream_t s);
-// from_values in one go (iNTT + both coset NTTs, middle passes fused): tmp[C][N], tmp2[2][C][N]; values == coeffs allowed
-void ntt_inverse_lde(const NttTables* T, const u64* values, u64* coeffs, u64* lde, u64* tmp, u64* tmp2, int ncols, hipStream_t s);
 
-// ---- N = R * 2^16 (tall traces) ---------------------------------------------------------------------------------
+// N = R * 2^16 (tall traces): the tables of the outer pass over the R blocks of a column
 struct NttTallTables {
   unsigned log_n = 0;
   u64* wn_inv_pow = nullptr;              // w_N^-i2, i2 < 2^16
@@ -31,32 +26,37 @@ struct NttTallTables {
   u64 shift[2] = {0, 0};                  // g, g*w_2N
   u64 r_inv = 0;
 };
-int ntt_tall_tables_init(NttTallTables* T, unsigned log_n, u64 base_shift = GL_GEN);
-void ntt_tall_tables_free(NttTallTables* T);
-// Coefficients live in the "transposed" layout: coefficient k1 + R*k2 at position k1*2^16 + k2.
-void ntt_inverse_tall(const NttTables* T, const NttTallTables* TT, const u64* values, u64* coeffs, u64* tmp, int ncols,
-                      hipStream_t s);
-void ntt_coset_inverse_tall(const NttTables* T, const NttTallTables* TT, int h, const u64* values, u64* coeffs, u64* tmp, int ncols,
-                            hipStream_t s);
-void ntt_inverse_lde_tall(const NttTables* T, const NttTallTables* TT, const u64* values, u64* coeffs, u64* lde, u64* tmp, int ncols,
-                          hipStream_t s);
-// coset_mask: bit h set = compute coset h (the lower / upper half of the bit-reversed output); 3 = both
-void ntt_lde_tall(const NttTables* T, const NttTallTables* TT, const u64* coeffs, u64* lde, u64* tmp, int ncols, hipStream_t s,
-                  int coset_mask = 3);
-
-// ---- N = 2^23: one radix-2 level above the tall transforms (see ntt.hip) ---------------------------------------------
+// one radix-2 level above the tall transforms (2^23 rows; see ntt.hip)
 struct NttSplitTables {
   unsigned log_n = 0;
   u64 *fwd_lo = nullptr, *fwd_hi = nullptr, *inv_lo = nullptr, *inv_hi = nullptr;  // w_N^(+-b), w_N^(+-2048 a)
   u64 shift[2] = {0, 0};  // g, g*w_2N
   u64 half = 0;
 };
-int ntt_split_tables_init(NttSplitTables* S, unsigned log_n);
-void ntt_split_tables_free(NttSplitTables* S);
-void ntt_split_inverse(const NttSplitTables* S, const u64* values, u64* halves, int ncols, hipStream_t s);
-void ntt_split_forward(const NttSplitTables* S, const u64* eo, u64* lde, size_t lde_stride, int ncols, hipStream_t s, int coset_mask = 3);
-void ntt_coset_inverse_split(const NttTables* T, const NttTallTables* TT, const NttSplitTables* S, int h, const u64* values, u64* coeffs,
-                             u64* tmp, int ncols, hipStream_t s);
+
+// Everything the transforms of one trace height need.  2^16 rows: the four-step kernels on `base`; taller: an outer pass over
+// R = 2^log_r blocks (coefficient k1 + R*k2 is stored at k1*2^16 + k2, the "transposed" layout); log_s = 1: one radix-2 level above
+// that, a column of coefficients then holds the two halves [Pe | Po] of N/2 words, each in the transposed layout.
+struct NttPlan {
+  unsigned log_n = 0, log_s = 0, log_r = 0;  // log_r = log_n - 16 - log_s
+  const NttTables* base = nullptr;           // the context's 2^16 tables
+  NttTallTables tall;                        // used iff log_r (under the split level: of the halves, cosets g^2, g^2 w_N)
+  NttSplitTables split;                      // used iff log_s
+};
+int ntt_plan_init(NttPlan* P, const NttTables* base, unsigned log_n, bool split);  // frees what it allocated when it fails
+void ntt_plan_free(NttPlan* P);
+// words of `scratch` below for ncols columns (host arithmetic only): [tmp | y0 | y1] of the fused commitment at 2^16 rows, one tmp
+// for a tall transform, [E, O LDEs | tmp] under the split level
+size_t ntt_scratch_words(unsigned log_n, bool split, int ncols);
+// lde: [C][lde_stride] in bit-reversed order (both cosets).  lde_stride is 2 N except under the split level, whose last kernel
+// writes rows of any stride.  coset_mask: bit h set = compute coset h (the lower / upper half of the output); 3 = both (the only
+// value at 2^16 rows).
+// from_values: values[C][N] -> stored coefficients[C][N] and their LDE; values == coef allowed
+void ntt_commit(const NttPlan& P, const u64* vals, u64* coef, u64* lde, size_t lde_stride, u64* scratch, int ncols, hipStream_t s);
+// stored coefficients[C][N] -> LDE
+void ntt_lde(const NttPlan& P, const u64* coef, u64* lde, size_t lde_stride, u64* scratch, int ncols, hipStream_t s, int coset_mask = 3);
+// values on coset h (natural order) -> stored coefficients of the interpolant
+void ntt_coset_inverse(const NttPlan& P, int h, const u64* vals, u64* coef, u64* scratch, int ncols, hipStream_t s);
 
 // debug: runs the hand-written field sequences of gl_asm.h on n operand pairs (bn254s_selftest_field)
 static constexpr int FIELD_SELFTEST_OUTS = 17;

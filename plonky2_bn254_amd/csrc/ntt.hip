@@ -17,6 +17,12 @@
 // no bit-reversal pass exist.  Global accesses are 128-byte segments (16 lanes x 8 B), or 1 KB per store
 // instruction where the output is staged through LDS; twiddle / coset tables have the same access pattern
 // as the data and stay L2-resident.  The arithmetic is the hand-written code of gl_asm.h.
+//
+// Host side: ntt.h.  The kernels come in three groups (2^16 rows; the outer pass of taller traces; one radix-2 level above that),
+// each followed by its tables and by static helpers that launch its sequences; the NttPlan of a height and the three operations
+// on it (ntt_commit, ntt_lde, ntt_coset_inverse) stand after the last group and are all that callers see.
+#include <cassert>
+#include <type_traits>
 #include "gl_dev.h"
 #include "gl_asm.h"
 #include "ntt.h"
@@ -78,18 +84,6 @@ template <bool INV, int MODE>
 __device__ __forceinline__ void dft256_tile(u64* x, u32* lds, const u64* __restrict__ tw256, int& d, int& g) {
   dft16<INV>(x);
   // inner twiddle w_256^(g*ka), then transpose (g <-> ka) through LDS
-#if defined(BN254S_NTT_AB) && BN254S_NTT_AB == 1
-  // TIMING-ONLY build (tools/gpu_ntt_ab.sh, wrong results): the inner twiddles of the pass-1 tiles dropped = the upper bound of
-  // what a 64 x 64 x 16 decomposition (one general twiddle layer fewer per transform) could save
-  if (MODE != 0)
-#endif
-#if defined(BN254S_NTT_AB) && BN254S_NTT_AB == 2
-  // TIMING-ONLY build: ... replaced by power-of-two twiddles (what a radix-64 stage would put there instead)
-  if (MODE == 0) {
-#pragma unroll
-    for (int ka = 1; ka < 16; ka++) x[br4(ka)] = (ka & 1) ? gl_shl_asm<36>(x[br4(ka)]) : gl_shl_asm<12>(x[br4(ka)]);
-  } else
-#endif
 #pragma unroll
   for (int ka = 1; ka < 16; ka++) x[br4(ka)] = gl_mul_asm(x[br4(ka)], tw256[g * ka]);
   int d2 = d, g2 = g;
@@ -289,14 +283,17 @@ static void fill_pow_table(std::vector<u64>& t, u64 base, size_t n, u64 first = 
   }
 }
 
-int ntt_tables_init(NttTables* T) {
+// One rule for the three table sets: a failed upload returns -1 and leaves what is allocated to the owner's free function, which
+// the init of the owner (ntt_tables_init, ntt_plan_init) calls before it reports the failure; the free functions take structs
+// that are partly or not at all filled (hipFree(nullptr) is a no-op) and leave them empty.
+static int upload(u64** dst, const std::vector<u64>& src) {
+  if (hipMalloc((void**)dst, src.size() * 8) != hipSuccess) return -1;
+  return hipMemcpy(*dst, src.data(), src.size() * 8, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+
+static int base_tables_fill(NttTables* T) {
   const size_t N = NTT_N;
   std::vector<u64> h;
-  auto upload = [&](u64** dst, const std::vector<u64>& src) -> int {
-    if (hipMalloc((void**)dst, src.size() * 8) != hipSuccess) return -1;
-    if (hipMemcpy(*dst, src.data(), src.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    return 0;
-  };
   u64 wN = gl_root_of_unity(16), wNi = gl_inv(wN);
   u64 w256 = gl_root_of_unity(8), w256i = gl_inv(w256);
   fill_pow_table(h, w256, 256);
@@ -336,7 +333,11 @@ int ntt_tables_init(NttTables* T) {
   T->n_inv = ninv;
   return 0;
 }
-
+int ntt_tables_init(NttTables* T) {
+  if (base_tables_fill(T) == 0) return 0;
+  ntt_tables_free(T);
+  return -1;
+}
 void ntt_tables_free(NttTables* T) {
   hipFree(T->tw256_fwd);
   hipFree(T->tw256_inv);
@@ -347,33 +348,29 @@ void ntt_tables_free(NttTables* T) {
     hipFree(T->coset_pow[h]);
     hipFree(T->coset_inv_pow[h]);
   }
+  *T = NttTables{};
 }
 
-// values[C][N] (natural) -> coefficients[C][N] (natural); in place allowed (uses tmp[C][N]).
-void ntt_inverse(const NttTables* T, const u64* values, u64* coeffs, u64* tmp, int ncols, hipStream_t s) {
-  dim3 grid(16, ncols), block(256);
-  k_ntt_pass1<true><<<grid, block, 0, s>>>(values, NTT_N, tmp, NTT_N, nullptr, T->twmat_inv, T->tw256_inv, 0);
-  k_ntt_pass2<true, false><<<grid, block, 0, s>>>(tmp, NTT_N, coeffs, NTT_N, nullptr, T->n_inv, T->tw256_inv, 0);
-}
+// The three operations at 2^16 rows; tmp[C][N].
 // coset iNTT of values given on coset `h` (natural order) -> coefficients (natural)
-void ntt_coset_inverse(const NttTables* T, int h, const u64* values, u64* coeffs, u64* tmp, int ncols, hipStream_t s) {
+static void coset_inverse_base(const NttTables* T, int h, const u64* values, u64* coeffs, u64* tmp, int ncols, hipStream_t s) {
   dim3 grid(16, ncols), block(256);
   k_ntt_pass1<true><<<grid, block, 0, s>>>(values, NTT_N, tmp, NTT_N, nullptr, T->twmat_inv, T->tw256_inv, 0);
   k_ntt_pass2<true, false><<<grid, block, 0, s>>>(tmp, NTT_N, coeffs, NTT_N, T->coset_inv_pow[h], 1, T->tw256_inv, 0);
 }
-// coefficients[C][N] -> lde[C][2N] in bit-reversed order (both cosets); tmp[C][N].
-void ntt_lde(const NttTables* T, const u64* coeffs, u64* lde, u64* tmp, int ncols, hipStream_t s) {
+// coefficients[C][N] -> lde[C][2N] in bit-reversed order (both cosets)
+static void lde_base(const NttTables* T, const u64* coeffs, u64* lde, u64* tmp, int ncols, hipStream_t s) {
   dim3 grid(16, ncols), block(256);
   for (int h = 0; h < 2; h++) {
     k_ntt_pass1<false><<<grid, block, 0, s>>>(coeffs, NTT_N, tmp, NTT_N, T->coset_pow[h], T->twmat_fwd, T->tw256_fwd, 0);
     k_ntt_pass2<false, true><<<grid, block, 0, s>>>(tmp, NTT_N, lde + (size_t)h * NTT_N, 2 * NTT_N, nullptr, 1, T->tw256_fwd, 0);
   }
 }
-// values[C][N] -> coefficients[C][N] and lde[C][2N] (bit-reversed) with the fused middle kernel; tmp[C][N], tmp2[2][C][N].
-void ntt_inverse_lde(const NttTables* T, const u64* values, u64* coeffs, u64* lde, u64* tmp, u64* tmp2, int ncols, hipStream_t s) {
+// values[C][N] -> coefficients[C][N] and lde[C][2N] (bit-reversed) with the fused middle kernel; tmp[3][C][N] = [tmp | y0 | y1]
+static void commit_base(const NttTables* T, const u64* values, u64* coeffs, u64* lde, u64* tmp, int ncols, hipStream_t s) {
   dim3 grid(16, ncols), block(256);
-  u64* y0 = tmp2;
-  u64* y1 = tmp2 + (size_t)ncols * NTT_N;
+  u64* y0 = tmp + (size_t)ncols * NTT_N;
+  u64* y1 = y0 + (size_t)ncols * NTT_N;
   k_ntt_pass1<true><<<grid, block, 0, s>>>(values, NTT_N, tmp, NTT_N, nullptr, T->twmat_inv_ninv, T->tw256_inv, 0);
   k_ntt_intt2_lde1<8><<<grid, block, 0, s>>>(tmp, NTT_N, coeffs, NTT_N, y0, y1, NTT_N, T->tw256_inv, T->coset_pow[0],
                                           T->coset_pow[1], T->twmat_fwd, T->tw256_fwd, 0);
@@ -560,15 +557,9 @@ __global__ __launch_bounds__(256) void k_coset_unscale(u64* __restrict__ c, size
   col[pos] = gl_mul(col[pos], gl_pow(shift_inv, k));
 }
 
-int ntt_tall_tables_init(NttTallTables* T, unsigned log_n, u64 base_shift) {
-  const unsigned log_r = log_n - 16;
-  const size_t N = (size_t)1 << log_n, R = (size_t)1 << log_r;
+static int tall_tables_init(NttTallTables* T, unsigned log_n, u64 base_shift) {
+  const size_t R = (size_t)1 << (log_n - 16);
   std::vector<u64> h;
-  auto upload = [&](u64** dst, const std::vector<u64>& src) -> int {
-    if (hipMalloc((void**)dst, src.size() * 8) != hipSuccess) return -1;
-    if (hipMemcpy(*dst, src.data(), src.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return -1;
-    return 0;
-  };
   T->log_n = log_n;
   const u64 wN = gl_root_of_unity(log_n), wNi = gl_inv(wN);
   fill_pow_table(h, wNi, NTT_N);
@@ -588,64 +579,64 @@ int ntt_tall_tables_init(NttTallTables* T, unsigned log_n, u64 base_shift) {
     if (upload(&T->block_coset_pow[hh], h)) return -1;
   }
   T->r_inv = gl_inv((u64)R);
-  (void)N;
   return 0;
 }
-void ntt_tall_tables_free(NttTallTables* T) {
+static void tall_tables_free(NttTallTables* T) {
   hipFree(T->wn_inv_pow);
   hipFree(T->wn_pow_br);
   hipFree(T->block_coset_pow[0]);
   hipFree(T->block_coset_pow[1]);
+  *T = NttTallTables{};
 }
 
-template <int LOGR>
-static void outer_inv_launch(const u64* in, u64* out, size_t N, const NttTallTables* TT, int ncols, hipStream_t s) {
-  k_ntt_outer_inv<LOGR><<<dim3(NTT_N / 256, ncols), 256, 0, s>>>(in, out, N, TT->wn_inv_pow, TT->r_inv);
+// f(std::integral_constant<int, LOGR>) for the run-time log_r (1 .. 6): the one place that picks a LOGR instantiation
+template <class F>
+static void with_logr(unsigned log_r, F f) {
+  switch (log_r) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    default: f(std::integral_constant<int, 6>{}); break;
+  }
 }
-template <int LOGR>
-static void outer_fwd_launch(const u64* z, size_t N, u64* out, size_t out_stride, const NttTallTables* TT, int h, int ncols,
-                             hipStream_t s) {
-  k_ntt_outer_fwd<LOGR><<<dim3(NTT_N / 256, ncols), 256, 0, s>>>(z, N, out, out_stride, TT->wn_pow_br, TT->shift[h]);
+static void outer_inv(const NttTallTables* TT, const u64* in, u64* out, int ncols, hipStream_t s) {
+  with_logr(TT->log_n - 16, [&](auto L) {
+    k_ntt_outer_inv<decltype(L)::value><<<dim3(NTT_N / 256, ncols), 256, 0, s>>>(in, out, (size_t)1 << TT->log_n, TT->wn_inv_pow, TT->r_inv);
+  });
+}
+// coset h: z[C][N] -> the half of [C][2 N] that starts at `half`
+static void outer_fwd(const NttTallTables* TT, int h, const u64* z, u64* half, int ncols, hipStream_t s) {
+  const size_t N = (size_t)1 << TT->log_n;
+  with_logr(TT->log_n - 16, [&](auto L) {
+    k_ntt_outer_fwd<decltype(L)::value><<<dim3(NTT_N / 256, ncols), 256, 0, s>>>(z, N, half, 2 * N, TT->wn_pow_br, TT->shift[h]);
+  });
 }
 
 // values[C][N] natural -> coefficients[C][N] in the transposed layout; may run in place; tmp[C][N].
-void ntt_inverse_tall(const NttTables* T, const NttTallTables* TT, const u64* values, u64* coeffs, u64* tmp, int ncols,
-                      hipStream_t s) {
+static void inverse_tall(const NttTables* T, const NttTallTables* TT, const u64* values, u64* coeffs, u64* tmp, int ncols, hipStream_t s) {
   const unsigned log_r = TT->log_n - 16;
   const size_t N = (size_t)1 << TT->log_n;
-  switch (log_r) {
-    case 1: outer_inv_launch<1>(values, coeffs, N, TT, ncols, s); break;
-    case 2: outer_inv_launch<2>(values, coeffs, N, TT, ncols, s); break;
-    case 3: outer_inv_launch<3>(values, coeffs, N, TT, ncols, s); break;
-    case 4: outer_inv_launch<4>(values, coeffs, N, TT, ncols, s); break;
-    case 5: outer_inv_launch<5>(values, coeffs, N, TT, ncols, s); break;
-    default: outer_inv_launch<6>(values, coeffs, N, TT, ncols, s); break;
-  }
+  outer_inv(TT, values, coeffs, ncols, s);
   dim3 grid(16, (unsigned)(ncols << log_r)), block(256);
   k_ntt_pass1<true><<<grid, block, 0, s>>>(coeffs, N, tmp, N, nullptr, T->twmat_inv, T->tw256_inv, log_r);
   k_ntt_pass2<true, false><<<grid, block, 0, s>>>(tmp, N, coeffs, N, nullptr, T->n_inv, T->tw256_inv, log_r);
 }
 // values on coset h (natural) -> transposed coefficients of the interpolant
-void ntt_coset_inverse_tall(const NttTables* T, const NttTallTables* TT, int h, const u64* values, u64* coeffs, u64* tmp, int ncols,
-                            hipStream_t s) {
-  ntt_inverse_tall(T, TT, values, coeffs, tmp, ncols, s);
+static void coset_inverse_tall(const NttTables* T, const NttTallTables* TT, int h, const u64* values, u64* coeffs, u64* tmp, int ncols,
+                               hipStream_t s) {
+  inverse_tall(T, TT, values, coeffs, tmp, ncols, s);
   const size_t N = (size_t)1 << TT->log_n;
   k_coset_unscale<<<dim3((unsigned)(N / 256), ncols), 256, 0, s>>>(coeffs, N, TT->log_n - 16, gl_inv(TT->shift[h]));
 }
 // from_values of a tall commitment: outer inverse pass, block iNTT pass 1, the fused middle kernel (its two pass-1 images go
 // straight into the two halves of the LDE buffer), then pass 2 + outer forward pass per coset.  values == coeffs allowed.
-void ntt_inverse_lde_tall(const NttTables* T, const NttTallTables* TT, const u64* values, u64* coeffs, u64* lde, u64* tmp, int ncols,
-                          hipStream_t s) {
+static void commit_tall(const NttTables* T, const NttTallTables* TT, const u64* values, u64* coeffs, u64* lde, u64* tmp, int ncols,
+                        hipStream_t s) {
   const unsigned log_r = TT->log_n - 16;
   const size_t N = (size_t)1 << TT->log_n;
-  switch (log_r) {
-    case 1: outer_inv_launch<1>(values, coeffs, N, TT, ncols, s); break;
-    case 2: outer_inv_launch<2>(values, coeffs, N, TT, ncols, s); break;
-    case 3: outer_inv_launch<3>(values, coeffs, N, TT, ncols, s); break;
-    case 4: outer_inv_launch<4>(values, coeffs, N, TT, ncols, s); break;
-    case 5: outer_inv_launch<5>(values, coeffs, N, TT, ncols, s); break;
-    default: outer_inv_launch<6>(values, coeffs, N, TT, ncols, s); break;
-  }
+  outer_inv(TT, values, coeffs, ncols, s);
   dim3 grid(16, (unsigned)(ncols << log_r)), block(256);
   k_ntt_pass1<true><<<grid, block, 0, s>>>(coeffs, N, tmp, N, nullptr, T->twmat_inv_ninv, T->tw256_inv, log_r);
   k_ntt_intt2_lde1<8><<<grid, block, 0, s>>>(tmp, N, coeffs, N, lde, lde + N, 2 * N, T->tw256_inv, TT->block_coset_pow[0],
@@ -653,19 +644,12 @@ void ntt_inverse_lde_tall(const NttTables* T, const NttTallTables* TT, const u64
   for (int h = 0; h < 2; h++) {
     u64* half = lde + (size_t)h * N;
     k_ntt_pass2<false, true><<<grid, block, 0, s>>>(half, 2 * N, tmp, N, nullptr, 1, T->tw256_fwd, log_r);
-    switch (log_r) {
-      case 1: outer_fwd_launch<1>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      case 2: outer_fwd_launch<2>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      case 3: outer_fwd_launch<3>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      case 4: outer_fwd_launch<4>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      case 5: outer_fwd_launch<5>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      default: outer_fwd_launch<6>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-    }
+    outer_fwd(TT, h, tmp, half, ncols, s);
   }
 }
 // transposed coefficients[C][N] -> lde[C][2N] bit-reversed; tmp[C][N].
-void ntt_lde_tall(const NttTables* T, const NttTallTables* TT, const u64* coeffs, u64* lde, u64* tmp, int ncols, hipStream_t s,
-                  int coset_mask) {
+static void lde_tall(const NttTables* T, const NttTallTables* TT, const u64* coeffs, u64* lde, u64* tmp, int ncols, hipStream_t s,
+                     int coset_mask) {
   const unsigned log_r = TT->log_n - 16;
   const size_t N = (size_t)1 << TT->log_n;
   dim3 grid(16, (unsigned)(ncols << log_r)), block(256);
@@ -674,14 +658,7 @@ void ntt_lde_tall(const NttTables* T, const NttTallTables* TT, const u64* coeffs
     u64* half = lde + (size_t)h * N;
     k_ntt_pass1<false><<<grid, block, 0, s>>>(coeffs, N, half, 2 * N, TT->block_coset_pow[h], T->twmat_fwd, T->tw256_fwd, log_r);
     k_ntt_pass2<false, true><<<grid, block, 0, s>>>(half, 2 * N, tmp, N, nullptr, 1, T->tw256_fwd, log_r);
-    switch (log_r) {
-      case 1: outer_fwd_launch<1>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      case 2: outer_fwd_launch<2>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      case 3: outer_fwd_launch<3>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      case 4: outer_fwd_launch<4>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      case 5: outer_fwd_launch<5>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-      default: outer_fwd_launch<6>(tmp, N, half, 2 * N, TT, h, ncols, s); break;
-    }
+    outer_fwd(TT, h, tmp, half, ncols, s);
   }
 }
 
@@ -727,26 +704,15 @@ __global__ __launch_bounds__(256) void k_coset_unscale_half(u64* __restrict__ c,
   col[pos] = gl_mul(col[pos], gl_pow(base_inv, k1 + (k2 << log_r)));
 }
 
-void ntt_split_tables_free(NttSplitTables* S);
-int ntt_split_tables_init(NttSplitTables* S, unsigned log_n) {
-  if (log_n < 18 || log_n > 23) return -1;  // e < 2^22 in split_pow
+static int split_tables_init(NttSplitTables* S, unsigned log_n) {
   S->log_n = log_n;
   const u64 w = gl_root_of_unity(log_n), wi = gl_inv(w);
   std::vector<u64> h;
-  auto upload = [&](u64** dst) -> int {
-    if (hipMalloc((void**)dst, h.size() * 8) != hipSuccess) return -1;
-    return hipMemcpy(*dst, h.data(), h.size() * 8, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-  };
-  S->fwd_lo = S->fwd_hi = S->inv_lo = S->inv_hi = nullptr;
   const u64 bases[4] = {w, gl_pow(w, 2048), wi, gl_pow(wi, 2048)};
   u64** dsts[4] = {&S->fwd_lo, &S->fwd_hi, &S->inv_lo, &S->inv_hi};
   for (int t = 0; t < 4; t++) {
     fill_pow_table(h, bases[t], 2048);
-    if (upload(dsts[t])) {
-      ntt_split_tables_free(S);  // the tables uploaded so far (hipFree(nullptr) is a no-op)
-      S->fwd_lo = S->fwd_hi = S->inv_lo = S->inv_hi = nullptr;
-      return -1;
-    }
+    if (upload(dsts[t], h)) return -1;
   }
   const u64 w2N = gl_root_of_unity(log_n + 1);
   S->shift[0] = GL_GEN;
@@ -754,19 +720,20 @@ int ntt_split_tables_init(NttSplitTables* S, unsigned log_n) {
   S->half = gl_inv(2);
   return 0;
 }
-void ntt_split_tables_free(NttSplitTables* S) {
+static void split_tables_free(NttSplitTables* S) {
   hipFree(S->fwd_lo);
   hipFree(S->fwd_hi);
   hipFree(S->inv_lo);
   hipFree(S->inv_hi);
+  *S = NttSplitTables{};
 }
-// values[C][N] -> halves (in place allowed); the caller then runs the tall routines on 2 C columns of H words
-void ntt_split_inverse(const NttSplitTables* S, const u64* values, u64* halves, int ncols, hipStream_t s) {
+// values[C][N] -> halves (in place allowed); the tall routines then run on 2 C columns of H words
+static void split_inverse(const NttSplitTables* S, const u64* values, u64* halves, int ncols, hipStream_t s) {
   const size_t N = (size_t)1 << S->log_n;
   k_split_inv<<<dim3((unsigned)(N / 512), ncols), 256, 0, s>>>(values, halves, N, S->inv_hi, S->inv_lo, S->half, S->half);
 }
-// eo[C][2][N] (bit-reversed LDEs of the two halves of each column) -> lde[C][2N] bit-reversed
-void ntt_split_forward(const NttSplitTables* S, const u64* eo, u64* lde, size_t lde_stride, int ncols, hipStream_t s, int coset_mask) {
+// eo[C][2][N] (bit-reversed LDEs of the two halves of each column) -> lde[C][lde_stride] bit-reversed
+static void split_forward(const NttSplitTables* S, const u64* eo, u64* lde, size_t lde_stride, int ncols, hipStream_t s, int coset_mask) {
   const size_t N = (size_t)1 << S->log_n, H = N >> 1;
   if (coset_mask == 3) {
     k_split_fwd<<<dim3((unsigned)(N / 256), ncols), 256, 0, s>>>(eo, lde, N, S->log_n - 1, lde_stride, S->fwd_hi, S->fwd_lo, S->shift[0], S->shift[1], 0);
@@ -777,14 +744,64 @@ void ntt_split_forward(const NttSplitTables* S, const u64* eo, u64* lde, size_t 
                                                              (size_t)h * H);
 }
 // values on coset h of the N-point domain (natural order) -> the halves of the interpolant's coefficients; TT = tall tables of H
-void ntt_coset_inverse_split(const NttTables* T, const NttTallTables* TT, const NttSplitTables* S, int h, const u64* values, u64* coeffs,
-                             u64* tmp, int ncols, hipStream_t s) {
+static void coset_inverse_split(const NttTables* T, const NttTallTables* TT, const NttSplitTables* S, int h, const u64* values, u64* coeffs,
+                                u64* tmp, int ncols, hipStream_t s) {
   const size_t N = (size_t)1 << S->log_n, H = N >> 1;
   const u64 si = gl_inv(S->shift[h]);
   // Q(s x) has coefficients q_k s^k: halves hold q_(2e) s^(2e) and q_(2e+1) s^(2e+1); the odd half's s^-1 rides on its 1/2
   k_split_inv<<<dim3((unsigned)(N / 512), ncols), 256, 0, s>>>(values, coeffs, N, S->inv_hi, S->inv_lo, S->half, gl_mul(S->half, si));
-  ntt_inverse_tall(T, TT, coeffs, coeffs, tmp, 2 * ncols, s);
+  inverse_tall(T, TT, coeffs, coeffs, tmp, 2 * ncols, s);
   k_coset_unscale_half<<<dim3((unsigned)(H / 256), 2 * ncols), 256, 0, s>>>(coeffs, H, TT->log_n - 16, gl_mul(si, si));
+}
+
+// ---- one plan per trace height, three operations (ntt.h) ----------------------------------------------------------------
+// The only place that chooses between the 2^16, the tall and the split sequence, and that lays the scratch out.
+int ntt_plan_init(NttPlan* P, const NttTables* base, unsigned log_n, bool split) {
+  *P = NttPlan{};
+  if (log_n < 16 || log_n - split > 22 || (split && log_n < 18)) return -1;  // R <= 64 (and e < 2^22 in split_pow); a split height has R >= 2
+  P->log_n = log_n;
+  P->log_s = split ? 1 : 0;
+  P->log_r = log_n - 16 - P->log_s;
+  P->base = base;
+  // under the split level the tall transforms run on the halves: H = N / 2 points, cosets g^2 and g^2 w_N
+  if ((P->log_r && tall_tables_init(&P->tall, log_n - P->log_s, split ? gl_mul(GL_GEN, GL_GEN) : GL_GEN)) ||
+      (split && split_tables_init(&P->split, log_n))) {
+    ntt_plan_free(P);
+    return -1;
+  }
+  return 0;
+}
+void ntt_plan_free(NttPlan* P) {
+  tall_tables_free(&P->tall);
+  split_tables_free(&P->split);
+}
+size_t ntt_scratch_words(unsigned log_n, bool split, int ncols) { return (size_t)(log_n == 16 || split ? 3 : 1) * ncols << log_n; }
+
+// Split level: the E and O LDEs of the columns at scratch [C][2][N], the tall transforms' tmp [2 C][N / 2] behind them.
+void ntt_commit(const NttPlan& P, const u64* vals, u64* coef, u64* lde, size_t lde_stride, u64* scratch, int ncols, hipStream_t s) {
+  const size_t N = (size_t)1 << P.log_n;
+  assert(P.log_s || lde_stride == 2 * N);
+  if (P.log_s) {
+    split_inverse(&P.split, vals, coef, ncols, s);
+    commit_tall(P.base, &P.tall, coef, coef, scratch, scratch + (size_t)ncols * 2 * N, 2 * ncols, s);
+    split_forward(&P.split, scratch, lde, lde_stride, ncols, s, 3);
+  } else if (P.log_r) commit_tall(P.base, &P.tall, vals, coef, lde, scratch, ncols, s);
+  else commit_base(P.base, vals, coef, lde, scratch, ncols, s);
+}
+void ntt_lde(const NttPlan& P, const u64* coef, u64* lde, size_t lde_stride, u64* scratch, int ncols, hipStream_t s, int coset_mask) {
+  const size_t N = (size_t)1 << P.log_n;
+  assert(P.log_s || lde_stride == 2 * N);
+  assert(P.log_r || coset_mask == 3);
+  if (P.log_s) {
+    lde_tall(P.base, &P.tall, coef, scratch, scratch + (size_t)ncols * 2 * N, 2 * ncols, s, coset_mask);
+    split_forward(&P.split, scratch, lde, lde_stride, ncols, s, coset_mask);
+  } else if (P.log_r) lde_tall(P.base, &P.tall, coef, lde, scratch, ncols, s, coset_mask);
+  else lde_base(P.base, coef, lde, scratch, ncols, s);
+}
+void ntt_coset_inverse(const NttPlan& P, int h, const u64* vals, u64* coef, u64* scratch, int ncols, hipStream_t s) {
+  if (P.log_s) coset_inverse_split(P.base, &P.tall, &P.split, h, vals, coef, scratch, ncols, s);
+  else if (P.log_r) coset_inverse_tall(P.base, &P.tall, h, vals, coef, scratch, ncols, s);
+  else coset_inverse_base(P.base, h, vals, coef, scratch, ncols, s);
 }
 
 // ---- self test of the hand-written field sequences (gl_asm.h) -------------------------------------------------------
@@ -845,21 +862,12 @@ __global__ __launch_bounds__(256) void k_outer_dft_selftest(const u64* __restric
 #pragma unroll
   for (int r = 0; r < R; r++) out[i * R + r] = x[r];
 }
-template <int LOGR>
-static void outer_dft_selftest_launch(bool inverse, const u64* in, u64* out, size_t n, hipStream_t s) {
-  const unsigned blocks = (unsigned)((n + 255) / 256);
-  if (inverse) k_outer_dft_selftest<LOGR, true><<<blocks, 256, 0, s>>>(in, out, n);
-  else k_outer_dft_selftest<LOGR, false><<<blocks, 256, 0, s>>>(in, out, n);
-}
 void outer_dft_selftest(int log_r, bool inverse, const u64* in, u64* out, size_t n, hipStream_t s) {
-  switch (log_r) {
-    case 1: outer_dft_selftest_launch<1>(inverse, in, out, n, s); break;
-    case 2: outer_dft_selftest_launch<2>(inverse, in, out, n, s); break;
-    case 3: outer_dft_selftest_launch<3>(inverse, in, out, n, s); break;
-    case 4: outer_dft_selftest_launch<4>(inverse, in, out, n, s); break;
-    case 5: outer_dft_selftest_launch<5>(inverse, in, out, n, s); break;
-    default: outer_dft_selftest_launch<6>(inverse, in, out, n, s); break;
-  }
+  const unsigned blocks = (unsigned)((n + 255) / 256);
+  with_logr((unsigned)log_r, [&](auto L) {
+    if (inverse) k_outer_dft_selftest<decltype(L)::value, true><<<blocks, 256, 0, s>>>(in, out, n);
+    else k_outer_dft_selftest<decltype(L)::value, false><<<blocks, 256, 0, s>>>(in, out, n);
+  });
 }
 
 // loads this translation unit's code object (the HIP runtime defers that to the first launch otherwise)

@@ -1,7 +1,7 @@
 // Debug entry points for the NTT / LDE stage above 2^16 rows (bn254s_selftest_transforms, _mul_2exp, _outer_dft;
 // include/bn254_stark.h).  bn254s_selftest_transforms runs the members of Transforms (transforms.h) that the provers' stages run,
-// on caller data, in named scratch of the context on its stream, with the tall and split tables of the context's caches: the
-// dispatch by height and workspace is the provers' own, nothing of it is repeated here.  The two small ones run the shift table and
+// on caller data, in named scratch of the context on its stream, on the context's plan of the height: the chunking by workspace
+// is the provers' own, the dispatch by height is ntt.hip's, nothing of either is repeated here.  The two small ones run the shift table and
 // the R-point DFT of the outer passes through the kernels beside k_field_selftest in ntt.hip.  Every argument is checked on the
 // host (pointers, sizes, every field word below p) before anything is launched.
 #include "ctx.h"
@@ -32,24 +32,14 @@ int bn254s_selftest_transforms(bn254s_ctx* c, int op, int log_n, int flags, int 
   const size_t N = pl.N = (size_t)1 << log_n, M2 = pl.M2 = 2 * N;
   pl.log_m2 = pl.log_n + 1;
   pl.log_s = split ? 1 : 0;
-  pl.log_r = pl.log_n - 16 - pl.log_s;
-  pl.R = (size_t)1 << pl.log_r;
-  pl.NH = N >> pl.log_s;
-  pl.NSPL = 1 << pl.log_s;
-  pl.stream = op == 2;  // (lde_chunk is a member of the streaming workspace)
-  pl.lowmem = pl.stream || pl.log_s || compact;
+  pl.lowmem = op == 2 || split || compact;  // (op 2: lde_chunk is a member of the streaming workspace, which is a compact one)
   const size_t n_in = (size_t)ncols * N;
   if (!all_canonical(in, n_in)) return BN254S_E_INVALID_ARG;
 
   HIP_TRY(c, hipSetDevice(c->device));
-  const NttTallTables* TT = nullptr;
-  const NttSplitTables* SP = nullptr;
-  if (pl.log_r && !(TT = get_tall_tables(c, pl.log_n - pl.log_s, pl.log_s != 0))) {
-    c->set_err("tall NTT tables");
-    return BN254S_E_OOM;
-  }
-  if (pl.log_s && !(SP = get_split_tables(c, pl.log_n))) {
-    c->set_err("split NTT tables");
+  const NttPlan* np = c->ntt_plan(pl.log_n, split);
+  if (!np) {
+    c->set_err("NTT tables");
     return BN254S_E_OOM;
   }
   const size_t n_lde = (size_t)ncols * M2;
@@ -60,7 +50,7 @@ int bn254s_selftest_transforms(bn254s_ctx* c, int op, int log_n, int flags, int 
   if (!d_in || !d_tmp || (!d_coef && (op == 0 || op == 3)) || (!d_lde && op != 3)) return BN254S_E_OOM;
   hipStream_t st = c->stream;
   HIP_TRY(c, hipMemcpyAsync(d_in, in, 8 * n_in, hipMemcpyHostToDevice, st));
-  const Transforms tf{c, st, TT, SP, pl, d_tmp, d_lde, nullptr};
+  const Transforms tf{*np, st, pl, d_tmp, d_lde, nullptr};
   switch (op) {
     case 0: tf.commit_ntt(d_in, d_coef, d_lde, ncols); break;
     case 1: tf.lde(d_in, d_lde, ncols); break;

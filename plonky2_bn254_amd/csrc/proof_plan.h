@@ -5,6 +5,7 @@
 #include <string>
 #include "aux.h"
 #include "fri.h"
+#include "ntt.h"
 
 // The test overrides, read from the environment per call by the caller (plan_overrides_from_env):
 // BN254S_FORCE_SPLIT / BN254S_FORCE_LOWMEM / BN254S_FORCE_STREAM, and BN254S_STREAM_WIN_LOG (-1: not set).
@@ -45,11 +46,9 @@ struct ProofPlan {
   size_t tree_words = 0, fri_words = 0, fri_tree_words = 0, in_words = 0;
   PlanBuffers words = {};
   size_t pinned_bytes = 0;  // staging for the two larger device -> host copies (opening partials, query rounds)
-  // words of the transforms' scratch for commitments of at most `width` columns (needs N, log_s, log_r, lowmem):
-  // [tmp | y0 | y1] for the fused commitment; one tmp for a tall one; [E,O LDEs | tmp] of one column chunk under the split level
-  size_t ntt_tmp_words(int width) const {
-    return log_s ? (size_t)3 * CH * N : lowmem ? (size_t)CH * N : (size_t)(log_r ? 1 : 3) * width * N;
-  }
+  // words of the transforms' scratch for commitments of at most `width` columns (needs log_n, log_s, lowmem): the compact and
+  // the streaming workspace transform one chunk of columns at a time
+  size_t ntt_tmp_words(int width) const { return ntt_scratch_words(log_n, log_s != 0, lowmem ? CH : width); }
   size_t n_part() const { return (size_t)(W + A + NQ) * NSPL * R * 5; }  // words of the opening partials
   size_t n_q() const { return wpq * P.num_queries; }                     // words of the query rounds
 };

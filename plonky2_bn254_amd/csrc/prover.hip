@@ -799,26 +799,15 @@ static int prove_on_slot(bn254s_ctx* c, Slot& sl, int kind, const bn254s_params&
     err = "point tables";
     return rc;
   }
-  const NttTallTables* TT = nullptr;
-  const NttSplitTables* SP = nullptr;
-  if (pl.log_r) {
-    TT = get_tall_tables(c, pl.log_n - pl.log_s, pl.log_s != 0);
-    if (!TT) {
-      err = "tall NTT tables";
-      return BN254S_E_OOM;
-    }
-  }
-  if (pl.log_s) {
-    SP = get_split_tables(c, pl.log_n);
-    if (!SP) {
-      err = "split NTT tables";
-      return BN254S_E_OOM;
-    }
+  const NttPlan* np = c->ntt_plan(pl.log_n, pl.log_s != 0);
+  if (!np) {
+    err = "NTT tables";
+    return BN254S_E_OOM;
   }
   Workspace ws;
   if (int rc = workspace_acquire(sl, pl, ws, err)) return rc;
   if (after_alloc) (*after_alloc)();
-  const Transforms tf{c, st, TT, SP, pl, ws.tmp, ws.ldechunk, ws.sponge};
+  const Transforms tf{*np, st, pl, ws.tmp, ws.ldechunk, ws.sponge};
   if (sl.events.empty()) {
     sl.events.resize(2 * ST_COUNT);
     for (auto& e : sl.events) CHK(hipEventCreate(&e));
