@@ -575,6 +575,45 @@ int bn254s_selftest_fri_combine(bn254s_ctx* ctx, int mode, int W, int n_rc, int 
 int bn254s_selftest_fri_fold(bn254s_ctx* ctx, const uint64_t* in, int log_m, uint64_t shift, const uint64_t beta[2], uint64_t* out);
 int bn254s_selftest_fri_rows(bn254s_ctx* ctx, const uint64_t* lde, int ncols, int log_n, int h, size_t k0, size_t rows,
                              const uint32_t* indices, int nq, uint64_t* window, uint64_t* gathered);
+/* Debug: the quotient (AIR constraint) kernels and the auxiliary columns of one STARK kind on caller data, through what the provers
+ * and bn254s_verify run (csrc/quotient_selftest.hip).  kind: 0 = G1, 1 = G2, 2 = Fq exp, with that kind's real shape: trace width
+ * W = 781 / 1295 / 427, A = 456 / 906 / 134 auxiliary columns (per challenge the LogUp helpers and Z, then the four CTL Z's),
+ * K = 1573 / 2605 / 910 constraints in emission order (AIR, lookups, CTLs).  All buffers are host memory; every field word must be
+ * canonical.  BN254S_E_INVALID_ARG: a NULL argument, a size or combination outside what is stated below, a word of p or more;
+ * nothing is launched then.
+ *
+ * bn254s_selftest_quotient builds the alpha tables (quotient_host_tables), fills the kernel arguments (quotient_fill_args, and
+ *   quotient_window_args in window mode) and calls the kind's quotient_launch: the part kernels, then k_quotient_finish.
+ *   N = 2^log_n.  flags: BN254S_QS_WINDOW, BN254S_QS_RAW (or 0).
+ *   Whole domain (no BN254S_QS_WINDOW; 3 <= log_n <= 12; h, k0, count, stride ignored: count = stride = 2 N): trace[W][2 N] and
+ *     aux[A][2 N] in leaf order (point g w_2N^(2 k + h) at h N + bitrev(k)); the next row of a point is row k + 1 (mod N) of its coset.
+ *   Window (3 <= log_n <= 20): trace[W][stride], aux[A][stride] hold the rows k0 .. k0 + count of coset h in {0, 1} in natural
+ *     order (count + 1 rows: the last serves the transition constraints of the one before); 1 <= count, k0 + count <= N,
+ *     count + 1 <= stride <= 8192.  The points evaluated are the first `count`.
+ *   x / lfirst / llast: all NULL = the library's tables (quotient_point_tables / quotient_point_tables_window); otherwise three
+ *     arrays of `count` words each (whole domain: 2 N, leaf order): x_j, L_first(x_j), L_last(x_j) as the kernels are to see them.
+ *   BN254S_QS_RAW: zh_inv = {1, 1} and w_inv = 0 as bn254s_verify sets them: no division by Z_H, and the transition selector
+ *     z_last is the table value x_j itself.  Otherwise z_last = x_j - w_N^-1 and the sums are multiplied by 1 / Z_H of the coset.
+ *   out[2 alphas][2 cosets][N] (natural order on each coset) and part[7][2 alphas][stride] (the partial sums of part kernel p at
+ *     [p][alpha][j], j as in trace; G1 writes parts 0..5, G2 0..6, Fq 0..1) are IN/OUT: they are uploaded as the caller filled
+ *     them, so a word that no lane writes comes back unchanged.
+ * bn254s_selftest_point_tables: out[3][n] = x, L_first, L_last as quotient_point_tables (window = 0: n = 2 N, leaf order; h, k0,
+ *   count ignored) or quotient_point_tables_window (window = 1: n = count rows from k0 (mod N) of coset h; k0 < N, 1 <= count <= N)
+ *   write them; 3 <= log_n <= 20.
+ * bn254s_selftest_aux: trace[W][rows] (rows a power of two in 64 .. 2^16) -> out[A][rows], all auxiliary columns through aux_build
+ *   with the kind's shape: per challenge the helpers and Z, then the CTL Z's in (ctl, challenge) order.  Returns the device error
+ *   word: BN254S_E_INTERNAL for a range-checked or table value above 65535 or a CTL filter value other than 0 and 1 (`out` is not
+ *   meaningful then). */
+#define BN254S_QS_WINDOW 1
+#define BN254S_QS_RAW 2
+#define BN254S_QS_MAX_PARTS 7
+int bn254s_selftest_quotient(bn254s_ctx* ctx, int kind, int log_n, int flags, int h, size_t k0, size_t count, size_t stride,
+                             const uint64_t* trace, const uint64_t* aux, const uint64_t alphas[2], const uint64_t betas[2],
+                             const uint64_t gammas[2], const uint64_t* x, const uint64_t* lfirst, const uint64_t* llast, uint64_t* out,
+                             uint64_t* part);
+int bn254s_selftest_point_tables(bn254s_ctx* ctx, int log_n, int window, int h, size_t k0, size_t count, uint64_t* out);
+int bn254s_selftest_aux(bn254s_ctx* ctx, int kind, const uint64_t* trace, size_t rows, const uint64_t betas[2], const uint64_t gammas[2],
+                        uint64_t* out);
 /* Debug: the NTT / LDE stage at every supported height on caller data (csrc/ntt_selftest.hip).  All buffers are host memory and
  * every word must be canonical.  BN254S_E_INVALID_ARG: a NULL argument, a size or combination outside what is stated below, a word
  * of p or more; nothing is launched then.

@@ -441,4 +441,93 @@ int orc_eval_constraints(int kind, const u64* local, const u64* next, const u64*
   return (int)cc.count;
 }
 
+// Every constraint value of eval_vanishing<F> (AIR, then lookups, then CTLs) at one point, as handed to Consumer::constraint
+// after its selector, in emission order.  local / next: W words, aux_local / aux_next: A words.  Returns K, the number written.
+static int vanishing_values(const StarkDef& d, const StarkConfig& cfg, const F* l, const F* nx, const F* al, const F* an,
+                            const u64* betas2, const u64* gammas2, u64 z_last, u64 lfirst, u64 llast, u64* values_out) {
+  Consumer<F> cc({F(1), F(1)}, F(z_last), F(lfirst), F(llast));
+  std::vector<F> log;
+  cc.log = &log;
+  AuxVars<F> av{al, an};
+  eval_vanishing<F>(d, cfg, l, nx, av, {betas2[0], betas2[1]}, {gammas2[0], gammas2[1]}, cc, d.eval_base);
+  for (size_t e = 0; e < log.size(); e++) values_out[e] = log[e].v;
+  return (int)log.size();
+}
+static int aux_width(const StarkDef& d, const StarkConfig& cfg) {
+  return 2 * (d.num_helpers() + 1) + cfg.num_challenges * (int)d.ctls.size();
+}
+int orc_aux_width(int kind) { return aux_width(def_of(kind), StarkConfig()); }
+int orc_eval_vanishing_values(int kind, const u64* local, const u64* next, const u64* aux_local, const u64* aux_next,
+                              const u64* betas2, const u64* gammas2, u64 z_last, u64 lfirst, u64 llast, u64* values_out) {
+  StarkDef d = def_of(kind);
+  StarkConfig cfg;
+  const int A = aux_width(d, cfg);
+  std::vector<F> l(d.W), nx(d.W), al(A), an(A);
+  for (int i = 0; i < d.W; i++) {
+    l[i] = F(local[i]);
+    nx[i] = F(next[i]);
+  }
+  for (int i = 0; i < A; i++) {
+    al[i] = F(aux_local[i]);
+    an[i] = F(aux_next[i]);
+  }
+  return vanishing_values(d, cfg, l.data(), nx.data(), al.data(), an.data(), betas2, gammas2, z_last, lfirst, llast, values_out);
+}
+// The same for n points of column-major data trace[W][stride], aux[A][stride]: point i has its local row at position idx_local[i]
+// and its next row at idx_next[i]; z_last / lfirst / llast: n words each; values_out[n][K].  Returns K.
+int orc_eval_vanishing_values_at(int kind, const u64* trace, const u64* aux, size_t stride, size_t n, const u64* idx_local,
+                                 const u64* idx_next, const u64* betas2, const u64* gammas2, const u64* z_last, const u64* lfirst,
+                                 const u64* llast, u64* values_out, size_t K_cap) {
+  StarkDef d = def_of(kind);
+  StarkConfig cfg;
+  const int A = aux_width(d, cfg);
+  int K = 0;
+#pragma omp parallel
+  {
+    std::vector<F> l(d.W), nx(d.W), al(A), an(A);
+#pragma omp for schedule(static)
+    for (size_t i = 0; i < n; i++) {
+      const size_t j = idx_local[i], jn = idx_next[i];
+      for (int c = 0; c < d.W; c++) {
+        l[c] = F(trace[(size_t)c * stride + j]);
+        nx[c] = F(trace[(size_t)c * stride + jn]);
+      }
+      for (int c = 0; c < A; c++) {
+        al[c] = F(aux[(size_t)c * stride + j]);
+        an[c] = F(aux[(size_t)c * stride + jn]);
+      }
+      Consumer<F> cc({F(1), F(1)}, F(z_last[i]), F(lfirst[i]), F(llast[i]));
+      std::vector<F> log;
+      cc.log = &log;
+      AuxVars<F> av{al.data(), an.data()};
+      eval_vanishing<F>(d, cfg, l.data(), nx.data(), av, {betas2[0], betas2[1]}, {gammas2[0], gammas2[1]}, cc, d.eval_base);
+      if (log.size() <= K_cap)
+        for (size_t e = 0; e < log.size(); e++) values_out[i * K_cap + e] = log[e].v;
+      if (i == 0) K = (int)log.size();
+    }
+  }
+  return K;
+}
+// All auxiliary columns of trace[W][N] in the prover's column order: lookup_helper_columns per challenge (helpers, then Z), then
+// ctl_z_column per (ctl, challenge).  out[A][N].  Returns 0, or -1 with "Non-binary filter?" in orc_last_error.
+int orc_aux_columns(int kind, const u64* trace, size_t N, const u64* betas2, const u64* gammas2, u64* out) {
+  try {
+    StarkDef d = def_of(kind);
+    StarkConfig cfg;
+    std::vector<std::vector<u64>> tr(d.W);
+    for (int c = 0; c < d.W; c++) tr[c].assign(trace + (size_t)c * N, trace + (size_t)(c + 1) * N);
+    size_t col = 0;
+    for (int ch = 0; ch < cfg.num_challenges; ch++)
+      for (auto& v : lookup_helper_columns(d, tr, betas2[ch])) memcpy(out + (col++) * N, v.data(), 8 * N);
+    for (auto& ctl : d.ctls)
+      for (int ch = 0; ch < cfg.num_challenges; ch++) {
+        std::vector<u64> z = ctl_z_column(ctl, tr, betas2[ch], gammas2[ch]);
+        memcpy(out + (col++) * N, z.data(), 8 * N);
+      }
+    return 0;
+  } catch (std::exception& e) {
+    return fail(e);
+  }
+}
+
 }  // extern "C"

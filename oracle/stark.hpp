@@ -44,9 +44,11 @@ struct Consumer {
   std::vector<T> alphas, accs;
   T z_last, lagrange_first, lagrange_last;
   size_t count = 0;
+  std::vector<T>* log = nullptr;  // optional: every value handed to constraint(), after its selector, in emission order
   Consumer(const std::vector<T>& al, T zl, T lf, T ll) : alphas(al), accs(al.size()), z_last(zl), lagrange_first(lf), lagrange_last(ll) {}
   void constraint(T c) {
     for (size_t j = 0; j < alphas.size(); j++) accs[j] = accs[j] * alphas[j] + c;
+    if (log) log->push_back(c);
     count++;
   }
   void constraint_transition(T c) { constraint(c * z_last); }

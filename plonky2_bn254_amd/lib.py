@@ -130,6 +130,11 @@ def load_library():
         lib.bn254s_selftest_transforms.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
         lib.bn254s_selftest_mul_2exp.argtypes = [vp, vp, C.c_size_t, vp]
         lib.bn254s_selftest_outer_dft.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t, vp]
+    if hasattr(lib, "bn254s_selftest_quotient"):   # (likewise; the three entry points of csrc/quotient_selftest.hip come together)
+        lib.bn254s_selftest_quotient.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp,
+                                                 vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.bn254s_selftest_point_tables.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, vp]
+        lib.bn254s_selftest_aux.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, vp, vp]
     if hasattr(lib, "bn254s_selftest_proof_plan"):   # (likewise)
         lib.bn254s_selftest_proof_plan.argtypes = [C.c_int, C.c_size_t, C.POINTER(Params), C.c_uint64, C.c_int, C.c_int, C.c_int,
                                                    C.c_int, vp, C.c_char_p, C.c_size_t]
@@ -725,6 +730,62 @@ class Context:
         out = np.zeros((2 * ((n_rc + 1) // 2 + 1), rows), np.uint64)
         self._check(self._lib.bn254s_selftest_logup(self._h, _ptr(trace), rows, ncols, rc_begin, n_rc, table_col, freq_col, _ptr(b),
                                                     _ptr(out)), "bn254s_selftest_logup")
+        return out
+
+    # The quotient kernels and the auxiliary columns of a STARK kind on caller data (csrc/quotient_selftest.hip; include/bn254_stark.h
+    # has the layouts).
+    STARK_SHAPES = {0: (781, 456, 1111, 1573), 1: (1295, 906, 1693, 2605), 2: (427, 134, 770, 910)}   # kind: W, A, AIR constraints, K
+    QS_MAX_PARTS = 7
+    QS_N_PARTS = {0: 6, 1: 7, 2: 2}
+
+    def selftest_quotient(self, kind: int, log_n: int, trace: np.ndarray, aux: np.ndarray, alphas, betas, gammas, raw: bool = False,
+                          window=None, tables=None, fill: int = 0):
+        """Debug: the quotient kernels of `kind` on trace[W][stride], aux[A][stride] (bn254s_selftest_quotient).  window = None: the
+        whole domain in leaf order, stride = 2^(log_n + 1); window = (h, k0, count): the rows k0 .. k0 + count of coset h in natural
+        order.  tables = (x, lfirst, llast) or None for the library's own.  raw: no division by Z_H, z_last = x.  Returns
+        (out[2][2][N], part[7][2][stride]); both start out filled with the word `fill`."""
+        w, a, _, _ = self.STARK_SHAPES[kind]
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        aux = np.ascontiguousarray(aux, dtype=np.uint64)
+        stride = trace.shape[1]
+        assert trace.shape == (w, stride) and aux.shape == (a, stride), (trace.shape, aux.shape)
+        n = 1 << log_n
+        flags = (2 if raw else 0) | (1 if window is not None else 0)
+        h, k0, count = window if window is not None else (0, 0, 0)
+        if window is None:
+            assert stride == 2 * n, (stride, n)
+        ch = [np.array([int(v[0]), int(v[1])], dtype=np.uint64) for v in (alphas, betas, gammas)]
+        tabs = [None, None, None] if tables is None else [np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
+        if tables is not None:
+            want = count if window is not None else 2 * n
+            assert all(t.shape == (want,) for t in tabs), [t.shape for t in tabs]
+        out = np.full((2, 2, n), fill, np.uint64)
+        part = np.full((self.QS_MAX_PARTS, 2, stride), fill, np.uint64)
+        self._check(self._lib.bn254s_selftest_quotient(self._h, kind, log_n, flags, h, k0, count, stride if window is not None else 0,
+                                                       _ptr(trace), _ptr(aux), _ptr(ch[0]), _ptr(ch[1]), _ptr(ch[2]), _ptr(tabs[0]),
+                                                       _ptr(tabs[1]), _ptr(tabs[2]), _ptr(out), _ptr(part)), "bn254s_selftest_quotient")
+        return out, part
+
+    def selftest_point_tables(self, log_n: int, window=None) -> np.ndarray:
+        """Debug: out[3][n] = x, L_first, L_last of the quotient kernels' point tables: the whole domain in leaf order (n = 2^(log_n + 1))
+        or, window = (h, k0, count), the rows k0 .. of coset h in natural order (bn254s_selftest_point_tables)."""
+        h, k0, count = window if window is not None else (0, 0, 2 << log_n)
+        out = np.zeros((3, count), np.uint64)
+        self._check(self._lib.bn254s_selftest_point_tables(self._h, log_n, int(window is not None), h, k0, count, _ptr(out)),
+                    "bn254s_selftest_point_tables")
+        return out
+
+    def selftest_aux(self, kind: int, trace: np.ndarray, betas, gammas) -> np.ndarray:
+        """Debug: all auxiliary columns out[A][rows] of trace[W][rows] through the provers' aux_build with the kind's shape, CTL Z
+        columns included (bn254s_selftest_aux)."""
+        w, a, _, _ = self.STARK_SHAPES[kind]
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        assert trace.ndim == 2 and trace.shape[0] == w, trace.shape
+        rows = trace.shape[1]
+        b = np.array([int(betas[0]), int(betas[1])], dtype=np.uint64)
+        g = np.array([int(gammas[0]), int(gammas[1])], dtype=np.uint64)
+        out = np.zeros((a, rows), np.uint64)
+        self._check(self._lib.bn254s_selftest_aux(self._h, kind, _ptr(trace), rows, _ptr(b), _ptr(g), _ptr(out)), "bn254s_selftest_aux")
         return out
 
     # The openings / FRI kernels and the un-reduced accumulators on caller data (csrc/fri_selftest.hip; include/bn254_stark.h has

@@ -15,8 +15,8 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(PATH):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle")])
+    # make checks the dependencies itself: a library older than one of its sources is rebuilt, an up-to-date one costs a stat each
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")], stdout=subprocess.DEVNULL)
     lib = C.CDLL(PATH)
     lib.orc_last_error.restype = C.c_char_p
     lib.orc_gl_mul.restype = C.c_uint64
@@ -49,6 +49,10 @@ def load():
     lib.orc_prove.argtypes = [C.c_int, VP, VP, VP, C.c_size_t, C.c_int, VP, C.c_size_t, VP, VP]
     lib.orc_verify.argtypes = [C.c_int, VP, C.c_size_t, C.c_int, VP, VP, VP, C.c_size_t]
     lib.orc_eval_constraints.argtypes = [C.c_int, VP, VP, VP, C.c_uint64, C.c_uint64, C.c_uint64, VP]
+    lib.orc_aux_width.argtypes = [C.c_int]
+    lib.orc_eval_vanishing_values.argtypes = [C.c_int, VP, VP, VP, VP, VP, VP, C.c_uint64, C.c_uint64, C.c_uint64, VP]
+    lib.orc_eval_vanishing_values_at.argtypes = [C.c_int, VP, VP, C.c_size_t, C.c_size_t, VP, VP, VP, VP, VP, VP, VP, VP, C.c_size_t]
+    lib.orc_aux_columns.argtypes = [C.c_int, VP, C.c_size_t, VP, VP, VP]
     _lib = lib
     return lib
 
@@ -112,6 +116,43 @@ def prove(lib, kind, s, x, o=None, min_rows_log2=16):
     if r < 0:
         raise RuntimeError(lib.orc_last_error().decode())
     return proof[:r], outs, tm, degree_bits
+
+
+def vanishing_values(lib, kind, local, nxt, aux_local, aux_next, betas, gammas, z_last, lfirst, llast):
+    """Every constraint value of one point in emission order (AIR, lookups, CTLs), as Python integers."""
+    arrs = [np.ascontiguousarray(a, dtype=np.uint64) for a in (local, nxt, aux_local, aux_next, betas, gammas)]
+    out = np.zeros(4096, np.uint64)
+    k = lib.orc_eval_vanishing_values(kind, *[ptr(a) for a in arrs], int(z_last), int(lfirst), int(llast), ptr(out))
+    return [int(v) for v in out[:k]]
+
+
+def vanishing_values_at(lib, kind, trace, aux, idx_local, idx_next, betas, gammas, z_last, lfirst, llast):
+    """values[n][K] (uint64) for the n points whose local / next rows are the positions idx_local / idx_next of the column-major
+    trace[W][stride], aux[A][stride]."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    aux = np.ascontiguousarray(aux, dtype=np.uint64)
+    stride = trace.shape[1]
+    assert trace.shape[0] == lib.orc_stark_width(kind) and aux.shape == (lib.orc_aux_width(kind), stride)
+    v = [np.ascontiguousarray(a, dtype=np.uint64) for a in (idx_local, idx_next, betas, gammas, z_last, lfirst, llast)]
+    n = v[0].shape[0]
+    assert all(a.shape == (n,) for a in (v[1], v[4], v[5], v[6])) and int(max(v[0].max(), v[1].max())) < stride
+    cap = 4096
+    out = np.zeros((n, cap), np.uint64)
+    k = lib.orc_eval_vanishing_values_at(kind, ptr(trace), ptr(aux), stride, n, *[ptr(a) for a in v], ptr(out), cap)
+    assert 0 < k <= cap
+    return out[:, :k]
+
+
+def aux_columns(lib, kind, trace, betas, gammas):
+    """out[A][N] of trace[W][N]: the oracle's LogUp columns per challenge, then its CTL Z columns.  RuntimeError with the
+    oracle's text on a filter that is not 0 or 1."""
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    b = np.array([int(v) for v in betas], dtype=np.uint64)
+    g = np.array([int(v) for v in gammas], dtype=np.uint64)
+    out = np.zeros((lib.orc_aux_width(kind), trace.shape[1]), np.uint64)
+    if lib.orc_aux_columns(kind, ptr(trace), trace.shape[1], ptr(b), ptr(g), ptr(out)) != 0:
+        raise RuntimeError(lib.orc_last_error().decode())
+    return out
 
 
 def verify(lib, kind, proof, degree_bits, s, x, o=None):
