@@ -33,17 +33,19 @@
  * GPU / per host thread).  A batch opened with bn254s_prove_batch_begin stays in flight after _begin returns: until its _end
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
  * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x /
- * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor / bn254s_job_outputs / bn254s_map_to_g1) queues
- * behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its own, so it can never share
- * device state with a proof of the open batch; bn254s_verify_batch uses the context's own stream and device memory that it allocates
+ * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor / bn254s_job_outputs / bn254s_map_to_g1 / bn254s_fq_sqrt /
+ * bn254s_fq2_sqrt) queues behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its
+ * own, so it can never share device state with a proof of the open batch; bn254s_verify_batch uses the context's own stream and device memory that it allocates
  * and frees itself, so it is independent of open batches too; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
  * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch,
  * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch, bn254s_job_outputs_batch,
- * bn254s_hash_to_fq_batch, bn254s_map_to_g1_batch, bn254s_hash_to_g1_batch and the front-end halves of bn254s_g1_recover_from_x,
- * bn254s_g2_recover_from_x, bn254s_g2_subgroup_check, bn254s_g2_clear_cofactor, bn254s_job_outputs and bn254s_map_to_g1, like
- * those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub"
+ * bn254s_hash_to_fq_batch, bn254s_map_to_g1_batch, bn254s_hash_to_g1_batch, bn254s_fq_sqrt_batch, bn254s_fq2_sqrt_batch,
+ * bn254s_fq_inv_batch, bn254s_fq2_inv_batch and the front-end halves of bn254s_g1_recover_from_x,
+ * bn254s_g2_recover_from_x, bn254s_g2_subgroup_check, bn254s_g2_clear_cofactor, bn254s_job_outputs, bn254s_map_to_g1,
+ * bn254s_fq_sqrt and bn254s_fq2_sqrt, like those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub"
  * for the subgroup check, "g2cof" and "g2cof.link" for cofactor clearing, "m2g.batch" for the proof-free map, "jobout" for the
- * job outputs, "m2g1", "h2f1.in" and "h2f1.out" for map_to_g1 and hash_to_fq) and are independent of open batches.
+ * job outputs, "m2g1", "h2f1.in" and "h2f1.out" for map_to_g1 and hash_to_fq, "fqsqrt", "fq2sqrt" and "fqinv" for the field
+ * gadgets) and are independent of open batches.
  */
 #ifndef BN254_STARK_H
 #define BN254_STARK_H
@@ -330,6 +332,49 @@ int bn254s_g2_recover_from_x_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 8:
 int bn254s_g2_recover_from_x(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* xs, const uint8_t* sgns, size_t n,
                              size_t per_proof, uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs /* may be NULL */,
                              bn254s_proof** fq_proofs);
+/* The field gadgets on their own: the witness side of FqTarget::is_square (src/fields/fq.rs:283-295), FqTarget::sqrt_with_sgn
+ * (fq.rs:266-281, generator :357-365), Fq2Target::is_square (src/fields/fq2.rs:228-241), Fq2Target::sqrt_with_sgn (fq2.rs:209-226,
+ * generator :305-313; sign rule src/fields/sgn.rs) and the two inv gadgets (fq.rs:241-255, fq2.rs:190-204; native inv.rs), for a
+ * value that is not the g(x) of a curve (csrc/field_gadgets.hip; the recovery and map calls above fuse the same arithmetic behind
+ * their equations).  For every x_i (Fq: 4 words; Fq2: 8 words c0, c1; each coordinate canonical) and wanted sign sgns[i] (0 or 1;
+ * sgns == NULL: all 0), exactly and with canonical outputs:
+ *   square_out[i]  = the is_square gadget: 1 iff b^((p-1)/2) == 1 for b = x_i (Fq) or b = norm(x_i) = c0^2 + c1^2 (Fq2).  0 for
+ *                    x_i = 0: the Legendre symbol of 0 is 0 (the norm is zero only for x_i = 0, as p = 3 mod 4);
+ *   root_ok_out[i] = 1 iff a y exists with y^2 = x_i and sgn(y) == sgns[i].  For x_i != 0 that is square_out[i] (y and -y have
+ *                    opposite signs, in Fq and under the Fq2 rule); for x_i = 0 it is sgns[i] == 0: the only root is 0, and a
+ *                    circuit that asks for the odd root of zero has no witness;
+ *   roots_out[i]   = that y where root_ok_out[i] is 1, zero words where it is 0 (the reference's generator panics there).
+ *                    Fq sign: the parity of the canonical value; Fq2 sign: the parity of c0, or of c1 when c0 is zero;
+ *   fq_jobs[i]     = (p-1)/2 | b (8 words; may be NULL): the Fq-exp job whose output is the Legendre symbol, as in
+ *                    bn254s_g1_recover_from_x.
+ * Errors, all before any device work and before anything is written: BN254S_E_INVALID_ARG for a NULL required pointer, n == 0 or
+ * n >= 2^32, an sgns[i] above 1, or a coordinate >= p (bn254s_last_error names "x_<i>", for Fq2 with the coordinate c0 | c1; the
+ * first such i, the coordinates before the sign).  BN254S_E_INTERNAL: a device self-check (the ladder's result squares to neither
+ * x nor -x, or the root does not square back).
+ * bn254s_fq_sqrt_batch, bn254s_fq2_sqrt_batch: device front-end only, no proof. */
+int bn254s_fq_sqrt_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 4, canonical < p */,
+                         const uint8_t* sgns /* n bytes, 0 or 1; NULL = all 0 */, size_t n, uint64_t* roots_out /* n x 4 */,
+                         uint8_t* square_out /* n */, uint8_t* root_ok_out /* n */,
+                         uint64_t* fq_jobs /* may be NULL: n x 8 = (p-1)/2 | x */);
+int bn254s_fq2_sqrt_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 8: c0, c1, each < p */,
+                          const uint8_t* sgns /* n bytes, 0 or 1; NULL = all 0 */, size_t n, uint64_t* roots_out /* n x 8 */,
+                          uint8_t* square_out /* n */, uint8_t* root_ok_out /* n */,
+                          uint64_t* fq_jobs /* may be NULL: n x 8 = (p-1)/2 | norm(x) */);
+/* The front-end plus the Fq-exp proofs of the n Legendre jobs, cut into ceil(n / per_proof) proofs exactly as
+ * bn254s_prove_batch (kind 2) cuts them.  The outputs of the proofs are checked word for word against the flags, three-valued:
+ * job i must give 1 where square_out[i] is 1, p - 1 where it is 0 and the job's base is non-zero, and 0 where the base is zero; a
+ * mismatch is BN254S_E_INTERNAL naming i.  On any error every proof of the call is freed, its slot in fq_proofs is NULL and no
+ * output is written.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work (invalid arguments are reported first). */
+int bn254s_fq_sqrt(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* xs, const uint8_t* sgns, size_t n, size_t per_proof,
+                   uint64_t* roots_out, uint8_t* square_out, uint8_t* root_ok_out, uint64_t* fq_jobs /* may be NULL */,
+                   bn254s_proof** fq_proofs /* ceil(n / per_proof) */);
+int bn254s_fq2_sqrt(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* xs, const uint8_t* sgns, size_t n, size_t per_proof,
+                    uint64_t* roots_out, uint8_t* square_out, uint8_t* root_ok_out, uint64_t* fq_jobs /* may be NULL */,
+                    bn254s_proof** fq_proofs /* ceil(n / per_proof) */);
+/* out[i] = x_i^-1, zero words for x_i = 0 (the gadgets' inv(0) = 0); for Fq2 the inverse is (c0, -c1) / norm(x_i).  Device only,
+ * no proof (the gadgets constrain x * inv == 1 in the circuit).  Errors as above: NULL, n == 0 or n >= 2^32, a coordinate >= p. */
+int bn254s_fq_inv_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 4, canonical < p */, size_t n, uint64_t* out /* n x 4 */);
+int bn254s_fq2_inv_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 8: c0, c1, each < p */, size_t n, uint64_t* out /* n x 8 */);
 /* G2 subgroup check: is P_i, a point of the twist curve E'(Fq2), in the r-torsion subgroup, [r] P_i = O?  The twist has the
  * cofactor 2p - r = 10069 * 5864401 * 1875725156269 * (a 178-bit prime), so bn254s_g2_recover_from_x hands out points that are
  * no group elements of G2; this is the link between it and bn254s_g2_msm.  The reference has no such gadget: it is the circuit

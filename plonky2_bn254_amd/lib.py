@@ -92,6 +92,11 @@ def load_library():
     lib.bn254s_g1_recover_from_x.argtypes = [vp, C.POINTER(Params), vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
     lib.bn254s_g2_recover_from_x_batch.argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp]
     lib.bn254s_g2_recover_from_x.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, C.POINTER(vp)]
+    for name in ("bn254s_fq_sqrt", "bn254s_fq2_sqrt"):
+        getattr(lib, name + "_batch").argtypes = [vp, vp, vp, C.c_size_t, vp, vp, vp, vp]
+        getattr(lib, name).argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, C.POINTER(vp)]
+    lib.bn254s_fq_inv_batch.argtypes = [vp, vp, C.c_size_t, vp]
+    lib.bn254s_fq2_inv_batch.argtypes = [vp, vp, C.c_size_t, vp]
     lib.bn254s_g2_subgroup_check_batch.argtypes = [vp, vp, C.c_size_t, vp]
     lib.bn254s_g2_subgroup_check.argtypes = [vp, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.POINTER(vp)]
     lib.bn254s_g2_clear_cofactor_batch.argtypes = [vp, vp, C.c_size_t, vp, vp]
@@ -466,6 +471,60 @@ class Context:
         self._check(self._lib.bn254s_g2_recover_from_x(self._h, C.byref(params), _ptr(xs), sp, n, per_proof, _ptr(pts),
                                                        flags.ctypes.data_as(C.c_void_p), _ptr(jobs), outs), "bn254s_g2_recover_from_x")
         return pts, flags, jobs, _proofs(self._lib, outs)
+
+    def _sqrt(self, fn, w, xs, sgns, per_proof, params):
+        """The four root calls: w words per element, per_proof None for the front-end alone."""
+        xs = np.ascontiguousarray(xs, dtype=np.uint64)
+        n = xs.shape[0]
+        sgns, sp = self._sgns(sgns, n)
+        roots, jobs = np.zeros((n, w), np.uint64), np.zeros((n, 8), np.uint64)
+        square, ok = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        sq_p, ok_p = square.ctypes.data_as(C.c_void_p), ok.ctypes.data_as(C.c_void_p)
+        if per_proof is None:
+            self._check(getattr(self._lib, fn)(self._h, _ptr(xs), sp, n, _ptr(roots), sq_p, ok_p, _ptr(jobs)), fn)
+            return roots, square, ok, jobs
+        params = params or default_params()
+        outs = _slots(n, per_proof)
+        self._check(getattr(self._lib, fn)(self._h, C.byref(params), _ptr(xs), sp, n, per_proof, _ptr(roots), sq_p, ok_p, _ptr(jobs),
+                                           outs), fn)
+        return roots, square, ok, jobs, _proofs(self._lib, outs)
+
+    def fq_sqrt_batch(self, xs, sgns=None):
+        """xs [n,4] (canonical, below p), sgns [n] in {0, 1} (None: all 0) -> (roots [n,4], square [n] uint8, root_ok [n] uint8,
+        fq_jobs [n,8]): square[i] = 1 iff x_i^((p-1)/2) == 1 (0 for x_i = 0), root_ok[i] = 1 iff a y with y^2 = x_i and the parity
+        sgns[i] exists (for x_i = 0: iff sgns[i] == 0), roots[i] that y or zeros, fq_jobs[i] = (p-1)/2 | x_i: the witness side of
+        FqTarget::is_square / sqrt_with_sgn on the device, no proof (bn254s_fq_sqrt_batch)."""
+        return self._sqrt("bn254s_fq_sqrt_batch", 4, xs, sgns, None, None)
+
+    def fq2_sqrt_batch(self, xs, sgns=None):
+        """xs [n,8] (c0, c1), sgns [n] -> (roots [n,8], square [n], root_ok [n], fq_jobs [n,8]): the same for Fq2, the Legendre
+        symbol taken of norm(x_i) = c0^2 + c1^2 (fq_jobs[i] = (p-1)/2 | norm(x_i)) and the sign the parity of the root's c0, or of
+        its c1 when c0 is zero: the witness side of Fq2Target::is_square / sqrt_with_sgn (bn254s_fq2_sqrt_batch)."""
+        return self._sqrt("bn254s_fq2_sqrt_batch", 8, xs, sgns, None, None)
+
+    def fq_sqrt(self, xs, sgns=None, per_proof=128, params: Optional[Params] = None):
+        """-> (roots, square, root_ok, fq_jobs, proofs): the front-end plus the Fq-exp proofs of the n Legendre jobs, cut into
+        ceil(n / per_proof) proofs like prove_batch(2, ...) (bn254s_fq_sqrt).  Check it with verify_fq_sqrt."""
+        return self._sqrt("bn254s_fq_sqrt", 4, xs, sgns, per_proof, params)
+
+    def fq2_sqrt(self, xs, sgns=None, per_proof=128, params: Optional[Params] = None):
+        """-> (roots, square, root_ok, fq_jobs, proofs): the Fq2 twin of fq_sqrt (bn254s_fq2_sqrt).  Check it with
+        verify_fq2_sqrt."""
+        return self._sqrt("bn254s_fq2_sqrt", 8, xs, sgns, per_proof, params)
+
+    def _inv(self, fn, xs):
+        xs = np.ascontiguousarray(xs, dtype=np.uint64)
+        out = np.zeros_like(xs)
+        self._check(getattr(self._lib, fn)(self._h, _ptr(xs), xs.shape[0], _ptr(out)), fn)
+        return out
+
+    def fq_inv_batch(self, xs):
+        """xs [n,4] (canonical, below p) -> [n,4]: x_i^-1, zeros for x_i = 0: FqTarget::inv on the device (bn254s_fq_inv_batch)."""
+        return self._inv("bn254s_fq_inv_batch", xs)
+
+    def fq2_inv_batch(self, xs):
+        """xs [n,8] (c0, c1) -> [n,8]: (c0, -c1) / norm, zeros for x_i = 0: Fq2Target::inv on the device (bn254s_fq2_inv_batch)."""
+        return self._inv("bn254s_fq2_inv_batch", xs)
 
     def g2_subgroup_check_batch(self, points):
         """points [n,16] (x.c0, x.c1, y.c0, y.c1, canonical, below p, on the twist curve) -> flags [n] uint8: flags[i] = 1 iff
@@ -1313,6 +1372,80 @@ def verify_g2_recover(xs, sgns, points, flags, fq_jobs, proofs, per_proof, ctx: 
                 raise VerifyError(f"{tag}: sign {i} is {int(sgns[i])}, y of point {i} has the other one")
         elif y != (0, 0):
             raise VerifyError(f"{tag}: point {i} is not (x_{i}, 0) although its flag is clear")
+
+
+def _verify_sqrt(tag, w, xs, sgns, roots, square, root_ok, fq_jobs, proofs, per_proof, ctx, params):
+    """The checks of verify_fq_sqrt / verify_fq2_sqrt for elements of w words (4: Fq, 8: Fq2)."""
+    from tools import synth
+
+    p = synth.P
+    xs, roots, fq_jobs = (np.ascontiguousarray(a, dtype=np.uint64) for a in (xs, roots, fq_jobs))
+    square, root_ok = np.asarray(square).reshape(-1), np.asarray(root_ok).reshape(-1)
+    n = xs.shape[0]
+    sgns = np.zeros(n, np.uint8) if sgns is None else np.asarray(sgns).reshape(-1)
+    if xs.shape != (n, w) or roots.shape != (n, w) or fq_jobs.shape != (n, 8) or square.shape != (n,) or root_ok.shape != (n,) or \
+            sgns.shape != (n,):
+        raise VerifyError(f"{tag}: shapes: xs {xs.shape}, sgns {sgns.shape}, roots {roots.shape}, square {square.shape}, "
+                          f"root_ok {root_ok.shape}, fq_jobs {fq_jobs.shape}")
+    slices = _proof_slices(tag, proofs, n, per_proof, 4)
+
+    def elem(row):
+        return tuple(synth.words_to_int(row[4 * k:4 * k + 4]) for k in range(w // 4))
+
+    x, base = [], []
+    for i in range(n):
+        x.append(elem(xs[i]))
+        if max(x[i]) >= p:
+            raise VerifyError(f"{tag}: x_{i} is not below p")
+        if int(sgns[i]) not in (0, 1):
+            raise VerifyError(f"{tag}: sign {i} is {int(sgns[i])}, neither 0 nor 1")
+        base.append(sum(c * c for c in x[i]) % p if w == 8 else x[i][0])
+        if synth.words_to_int(fq_jobs[i, :4]) != (p - 1) // 2:
+            raise VerifyError(f"{tag}: scalar of job {i} != (p - 1)/2")
+        if synth.words_to_int(fq_jobs[i, 4:]) != base[i]:
+            raise VerifyError(f"{tag}: x of job {i} != {'norm(x_%d)' % i if w == 8 else 'x_%d' % i}")
+    for k, pr, lo, hi, outs in slices:
+        _verify_slice(tag, 2, k, pr, lo, hi, fq_jobs[:, :4], fq_jobs[:, 4:], None, ctx, params)
+        for j in range(lo, hi):  # the three-valued linkage: 1 for a square, p - 1 for a non-square, 0 for a zero base
+            leg = synth.words_to_int(outs[j - lo])
+            want = 0 if base[j] == 0 else 1 if square[j] else p - 1
+            if leg not in (0, 1, p - 1) or (leg == 0) != (base[j] == 0):
+                raise VerifyError(f"{tag}: output {j} of proof {k} is not a Legendre symbol of the base of job {j}")
+            if leg != want or int(square[j]) not in (0, 1) or (square[j] and base[j] == 0):
+                raise VerifyError(f"{tag}: flag {j} (square) is {int(square[j])}, the proven Legendre symbol of job {j} is "
+                                  f"{'0' if leg == 0 else '1' if leg == 1 else 'p - 1'}")
+    for i in range(n):
+        has = bool(square[i]) if base[i] else int(sgns[i]) == 0  # the one root of zero has the sign 0
+        if int(root_ok[i]) != int(has):
+            raise VerifyError(f"{tag}: flag {i} (root_ok) is {int(root_ok[i])}, a root of x_{i} with the sign {int(sgns[i])} "
+                              f"{'exists' if has else 'does not exist'}")
+        y = elem(roots[i])
+        if not has:
+            if any(y):
+                raise VerifyError(f"{tag}: root {i} is not zero although root_ok is clear")
+            continue
+        if max(y) >= p or (synth.f2_mul(y, y) if w == 8 else (y[0] * y[0] % p,)) != x[i]:
+            raise VerifyError(f"{tag}: root {i} is not a root of x_{i} below p")
+        if (synth.f2_sgn(y) if w == 8 else bool(y[0] & 1)) != bool(sgns[i]):
+            raise VerifyError(f"{tag}: sign {i} is {int(sgns[i])}, root {i} has the other one")
+
+
+def verify_fq_sqrt(xs, sgns, roots, square, root_ok, fq_jobs, proofs, per_proof, ctx: Optional[Context] = None,
+                   params: Optional[Params] = None):
+    """Checks an fq_sqrt: job i is ((p-1)/2, x_i), every Fq-exp proof verifies against its jobs (Context.verify with a context, else
+    verify_host), the proven Legendre symbol of job i is 1 where square[i] is set, p - 1 where it is clear and x_i != 0, and 0 for
+    x_i = 0 (where square[i] must be clear); root_ok[i] is square[i] for x_i != 0 and sgns[i] == 0 for x_i = 0; roots[i] is below p,
+    squares to x_i and has the parity sgns[i] (None: all 0) where root_ok[i] is set, and is zero where it is not.  `proofs`: objects
+    with `words`, `degree_bits` and `outputs`, such as Proof.  Returns None or raises VerifyError naming the first input or proof
+    that fails."""
+    _verify_sqrt("fq_sqrt", 4, xs, sgns, roots, square, root_ok, fq_jobs, proofs, per_proof, ctx, params)
+
+
+def verify_fq2_sqrt(xs, sgns, roots, square, root_ok, fq_jobs, proofs, per_proof, ctx: Optional[Context] = None,
+                    params: Optional[Params] = None):
+    """Checks an fq2_sqrt like verify_fq_sqrt, with job i ((p-1)/2, norm(x_i)), norm = c0^2 + c1^2 (zero only for x_i = 0), the
+    square taken in Fq2 and the sign rule of src/fields/sgn.rs:20-27: the parity of the root's c0, or of its c1 when c0 is zero."""
+    _verify_sqrt("fq2_sqrt", 8, xs, sgns, roots, square, root_ok, fq_jobs, proofs, per_proof, ctx, params)
 
 
 def verify_g2_subgroup(points, offsets, flags, g2_jobs, proofs, per_proof, ctx: Optional[Context] = None,

@@ -131,4 +131,24 @@ extern "C" {
     pub fn bn254s_job_outputs(ctx: *mut Bn254sCtx, kind: c_int, params: *const Bn254sParams, scalars: *const u64, x: *const u64,
                               offset: *const u64, n: usize, per_proof: usize, outputs_out: *mut u64,
                               proofs_out: *mut *mut Bn254sProof) -> c_int;
+    /// is_square and sqrt_with_sgn of n Fq elements (4 words each, below p; sgns: n bytes 0 | 1, null = all 0) on the device, no
+    /// proof: square_out[i] = 1 iff x_i^((p-1)/2) == 1 (0 for x_i = 0), root_ok_out[i] = 1 iff a root with the wanted parity exists,
+    /// roots_out[i] that root or zeros; fq_jobs (n x 8 words: (p-1)/2 | x_i) may be null
+    pub fn bn254s_fq_sqrt_batch(ctx: *mut Bn254sCtx, xs: *const u64, sgns: *const u8, n: usize, roots_out: *mut u64,
+                                square_out: *mut u8, root_ok_out: *mut u8, fq_jobs: *mut u64) -> c_int;
+    /// the same for Fq2 (8 words: c0, c1): the Legendre symbol of norm(x_i) (fq_jobs: (p-1)/2 | norm(x_i)); sign: the parity of c0,
+    /// or of c1 when c0 is zero
+    pub fn bn254s_fq2_sqrt_batch(ctx: *mut Bn254sCtx, xs: *const u64, sgns: *const u8, n: usize, roots_out: *mut u64,
+                                 square_out: *mut u8, root_ok_out: *mut u8, fq_jobs: *mut u64) -> c_int;
+    /// the front-end plus ceil(n / per_proof) Fq-exp proofs of the Legendre jobs, their outputs checked against the flags: 1 for a
+    /// square, p - 1 for a non-square, 0 for a zero base
+    pub fn bn254s_fq_sqrt(ctx: *mut Bn254sCtx, params: *const Bn254sParams, xs: *const u64, sgns: *const u8, n: usize,
+                          per_proof: usize, roots_out: *mut u64, square_out: *mut u8, root_ok_out: *mut u8, fq_jobs: *mut u64,
+                          fq_proofs: *mut *mut Bn254sProof) -> c_int;
+    pub fn bn254s_fq2_sqrt(ctx: *mut Bn254sCtx, params: *const Bn254sParams, xs: *const u64, sgns: *const u8, n: usize,
+                           per_proof: usize, roots_out: *mut u64, square_out: *mut u8, root_ok_out: *mut u8, fq_jobs: *mut u64,
+                           fq_proofs: *mut *mut Bn254sProof) -> c_int;
+    /// x_i^-1 of n Fq (4 words) or Fq2 (8 words) elements on the device, zeros for x_i = 0
+    pub fn bn254s_fq_inv_batch(ctx: *mut Bn254sCtx, xs: *const u64, n: usize, out: *mut u64) -> c_int;
+    pub fn bn254s_fq2_inv_batch(ctx: *mut Bn254sCtx, xs: *const u64, n: usize, out: *mut u64) -> c_int;
 }
