@@ -34,17 +34,17 @@
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
  * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x /
  * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor / bn254s_job_outputs / bn254s_map_to_g1 / bn254s_fq_sqrt /
- * bn254s_fq2_sqrt) queues behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its
+ * bn254s_fq2_sqrt / bn254s_prove_batch_checked) queues behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its
  * own, so it can never share device state with a proof of the open batch; bn254s_verify_batch uses the context's own stream and device memory that it allocates
  * and frees itself, so it is independent of open batches too; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
  * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch,
  * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch, bn254s_job_outputs_batch,
  * bn254s_hash_to_fq_batch, bn254s_map_to_g1_batch, bn254s_hash_to_g1_batch, bn254s_fq_sqrt_batch, bn254s_fq2_sqrt_batch,
- * bn254s_fq_inv_batch, bn254s_fq2_inv_batch and the front-end halves of bn254s_g1_recover_from_x,
+ * bn254s_fq_inv_batch, bn254s_fq2_inv_batch, bn254s_job_check_batch and the front-end halves of bn254s_g1_recover_from_x,
  * bn254s_g2_recover_from_x, bn254s_g2_subgroup_check, bn254s_g2_clear_cofactor, bn254s_job_outputs, bn254s_map_to_g1,
- * bn254s_fq_sqrt and bn254s_fq2_sqrt, like those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub"
+ * bn254s_fq_sqrt, bn254s_fq2_sqrt and bn254s_prove_batch_checked, like those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub"
  * for the subgroup check, "g2cof" and "g2cof.link" for cofactor clearing, "m2g.batch" for the proof-free map, "jobout" for the
- * job outputs, "m2g1", "h2f1.in" and "h2f1.out" for map_to_g1 and hash_to_fq, "fqsqrt", "fq2sqrt" and "fqinv" for the field
+ * job outputs, "jobchk" for the job check, "m2g1", "h2f1.in" and "h2f1.out" for map_to_g1 and hash_to_fq, "fqsqrt", "fq2sqrt" and "fqinv" for the field
  * gadgets) and are independent of open batches.
  */
 #ifndef BN254_STARK_H
@@ -515,11 +515,43 @@ int bn254s_job_outputs_batch(bn254s_ctx* ctx, int kind, const uint64_t* scalars 
  * for word: a mismatch is BN254S_E_INTERNAL and bn254s_last_error names the job.  A job whose output is the point at infinity
  * cannot be proven (the reference's targets cannot hold it): BN254S_E_INVALID_POINT naming the first such i, before any proof is
  * started.  Errors of the proofs themselves pass through unchanged - BN254S_E_INVALID_POINT where a running sum of the trace meets
- * a + (-a), which can happen for a job whose output is finite.  outputs_out is written on success only; on any error every proof
+ * a + (-a), which can happen for a job whose output is finite (bn254s_job_check_batch names such jobs).  outputs_out is written on success only; on any error every proof
  * of the call is freed and its slot in proofs_out is NULL.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work
  * (invalid arguments are reported first; the context is checked last). */
 int bn254s_job_outputs(bn254s_ctx* ctx, int kind, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
                        const uint64_t* offset, size_t n, size_t per_proof, uint64_t* outputs_out, bn254s_proof** proofs_out);
+/* Job check: which curve jobs can be proven at all.  The scalar-multiplication traces add sum + double in every adding row,
+ * whether or not the bit of the scalar is set, and the addition gadget cannot take opposite points: a job whose running sum meets
+ * minus its doubling makes every proving entry point fail with BN254S_E_INVALID_POINT for the whole proof, without an index.
+ * For a job (s, x, offset) of kind 0 (G1) or 1 (G2, on the twist), s the full 256-bit value, never reduced: dbl_0 = x,
+ * sum_0 = offset, and for k = 0 .. 255
+ *   step k hits iff sum_k == -dbl_k; otherwise sum_{k+1} = sum_k + dbl_k if bit k of s is set (equal points double, which can be
+ *   proven), else sum_k; dbl_{k+1} = 2 dbl_k.
+ * Equivalently step k hits iff offset == -[2^k + (s mod 2^k)] x.  A job is provable iff no step hits (DESIGN.md "Job check"): a
+ * finite output (bn254s_job_outputs_batch) is necessary for that and not sufficient - offset = -x with s = 2 has the output x.
+ *   provable_out[i] = 1 or 0;
+ *   step_out[i]     = the first hitting k, which lies in row 2k of the job's 512-row frame, or BN254S_JOB_STEP_NONE.  May be NULL.
+ * Unprovable jobs are a result, not an error: the call returns BN254S_OK.  Kind 2 (Fq exp) has no exceptional case: its
+ * coordinates are validated, every job is provable and nothing is launched; offset is not read and may be NULL.
+ * Arguments and errors are those of bn254s_job_outputs_batch with the prefix "job_check:": BN254S_E_INVALID_ARG for a NULL
+ * argument (offset only for kinds 0, 1; step_out never), n == 0, n >= UINT_MAX, a kind outside 0..2; a coordinate >= p, found on
+ * the host before any device work; a point x_i or offset_i that is not on its curve, found on the device, the smallest such i, x
+ * before offset.  Nothing is written on an error.
+ * bn254s_job_check_batch: device front-end only, no proof (csrc/job_check.hip). */
+#define BN254S_JOB_STEP_NONE 0xFFFFu
+int bn254s_job_check_batch(bn254s_ctx* ctx, int kind, const uint64_t* scalars /* n x 4 */, const uint64_t* x, const uint64_t* offset,
+                           size_t n, uint8_t* provable_out /* n */, uint16_t* step_out /* n; may be NULL */);
+/* The check followed by bn254s_prove_batch of the same jobs: if every job is provable the proofs are those of bn254s_prove_batch,
+ * byte for byte.  If any job is not, BN254S_E_INVALID_POINT before any proof is started; bn254s_last_error names the smallest such
+ * job and its step ("prove_batch_checked: job 77 cannot be proven: sum == -double at step 64 (row 128 of its frame)") and every
+ * slot of proofs_out is NULL.  Unlike the other proven calls this one fills provable_out and step_out (n_total entries each, either
+ * may be NULL) in that case as well as on success: they are the answer the caller came for.  Errors of the check (a coordinate
+ * >= p, a point off its curve) leave them untouched.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work (invalid
+ * arguments are reported first; the context is checked last). */
+int bn254s_prove_batch_checked(bn254s_ctx* ctx, int kind, const bn254s_params* params, const uint64_t* scalars,
+                               const uint64_t* x, const uint64_t* offset, size_t n_total, size_t per_proof,
+                               uint8_t* provable_out /* may be NULL */, uint16_t* step_out /* may be NULL */,
+                               bn254s_proof** proofs_out);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

@@ -23,6 +23,18 @@ class VerifyError(RuntimeError):
     """bn254s_verify rejected the proof; the message is the reference verifier's error text."""
 
 
+class UnprovableJobs(RuntimeError):
+    """prove_batch_checked found jobs whose trace meets a + (-a) (-4): `provable` [n] uint8 and `step` [n] uint16 are the answer
+    of the job check, step[i] the first hitting step of job i or JOB_STEP_NONE."""
+
+    def __init__(self, msg, provable, step):
+        super().__init__(msg)
+        self.provable, self.step = provable, step
+
+
+JOB_STEP_NONE = 0xFFFF  # BN254S_JOB_STEP_NONE
+
+
 class Params(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in (
         "struct_size", "security_bits", "num_challenges", "rate_bits", "cap_height", "pow_bits",
@@ -105,6 +117,9 @@ def load_library():
     lib.bn254s_hash_to_g2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     lib.bn254s_job_outputs_batch.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, vp, vp]
     lib.bn254s_job_outputs.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(vp)]
+    lib.bn254s_job_check_batch.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, vp, vp]
+    lib.bn254s_prove_batch_checked.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp,
+                                               C.POINTER(vp)]
     lib.bn254s_hash_to_fq2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
     if hasattr(lib, "bn254s_map_to_g1"):   # (as for bn254s_selftest_logup below: an older build in an A/B run has none of them)
         lib.bn254s_hash_to_fq.argtypes = [vp, C.c_size_t, vp]
@@ -683,6 +698,34 @@ class Context:
         self._check(self._lib.bn254s_job_outputs(self._h, kind, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof,
                                                  _ptr(outs), slots), "bn254s_job_outputs")
         return outs, _proofs(self._lib, slots)
+
+    def job_check_batch(self, kind, scalars, x, offset=None):
+        """kind, scalars, x, offset as for job_outputs_batch -> (provable [n] uint8, step [n] uint16): whether the trace of job i
+        can be proven, and the first step k at which its running sum meets minus its doubling (row 2k of its 512-row frame), or
+        JOB_STEP_NONE (bn254s_job_check_batch).  Every Fq-exp job is provable.  A coordinate >= p or a point off its curve
+        raises (-1, the message names the argument and the first such job)."""
+        _, n, scalars, x, offset = self._job_arrays(kind, scalars, x, offset)
+        provable, step = np.zeros(n, np.uint8), np.zeros(n, np.uint16)
+        self._check(self._lib.bn254s_job_check_batch(self._h, kind, _ptr(scalars), _ptr(x), _ptr(offset), n,
+                                                     provable.ctypes.data_as(C.c_void_p), step.ctypes.data_as(C.c_void_p)),
+                    "bn254s_job_check_batch")
+        return provable, step
+
+    def prove_batch_checked(self, kind, scalars, x, offset=None, per_proof=128, params: Optional[Params] = None):
+        """-> (proofs, provable, step): job_check_batch, then prove_batch(kind, ...) of the same jobs if every one is provable
+        (bn254s_prove_batch_checked); the proofs are those of prove_batch.  Otherwise nothing is proven and UnprovableJobs (-4, the
+        message names the first such job and its step) carries provable and step."""
+        params = params or default_params()
+        _, n, scalars, x, offset = self._job_arrays(kind, scalars, x, offset)
+        provable, step = np.zeros(n, np.uint8), np.zeros(n, np.uint16)
+        slots = _slots(n, per_proof)
+        rc = self._lib.bn254s_prove_batch_checked(self._h, kind, C.byref(params), _ptr(scalars), _ptr(x), _ptr(offset), n, per_proof,
+                                                  provable.ctypes.data_as(C.c_void_p), step.ctypes.data_as(C.c_void_p), slots)
+        if rc == -4 and not provable.all():
+            raise UnprovableJobs(f"bn254s_prove_batch_checked failed with -4: {self._lib.bn254s_last_error(self._h).decode()}",
+                                 provable, step)
+        self._check(rc, "bn254s_prove_batch_checked")
+        return _proofs(self._lib, slots), provable, step
 
     def ctl_values(self, kind, scalars, x, offset, outputs):
         """(input rows [n, 81|145|33], output rows [n, 33|65|17]): the extra looking values of the two CTLs."""

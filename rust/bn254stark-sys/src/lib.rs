@@ -131,6 +131,16 @@ extern "C" {
     pub fn bn254s_job_outputs(ctx: *mut Bn254sCtx, kind: c_int, params: *const Bn254sParams, scalars: *const u64, x: *const u64,
                               offset: *const u64, n: usize, per_proof: usize, outputs_out: *mut u64,
                               proofs_out: *mut *mut Bn254sProof) -> c_int;
+    /// which of n curve jobs (kind 0 = G1, 1 = G2) can be proven, on the device, no proof: provable_out[i] = 0 where the running
+    /// sum of the trace meets minus its doubling, step_out[i] (may be null) the first such step k (row 2k of the job's frame) or
+    /// BN254S_JOB_STEP_NONE = 0xFFFF.  Unprovable jobs are a result, not an error.  Every job of kind 2 is provable
+    pub fn bn254s_job_check_batch(ctx: *mut Bn254sCtx, kind: c_int, scalars: *const u64, x: *const u64, offset: *const u64,
+                                  n: usize, provable_out: *mut u8, step_out: *mut u16) -> c_int;
+    /// the check, then bn254s_prove_batch of the same jobs if every one is provable; otherwise BN254S_E_INVALID_POINT before any
+    /// proof, with provable_out and step_out (either may be null) filled all the same
+    pub fn bn254s_prove_batch_checked(ctx: *mut Bn254sCtx, kind: c_int, params: *const Bn254sParams, scalars: *const u64,
+                                      x: *const u64, offset: *const u64, n_total: usize, per_proof: usize, provable_out: *mut u8,
+                                      step_out: *mut u16, proofs_out: *mut *mut Bn254sProof) -> c_int;
     /// is_square and sqrt_with_sgn of n Fq elements (4 words each, below p; sgns: n bytes 0 | 1, null = all 0) on the device, no
     /// proof: square_out[i] = 1 iff x_i^((p-1)/2) == 1 (0 for x_i = 0), root_ok_out[i] = 1 iff a root with the wanted parity exists,
     /// roots_out[i] that root or zeros; fq_jobs (n x 8 words: (p-1)/2 | x_i) may be null
