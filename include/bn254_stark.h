@@ -34,17 +34,17 @@
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
  * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x /
  * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor / bn254s_job_outputs / bn254s_map_to_g1 / bn254s_fq_sqrt /
- * bn254s_fq2_sqrt / bn254s_prove_batch_checked) queues behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its
+ * bn254s_fq2_sqrt / bn254s_prove_batch_checked / bn254s_scalar_mul) queues behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its
  * own, so it can never share device state with a proof of the open batch; bn254s_verify_batch uses the context's own stream and device memory that it allocates
  * and frees itself, so it is independent of open batches too; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
  * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch,
  * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch, bn254s_job_outputs_batch,
  * bn254s_hash_to_fq_batch, bn254s_map_to_g1_batch, bn254s_hash_to_g1_batch, bn254s_fq_sqrt_batch, bn254s_fq2_sqrt_batch,
- * bn254s_fq_inv_batch, bn254s_fq2_inv_batch, bn254s_job_check_batch and the front-end halves of bn254s_g1_recover_from_x,
+ * bn254s_fq_inv_batch, bn254s_fq2_inv_batch, bn254s_job_check_batch, bn254s_scalar_mul_batch and the front-end halves of bn254s_g1_recover_from_x,
  * bn254s_g2_recover_from_x, bn254s_g2_subgroup_check, bn254s_g2_clear_cofactor, bn254s_job_outputs, bn254s_map_to_g1,
- * bn254s_fq_sqrt, bn254s_fq2_sqrt and bn254s_prove_batch_checked, like those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub"
+ * bn254s_fq_sqrt, bn254s_fq2_sqrt, bn254s_prove_batch_checked and bn254s_scalar_mul, like those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub"
  * for the subgroup check, "g2cof" and "g2cof.link" for cofactor clearing, "m2g.batch" for the proof-free map, "jobout" for the
- * job outputs, "jobchk" for the job check, "m2g1", "h2f1.in" and "h2f1.out" for map_to_g1 and hash_to_fq, "fqsqrt", "fq2sqrt" and "fqinv" for the field
+ * job outputs, "jobchk" for the job check, "smul" for the scalar multiplication without an offset, "m2g1", "h2f1.in" and "h2f1.out" for map_to_g1 and hash_to_fq, "fqsqrt", "fq2sqrt" and "fqinv" for the field
  * gadgets) and are independent of open batches.
  */
 #ifndef BN254_STARK_H
@@ -552,6 +552,44 @@ int bn254s_prove_batch_checked(bn254s_ctx* ctx, int kind, const bn254s_params* p
                                const uint64_t* x, const uint64_t* offset, size_t n_total, size_t per_proof,
                                uint8_t* provable_out /* may be NULL */, uint16_t* step_out /* may be NULL */,
                                bn254s_proof** proofs_out);
+/* Scalar multiplication without an offset argument: products_out[i] = s_i x_i.  Every proving entry point above proves the
+ * reference's statement s x + offset and leaves it to the caller to find offsets "as set_random_g1 / set_random_g2 draw them" and
+ * to subtract them again (src/utils/g1_msm.rs:22-36, src/utils/hash_to_g2.rs:184-201).  This call draws the offsets, checks them
+ * against the jobs, redraws the few that cannot be proven, and subtracts, all on the device (csrc/scalar_mul.hip; DESIGN.md
+ * "Scalar multiplication without an offset").  kind 0 = G1, 1 = G2 (on the twist); PW = 8 | 16 words per point; scalars are the
+ * full 256-bit values, never reduced.
+ *   offset of job i at attempt a = 0, 1, ...: bn254s_hash_to_g1_batch | bn254s_hash_to_g2_batch of the eight Goldilocks elements
+ *       seed[0], seed[1], seed[2], seed[3], i mod 2^32, i >> 32, a, 0x62736D00 + kind
+ *     - a function of seed, i, a and kind alone, not of n, of the other jobs or of how the call is cut into proofs;
+ *   attempts_out[i] = the smallest a < max_attempts for which (s_i, x_i, offset_i^(a)) is provable in the sense of
+ *     bn254s_job_check_batch; offsets_out[i] = that offset.  If job i has no such a: BN254S_E_INVALID_POINT, and bn254s_last_error
+ *     names the smallest such i with the step and row of its last attempt ("scalar_mul: job 77 cannot be proven: sum == -double at
+ *     step 64 (row 128 of its frame) with the offset of attempt 3, the last of 4");
+ *   outputs_out[i]  = s_i x_i + offsets_out[i]: what bn254s_proof_outputs of the proof holds; always finite;
+ *   products_out[i] = outputs_out[i] - offsets_out[i] = s_i x_i, affine, every coordinate below p;
+ *   finite_out[i]   = 1, or 0 with zero words in products_out[i] where s_i x_i is the point at infinity (s = 0, a multiple of the
+ *     order of x, on the twist a point whose order divides s): a result, not an error.
+ * The seed may be public: an x that is made to hit the offset of attempt 0 is answered with attempt 1, whose offset the same x
+ * cannot also hit unless its maker solves a discrete logarithm between two hashed points.
+ * BN254S_E_INVALID_ARG before any device work, nothing written: a NULL pointer (outputs_out and attempts_out may be NULL), n == 0,
+ * n >= UINT_MAX, a kind outside 0..1 (Fq exp has no offset), max_attempts outside 1..8, a seed word that is not a canonical
+ * Goldilocks element, a coordinate of x that is p or more (bn254s_last_error names "x_<i>", the first such i).  A point x_i off its
+ * curve is found on the device before anything is written: BN254S_E_INVALID_ARG naming the smallest i.  A failed device self-check
+ * (a drawn point or a product off its curve) is BN254S_E_INTERNAL.
+ * bn254s_scalar_mul_batch: device front-end only, no proof. */
+int bn254s_scalar_mul_batch(bn254s_ctx* ctx, int kind, const uint64_t* scalars /* n x 4 */, const uint64_t* x /* n x 8 | 16 */,
+                            size_t n, const uint64_t seed[4], int max_attempts, uint64_t* products_out /* n x PW */,
+                            uint8_t* finite_out /* n */, uint64_t* offsets_out /* n x PW */,
+                            uint64_t* outputs_out /* may be NULL: n x PW */, uint8_t* attempts_out /* may be NULL: n */);
+/* The front-end followed by bn254s_prove_batch(kind, ..., offsets_out, n, per_proof).  The concatenated outputs of the proofs must
+ * equal the front-end's word for word: a mismatch is BN254S_E_INTERNAL and bn254s_last_error names the job.  scalars, x,
+ * offsets_out, outputs_out and the proofs are exactly the arguments of bn254s_verify / bn254s_verify_batch.  Every output is
+ * written on success only; on any error every proof of the call is freed and its slot in proofs_out is NULL.  per_proof > 16384:
+ * BN254S_E_UNSUPPORTED before any device work (invalid arguments are reported first; the context is checked last). */
+int bn254s_scalar_mul(bn254s_ctx* ctx, int kind, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x, size_t n,
+                      size_t per_proof, const uint64_t seed[4], int max_attempts, uint64_t* products_out, uint8_t* finite_out,
+                      uint64_t* offsets_out, uint64_t* outputs_out, uint8_t* attempts_out,
+                      bn254s_proof** proofs_out /* ceil(n / per_proof) */);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 #include "job_curve.h"
+#include "job_device.h"
 #include "proven_jobs.h"
 
 namespace {
@@ -74,6 +75,19 @@ __global__ __launch_bounds__(WL_LANES) void k_job_check(const u64* __restrict__ 
   step[i] = (unsigned short)hit;
 }
 
+}  // namespace
+
+int bn254s_job_check_device(bn254s_ctx* c, int kind, const u64* d_scalars, const u64* d_x, const u64* d_offset, size_t n,
+                            unsigned short* d_step, unsigned* d_bad) {
+  const unsigned blocks = (unsigned)((n + WL_LANES - 1) / WL_LANES);
+  if (kind == 0) k_job_check<G1><<<blocks, WL_LANES, 0, c->stream>>>(d_scalars, d_x, d_offset, n, d_step, d_bad);
+  else k_job_check<G2><<<blocks, WL_LANES, 0, c->stream>>>(d_scalars, d_x, d_offset, n, d_step, d_bad);
+  HIP_TRY(c, hipGetLastError());
+  return BN254S_OK;
+}
+
+namespace {
+
 // The front-end into host memory: provable[n] and, where it is asked for, step[n].  Nothing is written on an error.
 int jobchk_front(bn254s_ctx* c, int kind, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, size_t n,
                  uint8_t* provable, uint16_t* step) {
@@ -96,10 +110,8 @@ int jobchk_front(bn254s_ctx* c, int kind, const uint64_t* scalars, const uint64_
     HIP_TRY(c, hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_x, x, n * PW * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_off, offset, n * PW * 8, hipMemcpyHostToDevice, st));
-    const unsigned blocks = (unsigned)((n + WL_LANES - 1) / WL_LANES);
-    if (kind == 0) k_job_check<G1><<<blocks, WL_LANES, 0, st>>>(d_s, d_x, d_off, n, d_step, d_bad);
-    else k_job_check<G2><<<blocks, WL_LANES, 0, st>>>(d_s, d_x, d_off, n, d_step, d_bad);
-    HIP_TRY(c, hipGetLastError());
+    const int rc = bn254s_job_check_device(c, kind, d_s, d_x, d_off, n, d_step, d_bad);
+    if (rc != BN254S_OK) return rc;
     unsigned h_bad[2] = {UINT_MAX, UINT_MAX};
     HIP_TRY(c, hipMemcpyAsync(h_bad, d_bad, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(h_step.data(), d_step, n * 2, hipMemcpyDeviceToHost, st));

@@ -1,4 +1,4 @@
-// What the one-lane-per-job front-ends of curve jobs share (job_outputs.hip, job_check.hip): the trait that names a curve for
+// What the one-lane-per-job front-ends of curve jobs share (job_outputs.hip, job_check.hip, scalar_mul.hip): the trait that names a curve for
 // window_ladder.h, with the load of an affine point from canonical words and its on-curve test, and the predicate on the
 // pointers and the count of a batch of jobs.
 #pragma once

@@ -36,6 +36,7 @@
 #include <string>
 #include <vector>
 #include "job_curve.h"
+#include "job_device.h"
 #include "proven_jobs.h"
 
 namespace {
@@ -95,6 +96,21 @@ __global__ __launch_bounds__(WL_LANES) void k_job_outputs(const u64* __restrict_
   }
 }
 
+}  // namespace
+
+int bn254s_job_outputs_device(bn254s_ctx* c, int kind, const u64* d_scalars, const u64* d_x, const u64* d_offset, size_t n, u64* d_out,
+                              unsigned char* d_finite, unsigned* d_bad) {
+  const unsigned blocks = (unsigned)((n + WL_LANES - 1) / WL_LANES);
+  hipStream_t st = c->stream;
+  if (kind == 0) k_job_outputs<G1><<<blocks, WL_LANES, 0, st>>>(d_scalars, d_x, d_offset, n, d_out, d_finite, d_bad);
+  else if (kind == 1) k_job_outputs<G2><<<blocks, WL_LANES, 0, st>>>(d_scalars, d_x, d_offset, n, d_out, d_finite, d_bad);
+  else k_job_outputs<FqExp><<<blocks, WL_LANES, 0, st>>>(d_scalars, d_x, d_offset, n, d_out, d_finite, d_bad);
+  HIP_TRY(c, hipGetLastError());
+  return BN254S_OK;
+}
+
+namespace {
+
 // The front-end into host memory: outputs[n x PW], finite[n].  Nothing is written on an error.
 int jobout_front(bn254s_ctx* c, int kind, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, size_t n,
                  uint64_t* outputs, uint8_t* finite) {
@@ -116,11 +132,8 @@ int jobout_front(bn254s_ctx* c, int kind, const uint64_t* scalars, const uint64_
   HIP_TRY(c, hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_x, x, n * PW * 8, hipMemcpyHostToDevice, st));
   if (curve) HIP_TRY(c, hipMemcpyAsync(d_off, offset, n * PW * 8, hipMemcpyHostToDevice, st));
-  const unsigned blocks = (unsigned)((n + WL_LANES - 1) / WL_LANES);
-  if (kind == 0) k_job_outputs<G1><<<blocks, WL_LANES, 0, st>>>(d_s, d_x, d_off, n, d_out, d_fin, d_bad);
-  else if (kind == 1) k_job_outputs<G2><<<blocks, WL_LANES, 0, st>>>(d_s, d_x, d_off, n, d_out, d_fin, d_bad);
-  else k_job_outputs<FqExp><<<blocks, WL_LANES, 0, st>>>(d_s, d_x, d_off, n, d_out, d_fin, d_bad);
-  HIP_TRY(c, hipGetLastError());
+  const int rc = bn254s_job_outputs_device(c, kind, d_s, d_x, d_off, n, d_out, d_fin, d_bad);
+  if (rc != BN254S_OK) return rc;
   unsigned h_bad[2] = {UINT_MAX, UINT_MAX};
   HIP_TRY(c, hipMemcpyAsync(h_bad, d_bad, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));

@@ -20,6 +20,7 @@
 #include <vector>
 #include "fq2_root.h"  // fq_select, fq_from_limbs
 #include "hash_to_fq.h"
+#include "job_device.h"
 #include "proven_jobs.h"
 #include "sqrt_ladder.h"
 #include "map_to_g1_constants.inc"
@@ -108,6 +109,17 @@ __global__ __launch_bounds__(64) void k_hash_to_fq(const u64* __restrict__ in, s
 // words of the front-end's device buffer: u (4n), points (8n), jobs (16n), err (1), flags (2n bytes)
 size_t m2g1_words(size_t n) { return 28 * n + 1 + (2 * n + 7) / 8; }
 
+// k_m2g1_point on the workspace d (m2g1_words(n) words on the device, u in its first 4n, then points, jobs, err, flags), not waited for
+int m2g1_launch(bn254s_ctx* c, u64* d, size_t n) {
+  u64 *d_pts = d + 4 * n, *d_jobs = d_pts + 8 * n;
+  int* d_err = (int*)(d_jobs + 16 * n);
+  HIP_TRY(c, hipMemsetAsync(d_err, 0, 8, c->stream));
+  k_m2g1_point<<<(unsigned)((n + G1R_LANES - 1) / G1R_LANES), G1R_LANES, 0, c->stream>>>(d, n, d_pts, (unsigned char*)(d_jobs + 16 * n + 1),
+                                                                                        d_jobs, d_err);
+  HIP_TRY(c, hipGetLastError());
+  return BN254S_OK;
+}
+
 // d (m2g1_words(n) words on the device, u in its first 4n) -> points[n x 8], flags[2n], jobs[2n x 8] in host memory (flags and
 // jobs may be NULL).  Nothing is written on an error.
 int m2g1_on_device(bn254s_ctx* c, const char* tag, u64* d, size_t n, uint64_t* points, uint8_t* flags, uint64_t* jobs) {
@@ -117,9 +129,8 @@ int m2g1_on_device(bn254s_ctx* c, const char* tag, u64* d, size_t n, uint64_t* p
   u64* d_jobs = d_pts + 8 * n;
   int* d_err = (int*)(d_jobs + 16 * n);
   unsigned char* d_flags = (unsigned char*)(d_jobs + 16 * n + 1);
-  HIP_TRY(c, hipMemsetAsync(d_err, 0, 8, st));
-  k_m2g1_point<<<(unsigned)((n + G1R_LANES - 1) / G1R_LANES), G1R_LANES, 0, st>>>(d_u, n, d_pts, d_flags, d_jobs, d_err);
-  HIP_TRY(c, hipGetLastError());
+  const int rc = m2g1_launch(c, d, n);
+  if (rc != BN254S_OK) return rc;
   int h_err = 0;
   HIP_TRY(c, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
@@ -145,6 +156,15 @@ int m2g1_front(bn254s_ctx* c, const char* tag, const uint64_t* u, size_t n, uint
 }
 
 }  // namespace
+
+size_t bn254s_hash_to_g1_device_words(size_t n) { return m2g1_words(n); }
+
+int bn254s_hash_to_g1_device(bn254s_ctx* c, const u64* d_in, size_t n, size_t len, u64* d_work, HashedPoints* at) {
+  k_hash_to_fq<<<(unsigned)((n + 63) / 64), 64, 0, c->stream>>>(d_in, n, len, d_work);
+  HIP_TRY(c, hipGetLastError());
+  *at = {d_work + 4 * n, (const int*)(d_work + 28 * n), nullptr, nullptr};
+  return m2g1_launch(c, d_work, n);
+}
 
 extern "C" int bn254s_hash_to_fq(const uint64_t* input, size_t len, uint64_t* out) {
   if ((!input && len) || !out) return BN254S_E_INVALID_ARG;

@@ -22,6 +22,7 @@
 #include "fq2_root.h"
 #include "g2_cofactor.h"
 #include "hash_to_fq.h"
+#include "job_device.h"
 #include "proven_jobs.h"
 #include "transcript.h"
 #include "../../include/bn254_stark.h"
@@ -327,6 +328,20 @@ extern "C" int bn254s_map_to_g2(bn254s_ctx* c, const bn254s_params* params, cons
 
 namespace {
 
+// k_m2g_point and k_g2_clear_cofactor on the workspace d (m2g_batch_words(n) words on the device: u in its first 8n, then the
+// mapped points, their images, err, bad, finite), not waited for
+int map_to_g2_launch(bn254s_ctx* c, u64* d, size_t n) {
+  hipStream_t st = c->stream;
+  u64 *d_pts = d + 8 * n, *d_img = d_pts + 16 * n;
+  int* d_err = (int*)(d_img + 16 * n);
+  unsigned* d_bad = (unsigned*)(d_img + 16 * n + 1);
+  HIP_TRY(c, hipMemsetAsync(d_err, 0, 8, st));
+  HIP_TRY(c, hipMemsetAsync(d_bad, 0xFF, 8, st));
+  k_m2g_point<<<(unsigned)((n + G1R_LANES - 1) / G1R_LANES), G1R_LANES, 0, st>>>(d, n, host_consts(), d_pts, d_err);
+  HIP_TRY(c, hipGetLastError());
+  return bn254s_g2_clear_cofactor_device(c, d_pts, n, d_img, (unsigned char*)(d_img + 16 * n + 2), d_bad);
+}
+
 // d_u (n x 8 canonical words on the device, in the buffer d of 8n + 16n + 16n + 2 + ceil(n/8) words that starts with it) ->
 // out_points: k_m2g_point, then k_g2_clear_cofactor on its points.  Nothing is written on an error.
 int map_to_g2_on_device(bn254s_ctx* c, const char* tag, u64* d, size_t n, uint64_t* out_points) {
@@ -338,11 +353,7 @@ int map_to_g2_on_device(bn254s_ctx* c, const char* tag, u64* d, size_t n, uint64
   unsigned* d_bad = (unsigned*)(d_img + 16 * n + 1);
   unsigned char* d_fin = (unsigned char*)(d_img + 16 * n + 2);
   const std::string who = std::string(tag) + ": ";
-  HIP_TRY(c, hipMemsetAsync(d_err, 0, 8, st));
-  HIP_TRY(c, hipMemsetAsync(d_bad, 0xFF, 8, st));
-  k_m2g_point<<<(unsigned)((n + G1R_LANES - 1) / G1R_LANES), G1R_LANES, 0, st>>>(d_u, n, host_consts(), d_pts, d_err);
-  HIP_TRY(c, hipGetLastError());
-  int rc = bn254s_g2_clear_cofactor_device(c, d_pts, n, d_img, d_fin, d_bad);
+  int rc = map_to_g2_launch(c, d, n);
   if (rc != BN254S_OK) return rc;
   int h_err = 0;
   unsigned h_bad = UINT_MAX;
@@ -371,6 +382,16 @@ int map_to_g2_on_device(bn254s_ctx* c, const char* tag, u64* d, size_t n, uint64
 size_t m2g_batch_words(size_t n) { return 40 * n + 2 + (n + 7) / 8; }
 
 }  // namespace
+
+size_t bn254s_hash_to_g2_device_words(size_t n) { return m2g_batch_words(n); }
+
+int bn254s_hash_to_g2_device(bn254s_ctx* c, const u64* d_in, size_t n, size_t len, u64* d_work, HashedPoints* at) {
+  k_hash_to_fq2<<<(unsigned)((n + 63) / 64), 64, 0, c->stream>>>(d_in, n, len, d_work);
+  HIP_TRY(c, hipGetLastError());
+  *at = {d_work + 24 * n, (const int*)(d_work + 40 * n), (const unsigned*)(d_work + 40 * n + 1),
+         (const unsigned char*)(d_work + 40 * n + 2)};
+  return map_to_g2_launch(c, d_work, n);
+}
 
 // The reference's native map_to_g2 (hash_to_g2.rs:113-148) without proofs: the point bn254s_map_to_g2 reads from its proofs.
 extern "C" int bn254s_map_to_g2_batch(bn254s_ctx* c, const uint64_t* u, size_t n, uint64_t* out_points) {

@@ -1,4 +1,4 @@
-// Host half of the proven front-ends (msm.hip, job_outputs.hip, job_check.hip, g1_recover.hip, g2_recover.hip, g2_subgroup.hip, g2_cofactor.hip,
+// Host half of the proven front-ends (msm.hip, job_outputs.hip, job_check.hip, scalar_mul.hip, g1_recover.hip, g2_recover.hip, g2_subgroup.hip, g2_cofactor.hip,
 // map_to_g1.hip, map_to_g2.hip, field_gadgets.hip): the range check of coordinates, the argument ladder of the full calls, "prove the jobs and collect
 // their outputs", the release of the proofs on an error, and the linkage of Legendre jobs to their flags.  Host code only.
 // A front-end brings its kernel, its own pointer / n predicate and its linkage rule: a flat loop over the collected outputs

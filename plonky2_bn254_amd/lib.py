@@ -121,6 +121,10 @@ def load_library():
     lib.bn254s_prove_batch_checked.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp,
                                                C.POINTER(vp)]
     lib.bn254s_hash_to_fq2_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+    if hasattr(lib, "bn254s_scalar_mul"):   # (as below: an older build in an A/B run has neither of the two)
+        lib.bn254s_scalar_mul_batch.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, vp, C.c_int, vp, vp, vp, vp, vp]
+        lib.bn254s_scalar_mul.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int, vp, vp, vp, vp,
+                                          vp, C.POINTER(vp)]
     if hasattr(lib, "bn254s_map_to_g1"):   # (as for bn254s_selftest_logup below: an older build in an A/B run has none of them)
         lib.bn254s_hash_to_fq.argtypes = [vp, C.c_size_t, vp]
         lib.bn254s_hash_to_fq_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
@@ -726,6 +730,42 @@ class Context:
                                  provable, step)
         self._check(rc, "bn254s_prove_batch_checked")
         return _proofs(self._lib, slots), provable, step
+
+    def _scalar_mul_arrays(self, kind, scalars, x, seed):
+        pw, n, scalars, x, _ = self._job_arrays(kind, scalars, x, None)
+        seed = np.ascontiguousarray(seed, dtype=np.uint64)
+        if seed.shape != (4,):
+            raise ValueError(f"scalar_mul: seed {seed.shape}, four Goldilocks elements expected")
+        out = (np.zeros((n, pw), np.uint64), np.zeros(n, np.uint8), np.zeros((n, pw), np.uint64), np.zeros((n, pw), np.uint64),
+               np.zeros(n, np.uint8))
+        return n, scalars, x, seed, out
+
+    def scalar_mul_batch(self, kind, scalars, x, seed, max_attempts=4):
+        """kind 0 = G1, 1 = G2; scalars [n,4], x [n, 8 | 16], seed [4] canonical Goldilocks elements -> (products [n, 8 | 16],
+        finite [n] uint8, offsets, outputs [n, 8 | 16], attempts [n] uint8): products[i] = s_i x_i with the offsets drawn from the
+        seed, checked against the jobs and redrawn where a job could not be proven, on the device, no proof
+        (bn254s_scalar_mul_batch).  offsets[i] = hash_to_g1 | hash_to_g2 of (seed, i mod 2^32, i >> 32, attempts[i],
+        0x62736D00 + kind), outputs[i] = s_i x_i + offsets[i].  Where finite[i] is 0 the product is the point at infinity and
+        products[i] is zeros.  A job that no attempt below max_attempts can prove raises (-4, the message names it, its step and
+        row)."""
+        n, scalars, x, seed, (prods, finite, offs, outs, att) = self._scalar_mul_arrays(kind, scalars, x, seed)
+        u8 = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.bn254s_scalar_mul_batch(self._h, kind, _ptr(scalars), _ptr(x), n, _ptr(seed), max_attempts, _ptr(prods),
+                                                      u8(finite), _ptr(offs), _ptr(outs), u8(att)), "bn254s_scalar_mul_batch")
+        return prods, finite, offs, outs, att
+
+    def scalar_mul(self, kind, scalars, x, seed, max_attempts=4, per_proof=128, params: Optional[Params] = None):
+        """-> (products, finite, offsets, outputs, attempts, proofs): the front-end plus prove_batch(kind, scalars, x, offsets) of
+        the same jobs, the outputs of the proofs checked word for word against the front-end's (bn254s_scalar_mul).  scalars, x,
+        offsets, outputs and the proofs are what verify / verify_batch take."""
+        params = params or default_params()
+        n, scalars, x, seed, (prods, finite, offs, outs, att) = self._scalar_mul_arrays(kind, scalars, x, seed)
+        u8 = lambda a: a.ctypes.data_as(C.c_void_p)
+        slots = _slots(n, per_proof)
+        self._check(self._lib.bn254s_scalar_mul(self._h, kind, C.byref(params), _ptr(scalars), _ptr(x), n, per_proof, _ptr(seed),
+                                                max_attempts, _ptr(prods), u8(finite), _ptr(offs), _ptr(outs), u8(att), slots),
+                    "bn254s_scalar_mul")
+        return prods, finite, offs, outs, att, _proofs(self._lib, slots)
 
     def ctl_values(self, kind, scalars, x, offset, outputs):
         """(input rows [n, 81|145|33], output rows [n, 33|65|17]): the extra looking values of the two CTLs."""
