@@ -34,17 +34,17 @@
  * the context may still be entered, one call at a time, and every proving entry point (bn254s_prove_g1 / _g2 / _fq_exp /
  * _batch* / bn254s_map_to_g2 / bn254s_g1_msm / bn254s_g2_msm / bn254s_g1_recover_from_x / bn254s_g2_recover_from_x /
  * bn254s_g2_subgroup_check / bn254s_g2_clear_cofactor / bn254s_job_outputs / bn254s_map_to_g1 / bn254s_fq_sqrt /
- * bn254s_fq2_sqrt / bn254s_prove_batch_checked / bn254s_scalar_mul) queues behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its
+ * bn254s_fq2_sqrt / bn254s_prove_batch_checked / bn254s_scalar_mul / bn254s_msm_multi) queues behind the open batches on the same worker pool and runs on a free slot (stream + workspace) of its
  * own, so it can never share device state with a proof of the open batch; bn254s_verify_batch uses the context's own stream and device memory that it allocates
  * and frees itself, so it is independent of open batches too; bn254s_verify, _commit_values, _generate_trace, the _bench_* calls and the device
  * front-ends (bn254s_g1_recover_from_x_batch, bn254s_g2_recover_from_x_batch, bn254s_g2_subgroup_check_batch,
  * bn254s_g2_clear_cofactor_batch, bn254s_map_to_g2_batch, bn254s_hash_to_g2_batch, bn254s_job_outputs_batch,
  * bn254s_hash_to_fq_batch, bn254s_map_to_g1_batch, bn254s_hash_to_g1_batch, bn254s_fq_sqrt_batch, bn254s_fq2_sqrt_batch,
- * bn254s_fq_inv_batch, bn254s_fq2_inv_batch, bn254s_job_check_batch, bn254s_scalar_mul_batch and the front-end halves of bn254s_g1_recover_from_x,
+ * bn254s_fq_inv_batch, bn254s_fq2_inv_batch, bn254s_job_check_batch, bn254s_scalar_mul_batch, bn254s_msm_multi_chain and the front-end halves of bn254s_g1_recover_from_x,
  * bn254s_g2_recover_from_x, bn254s_g2_subgroup_check, bn254s_g2_clear_cofactor, bn254s_job_outputs, bn254s_map_to_g1,
- * bn254s_fq_sqrt, bn254s_fq2_sqrt, bn254s_prove_batch_checked and bn254s_scalar_mul, like those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub"
+ * bn254s_fq_sqrt, bn254s_fq2_sqrt, bn254s_prove_batch_checked, bn254s_scalar_mul and bn254s_msm_multi, like those of bn254s_map_to_g2 and the msm chains) use the context's own stream and pooled buffers under keys of their own ("g2sub"
  * for the subgroup check, "g2cof" and "g2cof.link" for cofactor clearing, "m2g.batch" for the proof-free map, "jobout" for the
- * job outputs, "jobchk" for the job check, "smul" for the scalar multiplication without an offset, "m2g1", "h2f1.in" and "h2f1.out" for map_to_g1 and hash_to_fq, "fqsqrt", "fq2sqrt" and "fqinv" for the field
+ * job outputs, "jobchk" for the job check, "smul" for the scalar multiplication without an offset, "msm.multi" for many MSMs in one chain, "m2g1", "h2f1.in" and "h2f1.out" for map_to_g1 and hash_to_fq, "fqsqrt", "fq2sqrt" and "fqinv" for the field
  * gadgets) and are independent of open batches.
  */
 #ifndef BN254_STARK_H
@@ -590,6 +590,54 @@ int bn254s_scalar_mul(bn254s_ctx* ctx, int kind, const bn254s_params* params, co
                       size_t per_proof, const uint64_t seed[4], int max_attempts, uint64_t* products_out, uint8_t* finite_out,
                       uint64_t* offsets_out, uint64_t* outputs_out, uint8_t* attempts_out,
                       bn254s_proof** proofs_out /* ceil(n / per_proof) */);
+/* Many multi-scalar multiplications as one segmented chain: m MSMs, MSM j with seg_len[j] >= 1 inputs stored one after the other,
+ * n = sum seg_len[j] inputs in all (csrc/msm.hip; DESIGN.md "Many MSMs in one chain").  The reference puts the links of every
+ * g1_msm of a circuit into one STARK (src/hook.rs:63-71); bn254s_g1_msm / bn254s_g2_msm take one MSM per call, bring one random
+ * point R per call and fail as a whole where a partial sum is infinity.  kind 0 = G1, 1 = G2 (on the twist); PW = 8 | 16 words
+ * per point; scalars are the full 256-bit values, never reduced.  For input i, the t-th of MSM j, with T_{j,t} the sum of s x over
+ * the first t inputs of MSM j (without R; it may be the point at infinity):
+ *   offsets_out[i] = R_j + T_{j,t}      (R_j itself for t = 0)
+ *   outputs_out[i] = R_j + T_{j,t+1}    (the offset of the next link)
+ *   results_out[j] = T_{j,seg_len[j]}, affine, taken from the scan and not from outputs - R: it does not depend on R_j and is
+ *     returned for every MSM, provable or not;
+ *   finite_out[j]  = 1, or 0 with zero words in results_out[j] where the MSM is the point at infinity: a result, not an error.
+ * MSM j is provable under R_j iff every link (s_i, x_i, offsets_out[i]) is provable in the sense of bn254s_job_check_batch (an
+ * infinite output implies that its link hits at the top set bit of s_i, so the first bad link is always a hit on a finite offset):
+ *   bad_link_out[j] = the smallest local t whose link hits, or BN254S_MSM_LINK_NONE; bad_step_out[j] = its step, or
+ *     BN254S_JOB_STEP_NONE.  The rows of a bad MSM in offsets_out and outputs_out are zero words.
+ * Where R comes from:
+ *   R != NULL: m caller-supplied points, one attempt; seed and max_attempts are not read, attempts_out[j] = 0;
+ *   R == NULL: R_j at attempt a = bn254s_hash_to_g1_batch | bn254s_hash_to_g2_batch of the eight Goldilocks elements
+ *       seed[0], seed[1], seed[2], seed[3], j mod 2^32, j >> 32, a, 0x626D6D00 + kind
+ *     - a function of seed, j, a and kind alone; attempts_out[j] = the smallest a < max_attempts (1..8) under which MSM j is
+ *     provable, R_out[j] = that point.  An MSM with no such attempt keeps the bad_link / bad_step (and the point in R_out) of its
+ *     last attempt, and attempts_out[j] = max_attempts.  On G2 a drawn point whose cleared image is infinity counts as a failed
+ *     attempt (link 0, no step).
+ * bn254s_msm_multi_chain: device front-end only, no proof.  Unprovable MSMs are a result: it returns BN254S_OK.
+ * BN254S_E_INVALID_ARG before any device work, nothing written: a NULL pointer (R_out, attempts_out and bad_step_out may be NULL;
+ * R or seed, not both), m == 0, some seg_len[j] == 0, sum seg_len != n, n >= UINT_MAX, a kind outside 0..1, drawn offsets with
+ * max_attempts outside 1..8 or a seed word that is not a canonical Goldilocks element, a coordinate of x or R that is p or more
+ * (bn254s_last_error names "x_<i>" / "R_<j>").  A point x_i or R_j off its curve is found on the device before anything is
+ * written: BN254S_E_INVALID_ARG naming the smallest index, x before R.  A failed device self-check is BN254S_E_INTERNAL. */
+#define BN254S_MSM_LINK_NONE 0xFFFFFFFFu
+int bn254s_msm_multi_chain(bn254s_ctx* ctx, int kind, const uint64_t* scalars /* n x 4 */, const uint64_t* x /* n x PW */,
+                           const size_t* seg_len /* m */, size_t m, size_t n, const uint64_t* R /* m x PW or NULL */,
+                           const uint64_t* seed /* 4, read when R == NULL */, int max_attempts, uint64_t* results_out /* m x PW */,
+                           uint8_t* finite_out /* m */, uint64_t* offsets_out /* n x PW */, uint64_t* outputs_out /* n x PW */,
+                           uint64_t* R_out /* may be NULL: m x PW */, uint8_t* attempts_out /* may be NULL: m */,
+                           uint32_t* bad_link_out /* m */, uint16_t* bad_step_out /* may be NULL: m */);
+/* The front-end followed by bn254s_prove_batch(kind, scalars, x, offsets_out, n, per_proof): the n links are cut by per_proof
+ * regardless of MSM boundaries, as the hook does.  The concatenated outputs of the proofs must equal outputs_out word for word: a
+ * mismatch is BN254S_E_INTERNAL and bn254s_last_error names the job.  If any MSM is unprovable: BN254S_E_INVALID_POINT before any
+ * proof, naming the smallest such MSM ("msm_multi: msm 3 cannot be proven: link 17, sum == -double at step 64 (row 128 of its
+ * frame) with the offset of attempt 3, the last of 4"; "... with the supplied offset" for R != NULL).  Every output is written on
+ * success only; on any error every slot in proofs_out is NULL.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work
+ * (invalid arguments are reported first; the context is checked last). */
+int bn254s_msm_multi(bn254s_ctx* ctx, int kind, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
+                     const size_t* seg_len, size_t m, size_t n, const uint64_t* R, const uint64_t* seed, int max_attempts,
+                     size_t per_proof, uint64_t* results_out, uint8_t* finite_out, uint64_t* offsets_out, uint64_t* outputs_out,
+                     uint64_t* R_out, uint8_t* attempts_out, uint32_t* bad_link_out, uint16_t* bad_step_out,
+                     bn254s_proof** proofs_out /* ceil(n / per_proof) */);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

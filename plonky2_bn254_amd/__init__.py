@@ -10,4 +10,4 @@ import os as _os
 # one hardware queue per proof in flight (see csrc/capi.hip); must be in the environment before the HIP runtime starts
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-from .lib import Context, JOB_STEP_NONE, Proof, UnprovableJobs, load_library, LibraryMissing, VerifyError, default_params, proof_plan, proof_words, prove_batch_multi, query_round, query_text, verify_g1_msm, verify_g1_recover, verify_g2_clear_cofactor, verify_g2_msm, verify_g2_recover, verify_batch_host, verify_fq2_sqrt, verify_fq_sqrt, verify_front, verify_g2_subgroup, verify_host, verify_job_outputs, verify_map_to_g1  # noqa: F401
+from .lib import Context, JOB_STEP_NONE, MSM_LINK_NONE, MsmMulti, verify_msm_multi, Proof, UnprovableJobs, load_library, LibraryMissing, VerifyError, default_params, proof_plan, proof_words, prove_batch_multi, query_round, query_text, verify_g1_msm, verify_g1_recover, verify_g2_clear_cofactor, verify_g2_msm, verify_g2_recover, verify_batch_host, verify_fq2_sqrt, verify_fq_sqrt, verify_front, verify_g2_subgroup, verify_host, verify_job_outputs, verify_map_to_g1  # noqa: F401

@@ -113,3 +113,25 @@ __device__ __forceinline__ void pt_scan256(P& f, u64* sh, int k) {
     __syncthreads();
   }
 }
+
+// The segmented twin: lane k also holds a head flag, and a head cuts the sum, (f1, p1) + (f2, p2) = (f1 | f2, f2 ? p2 : p1 + p2).
+// Lane k ends with the sum from the last head at or before it (from lane 0 if there is none) up to itself, and with flag = "a head
+// lies in lanes 0 .. k".  sh as above; shf: 256 flag words.
+template <class P>
+__device__ __forceinline__ void pt_seg_scan256(P& f, unsigned& flag, u64* sh, unsigned* shf, int k) {
+#pragma unroll 1
+  for (int d = 1; d < 256; d <<= 1) {
+    lds_put(sh, k, f);
+    shf[k] = flag;
+    __syncthreads();
+    if (k >= d) {
+      if (!flag) {
+        P q;
+        lds_get(sh, k - d, q);
+        f = pt_add_complete(q, f);
+      }
+      flag |= shf[k - d];
+    }
+    __syncthreads();
+  }
+}

@@ -27,6 +27,10 @@
 // of phase A is used instead because it is already tuned (four lanes per input on G1, 3 products of latency per doubling) and
 // the 256-lane reduction after it is 8 additions deep, where a fused loop is 256 dependent doublings plus additions per input.
 //
+// The lower half of the file is many MSMs at once as one segmented chain with R outside the scan (bn254s_msm_multi_chain,
+// bn254s_msm_multi): the same products, a segmented scan, and per attempt round the drawn R_j, the links, one batched inversion
+// and the job check of every link; it has its own header comment.
+//
 // What differs between the curves is in the traits G1 / G2 below (on top of CurveG1 / CurveG2, trace_common.h); the coordinate
 // field is reached through the fe_* overloads (fq_dev.h, trace_common.h), the points through the pt_* / lds_* overloads
 // (chain_scan.h) and their SoA arrays through pa_load / pa_store (trace_common.h).
@@ -35,6 +39,8 @@
 #include <string>
 #include <type_traits>
 #include <vector>
+#include "g2_endo.h"
+#include "job_device.h"
 #include "proven_jobs.h"
 #include "trace_common.h"
 #include "trace.h"
@@ -301,7 +307,515 @@ int msm(bn254s_ctx* c, const bn254s_params* params, const uint64_t* scalars, con
   return BN254S_OK;
 }
 
+// ---- many MSMs as one segmented chain (bn254s_msm_multi_chain, bn254s_msm_multi; DESIGN.md "Many MSMs in one chain") -------------
+// m MSMs, MSM j the inputs first[j] .. first[j + 1] - 1 of n.  R is not in the scan:
+//   1. k_mm_check      x_i and (where they are supplied) R_j on their curve
+//   2. k_msm_products  P_i = s_i x_i, element i of level 0 (n points, no F_0)
+//   3. k_mm_scan_blocks / k_mm_scan_add: the segmented inclusive scan of (head flag, P_i), I_i = the sum from the head of i's MSM to i
+//   4. per attempt round (one for supplied R):
+//        k_mm_draw, hash_to_g1 | hash_to_g2, k_mm_take   R_j of the listed MSMs (round 0: all; later: the ones just rejected)
+//        k_mm_link     element i = R_seg(i) + I_i (the output of link i); elements n .. n + m - 1 = the last I of each MSM (its result)
+//        [k_g2_msm_norms,] launch_fq_batch_inv over the n + m Z
+//        k_mm_affine   outputs, offsets (R_j at a head, else the output before), results and finite flags in canonical words
+//        k_job_check of the n links, k_mm_min: the smallest (t << 16 | step) that hits per MSM
+//        k_mm_accept   a listed MSM without a hit is accepted; the others are marked and counted -> the control words go to the host
+//        k_mm_compact  the list of the marked MSMs, their attempt raised by one
+//   5. k_mm_final      bad_link / bad_step / attempts per MSM; the rows of an unprovable MSM are cleared
+// Every round links and checks all n jobs, also those of MSMs accepted before: their R_j has not moved, so their rows come out the
+// same, and a round after the first happens only for inputs crafted against a hashed point.
+// Where an output is infinite its link hits (at the top set bit of s_i), so the MSM is bad from that link or an earlier one on; the
+// next link gets R_j as the offset it is checked with, which keeps the job check on point words and cannot lower the minimum.
+
+constexpr int MM_MAX_ATTEMPTS = 8;
+constexpr u64 MM_DOMAIN = 0x626D6D00;  // "bmm\0" + kind: the last hash input
+constexpr u64 MM_GL_ORDER = 0xFFFFFFFF00000001ULL;
+constexpr unsigned long long MM_MIN_NONE = ~0ULL;
+// The control words: 32 u32, cleared before round 0 but for the four bad words, which start at UINT_MAX.
+enum { MM_COUNT = 0 /* [8]: MSMs rejected in round r */, MM_ERR = 8, MM_BAD = 10 /* [2]: x, R off the curve */,
+       MM_CHK_BAD = 12 /* [2]: what k_job_check says of x and of the offsets */, MM_LIST = 16 /* [8]: length of the list built after round r */,
+       MM_WORDS = 32 };
+enum { MM_ERR_DRAW = 1 /* self-check of the hash-to-curve kernels */ };
+
+struct MmSeed {
+  u64 w[4];
+};
+
+__device__ __forceinline__ bool mm_on_curve(const fq& x, const fq& y) {  // y^2 == x^3 + 3
+  const fq one = fq_one();
+  return fq_eq(fq_sqr(y), fq_add(fq_mul(fq_sqr(x), x), fq_add(one, fq_dbl(one))));
+}
+__device__ __forceinline__ bool mm_on_curve(const fq2& x, const fq2& y) { return g2_on_twist(x, y); }
+
+// bad[0] (bad[1]): the smallest i (j) whose x_i (R_j) is off the curve; R == nullptr: drawn points, checked by their own kernels
+template <class C>
+__global__ __launch_bounds__(64) void k_mm_check(const u64* __restrict__ x, size_t n, const u64* __restrict__ R, size_t m,
+                                                 unsigned* __restrict__ bad) {
+  using F = typename C::F;
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n + (R ? m : 0)) return;
+  const u64* w = e < n ? x + 2 * C::FW * e : R + 2 * C::FW * (e - n);
+  F px, py;
+  fe_from_canonical(w, px);
+  fe_from_canonical(w + C::FW, py);
+  if (!mm_on_curve(px, py)) atomicMin(bad + (e < n ? 0 : 1), (unsigned)(e < n ? e : e - n));
+}
+
+// the head flags of level 0
+__global__ __launch_bounds__(256) void k_mm_heads(const unsigned* __restrict__ seg_of, size_t n, unsigned* __restrict__ flags) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) flags[e] = e == 0 || seg_of[e] != seg_of[e - 1];
+}
+
+// Segmented inclusive scan of each block of 256 (flag, point) of a level in place: a lane's flag becomes "a head at or before it in
+// this block".  Lane 255's pair is the block total with "this block contains a head", element b of the next level.
+template <class C>
+__global__ __launch_bounds__(256) void k_mm_scan_blocks(u64* __restrict__ lv, unsigned* __restrict__ flags, size_t cnt, u64* __restrict__ up,
+                                                        unsigned* __restrict__ up_flags, size_t up_cnt) {
+  using P = typename C::P;
+  __shared__ u64 sh[3 * C::FW * 256];
+  __shared__ unsigned shf[256];
+  const int k = threadIdx.x;
+  const size_t e = (size_t)blockIdx.x * 256 + k;
+  P f = e < cnt ? pa_load<P>(lv, cnt, e) : pt_infinity((const P*)nullptr);
+  unsigned flag = e < cnt ? flags[e] : 0u;
+  pt_seg_scan256(f, flag, sh, shf, k);
+  if (e < cnt) {
+    pa_store(lv, cnt, e, f);
+    flags[e] = flag;
+  }
+  if (up && k == 255) {
+    pa_store(up, up_cnt, blockIdx.x, f);
+    up_flags[blockIdx.x] = flag;
+  }
+}
+
+// After the level above is scanned, its element b is the sum from the last head in blocks 0 .. b to the end of block b: block b + 1
+// adds it to the lanes before its first head.
+template <class C>
+__global__ __launch_bounds__(256) void k_mm_scan_add(u64* __restrict__ lv, const unsigned* __restrict__ flags, size_t cnt,
+                                                     const u64* __restrict__ up, size_t up_cnt) {
+  using P = typename C::P;
+  const size_t b = (size_t)blockIdx.x + 1, e = b * 256 + threadIdx.x;
+  if (e >= cnt || flags[e]) return;
+  const P pre = pa_load<P>(up, up_cnt, b - 1), f = pa_load<P>(lv, cnt, e);
+  pa_store(lv, cnt, e, pt_add_complete(pre, f));
+}
+
+// in: cnt x 8 Goldilocks elements; list: the cnt listed MSMs, or nullptr for MSMs 0 .. cnt - 1
+__global__ __launch_bounds__(256) void k_mm_draw(MmSeed seed, int kind, const unsigned* __restrict__ list,
+                                                 const unsigned char* __restrict__ attempts, size_t cnt, u64* __restrict__ in) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= cnt) return;
+  const u64 j = list ? list[k] : k;
+  u64* o = in + 8 * k;
+#pragma unroll
+  for (int w = 0; w < 4; w++) o[w] = seed.w[w];
+  o[4] = j & 0xFFFFFFFFu;
+  o[5] = j >> 32;
+  o[6] = attempts[j];
+  o[7] = MM_DOMAIN + (u64)kind;
+}
+
+// R_j of the listed MSMs from the drawn points.  A drawn point that is infinity (G2: the cleared image) fails the attempt: R_j
+// becomes the first x of the MSM, a point every kernel below can work with, and fail[j] is set.
+__global__ __launch_bounds__(256) void k_mm_take(const unsigned* __restrict__ list, size_t cnt, int pw, HashedPoints at,
+                                                 const u64* __restrict__ x, const unsigned* __restrict__ first, u64* __restrict__ R,
+                                                 unsigned char* __restrict__ fail, unsigned* __restrict__ ctl) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= cnt) return;
+  if (k == 0 && (*at.err != 0 || (at.bad && *at.bad != UINT_MAX))) atomicCAS(ctl + MM_ERR, 0u, (unsigned)MM_ERR_DRAW);
+  const size_t j = list ? list[k] : k;
+  const bool inf = at.finite && !at.finite[k];
+  const u64* src = inf ? x + (size_t)pw * first[j] : at.points + (size_t)pw * k;
+  for (int w = 0; w < pw; w++) R[(size_t)pw * j + w] = src[w];
+  fail[j] = inf;
+}
+
+// ob: n + m points.  Element i < n: R_seg(i) + I_i, the output of link i; element n + j: the last I of MSM j, its result.
+template <class C>
+__global__ __launch_bounds__(64) void k_mm_link(const u64* __restrict__ lv, size_t n, size_t m, const unsigned* __restrict__ seg_of,
+                                                const unsigned* __restrict__ first, const u64* __restrict__ R, u64* __restrict__ ob) {
+  using P = typename C::P;
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n + m) return;
+  if (e >= n) {
+    pa_store(ob, n + m, e, pa_load<P>(lv, n, (size_t)first[e - n + 1] - 1));
+    return;
+  }
+  const u64* r = R + 2 * C::FW * (size_t)seg_of[e];
+  P p;
+  fe_from_canonical(r, p.x);
+  fe_from_canonical(r + C::FW, p.y);
+  fe_one(p.z);
+  pa_store(ob, n + m, e, pt_add_complete(p, pa_load<P>(lv, n, e)));
+}
+
+// zni: the batched inverses of the Z words of ob (G1) or of their norms (G2).  Lane i < n writes outputs[i] and the offset of the
+// next link of its MSM (R_j in its place where the output is infinite, see above), and offsets[i] = R_j where i is a head; lane
+// n + j writes results[j] and finite[j].  Every row is written by exactly one lane.
+template <class C>
+__global__ __launch_bounds__(64) void k_mm_affine(const u64* __restrict__ ob, const u64* __restrict__ zni, size_t n, size_t m,
+                                                  const unsigned* __restrict__ seg_of, const unsigned* __restrict__ first,
+                                                  const u64* __restrict__ R, u64* __restrict__ outputs, u64* __restrict__ offsets,
+                                                  u64* __restrict__ results, unsigned char* __restrict__ finite) {
+  using F = typename C::F;
+  constexpr int PW = 2 * C::FW;
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x, cnt = n + m;
+  if (e >= cnt) return;
+  u64 w[PW];
+  F x, y, z;
+  fe_ld(ob + 2 * C::FW * cnt, cnt, e, z);
+  const bool inf = fe_is_zero(z);
+  if (inf) {
+#pragma unroll
+    for (int l = 0; l < PW; l++) w[l] = 0;
+  } else {
+    const F zi = fe_inv_from_norm_inv(z, ld_fq(zni, cnt, e)), z2 = fe_sqr(zi);
+    fe_ld(ob, cnt, e, x);
+    fe_ld(ob + C::FW * cnt, cnt, e, y);
+    fe_store_canonical(w, fe_mul(x, z2));
+    fe_store_canonical(w + C::FW, fe_mul(fe_mul(y, z2), zi));
+  }
+  if (e >= n) {
+#pragma unroll
+    for (int l = 0; l < PW; l++) results[PW * (e - n) + l] = w[l];
+    finite[e - n] = !inf;
+    return;
+  }
+  const size_t j = seg_of[e];
+  const u64* r = R + PW * j;
+#pragma unroll
+  for (int l = 0; l < PW; l++) outputs[PW * e + l] = w[l];
+  if (e == first[j]) {
+#pragma unroll
+    for (int l = 0; l < PW; l++) offsets[PW * e + l] = r[l];
+  }
+  if (e + 1 < first[j + 1]) {
+#pragma unroll
+    for (int l = 0; l < PW; l++) offsets[PW * (e + 1) + l] = inf ? r[l] : w[l];
+  }
+}
+
+// minw[j] = the smallest (t << 16 | step) over the links of MSM j that hit, t the link's place in its MSM
+__global__ __launch_bounds__(256) void k_mm_min(const unsigned short* __restrict__ step, size_t n, const unsigned* __restrict__ seg_of,
+                                                const unsigned* __restrict__ first, unsigned long long* __restrict__ minw) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || step[i] == BN254S_JOB_STEP_NONE) return;
+  const unsigned j = seg_of[i];
+  atomicMin(minw + j, ((unsigned long long)(i - first[j]) << 16) | step[i]);
+}
+
+// A listed MSM without a hit (and with a finite drawn point) is accepted; every other one is marked in rejected[j] and counted.
+__global__ __launch_bounds__(256) void k_mm_accept(const unsigned* __restrict__ list, size_t cnt, unsigned long long* __restrict__ minw,
+                                                   const unsigned char* __restrict__ fail, unsigned char* __restrict__ rejected,
+                                                   unsigned* __restrict__ ctl, int round) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= cnt) return;
+  const size_t j = list ? list[k] : k;
+  if (fail[j]) minw[j] = BN254S_JOB_STEP_NONE;  // link 0, no step
+  rejected[j] = minw[j] != MM_MIN_NONE;
+  if (rejected[j]) atomicAdd(ctl + MM_COUNT + round, 1u);
+}
+
+// list: the marked MSMs (in no particular order: everything an MSM gets depends on its own index alone), *len their number
+__global__ __launch_bounds__(256) void k_mm_compact(const unsigned char* __restrict__ rejected, size_t m, unsigned char* __restrict__ attempts,
+                                                    unsigned* __restrict__ list, unsigned* __restrict__ len) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m || !rejected[j]) return;
+  attempts[j]++;
+  list[atomicAdd(len, 1u)] = (unsigned)j;
+}
+
+// Lane i < n clears the rows of link i where its MSM is unprovable; lane n + j writes bad_link[j], bad_step[j] and, for drawn
+// points, raises the attempts of an MSM that ran out of them to max_attempts.
+__global__ __launch_bounds__(256) void k_mm_final(size_t n, size_t m, int pw, const unsigned* __restrict__ seg_of,
+                                                  const unsigned char* __restrict__ rejected, const unsigned long long* __restrict__ minw,
+                                                  u64* __restrict__ outputs, u64* __restrict__ offsets, unsigned* __restrict__ bad_link,
+                                                  unsigned short* __restrict__ bad_step, unsigned char* __restrict__ attempts, bool drawn) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n + m) return;
+  if (e < n) {
+    if (rejected[seg_of[e]])
+      for (int w = 0; w < pw; w++) outputs[(size_t)pw * e + w] = offsets[(size_t)pw * e + w] = 0;
+    return;
+  }
+  const size_t j = e - n;
+  const unsigned long long v = minw[j];
+  bad_link[j] = v == MM_MIN_NONE ? BN254S_MSM_LINK_NONE : (unsigned)(v >> 16);
+  bad_step[j] = (unsigned short)(v & 0xFFFF);
+  if (drawn && rejected[j]) attempts[j]++;
+}
+
+inline bool mm_coords_ok(bn254s_ctx* c, const char* tag, const char* name, int kind, const uint64_t* w, size_t cnt) {
+  const int nc = kind == 0 ? 2 : 4;
+  if (c) return coords_below_p(c, tag, name, kind == 0 ? COORD_G1 : COORD_G2, nc, w, cnt);
+  for (size_t i = 0; i < cnt * nc; i++)
+    if (!fq_below_p(w + 4 * i)) return false;
+  return true;
+}
+
+// The predicate of both entry points on their own arguments, every check that needs no device.
+bool mm_args_ok(bn254s_ctx* c, const char* tag, int kind, const uint64_t* scalars, const uint64_t* x, const size_t* seg_len, size_t m,
+                size_t n, const uint64_t* R, const uint64_t* seed, int max_attempts, const void* results, const void* finite,
+                const void* offsets, const void* outputs, const void* bad_link) {
+  if (kind < 0 || kind > 1 || !scalars || !x || !seg_len || !results || !finite || !offsets || !outputs || !bad_link || (!R && !seed) ||
+      m == 0 || n >= (size_t)UINT_MAX)
+    return false;
+  size_t sum = 0;
+  for (size_t j = 0; j < m; j++) {
+    if (seg_len[j] == 0 || seg_len[j] > n - sum) return false;
+    sum += seg_len[j];
+  }
+  if (sum != n) return false;
+  if (!R) {
+    if (max_attempts < 1 || max_attempts > MM_MAX_ATTEMPTS) return false;
+    for (int w = 0; w < 4; w++)
+      if (seed[w] >= MM_GL_ORDER) return false;
+  }
+  return mm_coords_ok(c, tag, "x", kind, x, n) && (!R || mm_coords_ok(c, tag, "R", kind, R, m));
+}
+
+// what the front-end answers, in host memory (bad_step and attempts always, unlike the optional arguments of the entry points)
+struct MmOut {
+  uint64_t *results, *offsets, *outputs, *R;
+  uint8_t *finite, *attempts;
+  uint32_t* bad_link;
+  uint16_t* bad_step;
+};
+
+// The front-end into host memory.  Nothing is written on an error.
+template <class C>
+int mm_front(bn254s_ctx* c, const char* tag, const uint64_t* scalars, const uint64_t* x, const size_t* seg_len, size_t m, size_t n,
+             const uint64_t* R, const uint64_t* seed, int max_attempts, const MmOut& o) {
+  constexpr size_t PW = 2 * C::FW, JW = 3 * C::FW;
+  constexpr bool g2 = std::is_same<typename C::F, fq2>::value;
+  constexpr int kind = C::KIND;
+  const std::string who = std::string(tag) + ": ";
+  const bool drawn = R == nullptr;
+  if (!drawn) max_attempts = 1;
+  std::vector<unsigned> h_seg(n), h_first(m + 1);
+  for (size_t j = 0, i = 0; j < m; j++) {
+    h_first[j] = (unsigned)i;
+    for (size_t t = 0; t < seg_len[j]; t++) h_seg[i++] = (unsigned)j;
+  }
+  h_first[m] = (unsigned)n;
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  // levels of the scan: level 0 = the n products, level l + 1 = the block totals of level l, until one block remains
+  std::vector<size_t> cnt{n}, at{0}, fat{0};
+  size_t lv_words = JW * n, fl = n;
+  while (cnt.back() > 256) {
+    cnt.push_back((cnt.back() + 255) / 256);
+    at.push_back(lv_words);
+    fat.push_back(fl);
+    lv_words += JW * cnt.back();
+    fl += cnt.back();
+  }
+  const size_t m_max = n < C::CHUNK ? n : C::CHUNK, pcnt = (size_t)NPTS * m_max, tot = n + m, mb = (m + 7) / 8 /* words of m bytes */;
+  const size_t hw = !drawn ? 0 : kind == 0 ? bn254s_hash_to_g1_device_words(m) : bn254s_hash_to_g2_device_words(m);
+  u64* d = c->words("msm.multi", 4 * n /* s */ + PW * n /* x */ + PW * m /* R */ + lv_words + JW * tot /* ob */ +
+                                     (g2 ? 2 : 1) * 4 * tot /* [zn,] zi */ + 2 * PW * n /* outputs, offsets */ + PW * m /* results */ +
+                                     8 * m /* hash inputs */ + hw + m /* minw */ + (fl + 1) / 2 /* flags */ + (n + 1) / 2 /* seg_of */ +
+                                     (m + 2) / 2 /* first */ + 2 * ((m + 1) / 2) /* list, bad_link */ + (n + 3) / 4 /* step */ +
+                                     (m + 3) / 4 /* bad_step */ + 4 * mb /* attempts, rejected, fail, finite */ + MM_WORDS / 2);
+  u64* d_pts = c->words(C::POOL_PTS, C::pts_words(pcnt));
+  if (!d || !d_pts) return BN254S_E_OOM;
+  u64 *d_s = d, *d_x = d_s + 4 * n, *d_R = d_x + PW * n, *d_lv = d_R + PW * m, *d_ob = d_lv + lv_words, *d_zn = d_ob + JW * tot;
+  u64 *d_zi = d_zn + (g2 ? 4 * tot : 0), *d_out = d_zi + 4 * tot, *d_off = d_out + PW * n, *d_res = d_off + PW * n, *d_in = d_res + PW * m;
+  u64* d_hash = d_in + 8 * m;
+  unsigned long long* d_min = (unsigned long long*)(d_hash + hw);
+  unsigned* d_flags = (unsigned*)(d_min + m);
+  unsigned* d_seg = d_flags + 2 * ((fl + 1) / 2);
+  unsigned* d_first = d_seg + 2 * ((n + 1) / 2);
+  unsigned* d_list = d_first + 2 * ((m + 2) / 2);
+  unsigned* d_blink = d_list + 2 * ((m + 1) / 2);
+  unsigned short* d_step = (unsigned short*)(d_blink + 2 * ((m + 1) / 2));
+  unsigned short* d_bstep = d_step + 4 * ((n + 3) / 4);
+  unsigned char* d_att = (unsigned char*)(d_bstep + 4 * ((m + 3) / 4));
+  unsigned char *d_rej = d_att + 8 * mb, *d_fail = d_rej + 8 * mb, *d_fin = d_fail + 8 * mb;
+  unsigned* d_ctl = (unsigned*)(d_fin + 8 * mb);
+  HIP_TRY(c, hipMemsetAsync(d_ctl, 0, MM_WORDS * 4, st));
+  HIP_TRY(c, hipMemsetAsync(d_ctl + MM_BAD, 0xFF, 16, st));  // bad and chk_bad
+  HIP_TRY(c, hipMemsetAsync(d_att, 0, 3 * 8 * mb, st));      // attempts, rejected and fail
+  HIP_TRY(c, hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_x, x, n * PW * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_seg, h_seg.data(), n * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_first, h_first.data(), (m + 1) * 4, hipMemcpyHostToDevice, st));
+  if (!drawn) HIP_TRY(c, hipMemcpyAsync(d_R, R, m * PW * 8, hipMemcpyHostToDevice, st));
+  k_mm_check<C><<<(unsigned)((tot + 63) / 64), 64, 0, st>>>(d_x, n, drawn ? nullptr : d_R, m, d_ctl + MM_BAD);
+  k_mm_heads<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(d_seg, n, d_flags);
+  for (size_t base = 0; base < n; base += C::CHUNK) {
+    const int mc = (int)(n - base < C::CHUNK ? n - base : C::CHUNK);
+    C::dbl_chain(d_x + PW * base, mc, d_pts, pcnt, st);
+    k_msm_products<C><<<(unsigned)mc, 256, 0, st>>>(d_s + 4 * base, mc, d_pts, d_lv, n, base);
+  }
+  const size_t top = cnt.size() - 1;
+  for (size_t l = 0; l <= top; l++)
+    k_mm_scan_blocks<C><<<(unsigned)((cnt[l] + 255) / 256), 256, 0, st>>>(d_lv + at[l], d_flags + fat[l], cnt[l],
+                                                                        l < top ? d_lv + at[l + 1] : nullptr,
+                                                                        l < top ? d_flags + fat[l + 1] : nullptr, l < top ? cnt[l + 1] : 0);
+  for (size_t l = top; l-- > 0;)
+    k_mm_scan_add<C><<<(unsigned)((cnt[l] + 255) / 256 - 1), 256, 0, st>>>(d_lv + at[l], d_flags + fat[l], cnt[l], d_lv + at[l + 1],
+                                                                         cnt[l + 1]);
+  HIP_TRY(c, hipGetLastError());
+  const MmSeed sd = drawn ? MmSeed{{seed[0], seed[1], seed[2], seed[3]}} : MmSeed{{0, 0, 0, 0}};
+  const char* curve = kind == 0 ? "the curve y^2 = x^3 + 3" : "the twist curve y^2 = x^3 + b'";
+  const unsigned gt = (unsigned)((tot + 63) / 64);
+  unsigned h_ctl[MM_WORDS];
+  size_t listed = m;  // MSMs of the round
+  for (int round = 0;; round++) {
+    const unsigned* list = round ? d_list : nullptr;
+    const unsigned gl = (unsigned)((listed + 255) / 256);
+    if (drawn) {
+      k_mm_draw<<<gl, 256, 0, st>>>(sd, kind, list, d_att, listed, d_in);
+      HIP_TRY(c, hipGetLastError());
+      HashedPoints hp;
+      const int rc = kind == 0 ? bn254s_hash_to_g1_device(c, d_in, listed, 8, d_hash, &hp) : bn254s_hash_to_g2_device(c, d_in, listed, 8, d_hash, &hp);
+      if (rc != BN254S_OK) return rc;
+      k_mm_take<<<gl, 256, 0, st>>>(list, listed, (int)PW, hp, d_x, d_first, d_R, d_fail, d_ctl);
+    }
+    HIP_TRY(c, hipMemsetAsync(d_min, 0xFF, m * 8, st));
+    k_mm_link<C><<<gt, 64, 0, st>>>(d_lv, n, m, d_seg, d_first, d_R, d_ob);
+    if (g2) {  // the batched inversion works on Fq: invert the norms of Z
+      k_g2_msm_norms<<<gt, 64, 0, st>>>(d_ob, tot, d_zn);
+      launch_fq_batch_inv(d_zn, d_zi, tot, st);
+    } else {
+      launch_fq_batch_inv(d_ob + 8 * tot, d_zi, tot, st);
+    }
+    k_mm_affine<C><<<gt, 64, 0, st>>>(d_ob, d_zi, n, m, d_seg, d_first, d_R, d_out, d_off, d_res, d_fin);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemsetAsync(d_step, 0xFF, n * 2, st));  // (a job k_job_check finds off its curve writes no step)
+    const int rc = bn254s_job_check_device(c, kind, d_s, d_x, d_off, n, d_step, d_ctl + MM_CHK_BAD);
+    if (rc != BN254S_OK) return rc;
+    k_mm_min<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(d_step, n, d_seg, d_first, d_min);
+    k_mm_accept<<<gl, 256, 0, st>>>(list, listed, d_min, d_fail, d_rej, d_ctl, round);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(h_ctl, d_ctl, sizeof h_ctl, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (h_ctl[MM_BAD] != UINT_MAX || h_ctl[MM_BAD + 1] != UINT_MAX) {  // x before R
+      const bool is_x = h_ctl[MM_BAD] != UINT_MAX;
+      c->set_err(who + (is_x ? "x_" : "R_") + std::to_string(h_ctl[MM_BAD + (is_x ? 0 : 1)]) + " is not on " + curve);
+      return BN254S_E_INVALID_ARG;
+    }
+    if (h_ctl[MM_ERR]) {
+      c->set_err(who + "a drawn offset failed the self-check of its hash-to-curve kernel (device self-check)");
+      return BN254S_E_INTERNAL;
+    }
+    if (h_ctl[MM_CHK_BAD] != UINT_MAX || h_ctl[MM_CHK_BAD + 1] != UINT_MAX) {
+      const bool is_x = h_ctl[MM_CHK_BAD] != UINT_MAX;
+      c->set_err(who + "the job check found " + (is_x ? "x_" : "the offset of link ") + std::to_string(h_ctl[MM_CHK_BAD + (is_x ? 0 : 1)]) +
+                 " off " + curve + " (device self-check)");
+      return BN254S_E_INTERNAL;
+    }
+    const unsigned count = h_ctl[MM_COUNT + round];
+    if (count == 0 || round + 1 == max_attempts) break;
+    k_mm_compact<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(d_rej, m, d_att, d_list, d_ctl + MM_LIST + round);
+    HIP_TRY(c, hipGetLastError());
+    unsigned len = 0;  // (this path is the rare one: a second small copy costs nothing that matters)
+    HIP_TRY(c, hipMemcpyAsync(&len, d_ctl + MM_LIST + round, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (len != count) {  // the next round would read list entries nobody wrote
+      c->set_err(who + "the list built after round " + std::to_string(round) + " has " + std::to_string(len) + " MSMs, " +
+                 std::to_string(count) + " were rejected (device self-check)");
+      return BN254S_E_INTERNAL;
+    }
+    listed = count;
+  }
+  k_mm_final<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(n, m, (int)PW, d_seg, d_rej, d_min, d_out, d_off, d_blink, d_bstep, d_att, drawn);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(o.results, d_res, m * PW * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(o.finite, d_fin, m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(o.offsets, d_off, n * PW * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(o.outputs, d_out, n * PW * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(o.R, d_R, m * PW * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(o.attempts, d_att, m, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(o.bad_link, d_blink, m * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(o.bad_step, d_bstep, m * 2, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return BN254S_OK;
+}
+
+// host copies of everything the front-end answers: the entry points write the caller's arrays only once nothing can fail any more
+struct MmHost {
+  std::vector<u64> results, offsets, outputs, R;
+  std::vector<uint8_t> finite, attempts;
+  std::vector<uint32_t> bad_link;
+  std::vector<uint16_t> bad_step;
+  MmHost(size_t m, size_t n, size_t pw) : results(pw * m), offsets(pw * n), outputs(pw * n), R(pw * m), finite(m), attempts(m), bad_link(m), bad_step(m) {}
+  MmOut out() { return {results.data(), offsets.data(), outputs.data(), R.data(), finite.data(), attempts.data(), bad_link.data(), bad_step.data()}; }
+  void copy_to(uint64_t* res, uint8_t* fin, uint64_t* off, uint64_t* outp, uint64_t* r, uint8_t* att, uint32_t* bl, uint16_t* bs) const {
+    memcpy(res, results.data(), results.size() * 8);
+    memcpy(fin, finite.data(), finite.size());
+    memcpy(off, offsets.data(), offsets.size() * 8);
+    memcpy(outp, outputs.data(), outputs.size() * 8);
+    if (r) memcpy(r, R.data(), R.size() * 8);
+    if (att) memcpy(att, attempts.data(), attempts.size());
+    memcpy(bl, bad_link.data(), bad_link.size() * 4);
+    if (bs) memcpy(bs, bad_step.data(), bad_step.size() * 2);
+  }
+};
+
+int mm_front_kind(bn254s_ctx* c, const char* tag, int kind, const uint64_t* scalars, const uint64_t* x, const size_t* seg_len, size_t m,
+                  size_t n, const uint64_t* R, const uint64_t* seed, int max_attempts, const MmOut& o) {
+  return kind == 0 ? mm_front<G1>(c, tag, scalars, x, seg_len, m, n, R, seed, max_attempts, o)
+                   : mm_front<G2>(c, tag, scalars, x, seg_len, m, n, R, seed, max_attempts, o);
+}
+
 }  // namespace
+
+extern "C" int bn254s_msm_multi_chain(bn254s_ctx* c, int kind, const uint64_t* scalars, const uint64_t* x, const size_t* seg_len, size_t m,
+                                      size_t n, const uint64_t* R, const uint64_t* seed, int max_attempts, uint64_t* results_out,
+                                      uint8_t* finite_out, uint64_t* offsets_out, uint64_t* outputs_out, uint64_t* R_out,
+                                      uint8_t* attempts_out, uint32_t* bad_link_out, uint16_t* bad_step_out) {
+  if (!mm_args_ok(c, "msm_multi_chain", kind, scalars, x, seg_len, m, n, R, seed, max_attempts, results_out, finite_out, offsets_out,
+                  outputs_out, bad_link_out) ||
+      !c)
+    return BN254S_E_INVALID_ARG;
+  MmHost h(m, n, kind == 0 ? 8 : 16);
+  const int rc = mm_front_kind(c, "msm_multi_chain", kind, scalars, x, seg_len, m, n, R, seed, max_attempts, h.out());
+  if (rc != BN254S_OK) return rc;
+  h.copy_to(results_out, finite_out, offsets_out, outputs_out, R_out, attempts_out, bad_link_out, bad_step_out);
+  return BN254S_OK;
+}
+
+extern "C" int bn254s_msm_multi(bn254s_ctx* c, int kind, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
+                                const size_t* seg_len, size_t m, size_t n, const uint64_t* R, const uint64_t* seed, int max_attempts,
+                                size_t per_proof, uint64_t* results_out, uint8_t* finite_out, uint64_t* offsets_out, uint64_t* outputs_out,
+                                uint64_t* R_out, uint8_t* attempts_out, uint32_t* bad_link_out, uint16_t* bad_step_out,
+                                bn254s_proof** proofs_out) {
+  int rc = proven_args(c, "msm_multi", "proof",
+                       mm_args_ok(c, "msm_multi", kind, scalars, x, seg_len, m, n, R, seed, max_attempts, results_out, finite_out,
+                                  offsets_out, outputs_out, bad_link_out),
+                       params, proofs_out, n, per_proof);
+  if (rc != BN254S_OK) return rc;
+  const size_t PW = kind == 0 ? 8 : 16;
+  MmHost h(m, n, PW);
+  rc = mm_front_kind(c, "msm_multi", kind, scalars, x, seg_len, m, n, R, seed, max_attempts, h.out());
+  if (rc != BN254S_OK) return rc;
+  for (size_t j = 0; j < m; j++)
+    if (h.bad_link[j] != BN254S_MSM_LINK_NONE) {
+      const unsigned step = h.bad_step[j];
+      const std::string hit = step == BN254S_JOB_STEP_NONE ? std::string("the drawn offset is the point at infinity")
+                                                           : "link " + std::to_string(h.bad_link[j]) + ", sum == -double at step " +
+                                                                 std::to_string(step) + " (row " + std::to_string(2 * step) + " of its frame)";
+      c->set_err("msm_multi: msm " + std::to_string(j) + " cannot be proven: " + hit +
+                 (R ? std::string(" with the supplied offset")
+                    : " with the offset of attempt " + std::to_string(max_attempts - 1) + ", the last of " + std::to_string(max_attempts)));
+      return BN254S_E_INVALID_POINT;
+    }
+  std::vector<u64> proven;
+  rc = prove_and_collect(c, "msm_multi", kind, params, scalars, x, h.offsets.data(), n, per_proof, proofs_out, proven);
+  if (rc != BN254S_OK) return rc;
+  // linkage: the trace generator computes every output bit by bit on its own; it must be the chain's, word for word
+  for (size_t i = 0; i < n; i++)
+    if (memcmp(proven.data() + PW * i, h.outputs.data() + PW * i, 8 * PW) != 0) {
+      c->set_err("msm_multi: the proven output of job " + std::to_string(i) + " is not the chain's");
+      release_proofs(proofs_out, n, per_proof);
+      return BN254S_E_INTERNAL;
+    }
+  h.copy_to(results_out, finite_out, offsets_out, outputs_out, R_out, attempts_out, bad_link_out, bad_step_out);
+  return BN254S_OK;
+}
 
 extern "C" int bn254s_g1_msm_chain(bn254s_ctx* c, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, size_t n,
                                    uint64_t* offsets_out, uint64_t* result) {

@@ -2,6 +2,7 @@
 missing or a call fails, an exception is raised."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Optional
@@ -33,6 +34,11 @@ class UnprovableJobs(RuntimeError):
 
 
 JOB_STEP_NONE = 0xFFFF  # BN254S_JOB_STEP_NONE
+MSM_LINK_NONE = 0xFFFFFFFF  # BN254S_MSM_LINK_NONE
+
+# what msm_multi_chain / msm_multi return: results [m,PW], finite [m] uint8, offsets, outputs [n,PW], R [m,PW], attempts [m] uint8,
+# bad_link [m] uint32, bad_step [m] uint16, and the proofs (None from msm_multi_chain)
+MsmMulti = collections.namedtuple("MsmMulti", "results finite offsets outputs R attempts bad_link bad_step proofs")
 
 
 class Params(C.Structure):
@@ -125,6 +131,10 @@ def load_library():
         lib.bn254s_scalar_mul_batch.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, vp, C.c_int, vp, vp, vp, vp, vp]
         lib.bn254s_scalar_mul.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int, vp, vp, vp, vp,
                                           vp, C.POINTER(vp)]
+    if hasattr(lib, "bn254s_msm_multi"):   # (likewise)
+        lib.bn254s_msm_multi_chain.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_int] + [vp] * 8
+        lib.bn254s_msm_multi.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_int,
+                                         C.c_size_t] + [vp] * 8 + [C.POINTER(vp)]
     if hasattr(lib, "bn254s_map_to_g1"):   # (as for bn254s_selftest_logup below: an older build in an A/B run has none of them)
         lib.bn254s_hash_to_fq.argtypes = [vp, C.c_size_t, vp]
         lib.bn254s_hash_to_fq_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
@@ -767,6 +777,45 @@ class Context:
                     "bn254s_scalar_mul")
         return prods, finite, offs, outs, att, _proofs(self._lib, slots)
 
+    def _msm_multi_arrays(self, kind, scalars, x, seg_len, R, seed):
+        pw, n, scalars, x, _ = self._job_arrays(kind, scalars, x, None)
+        seg = np.ascontiguousarray(seg_len, dtype=np.uintp).reshape(-1)
+        m = seg.shape[0]
+        R = None if R is None else np.ascontiguousarray(R, dtype=np.uint64)
+        seed = None if seed is None else np.ascontiguousarray(seed, dtype=np.uint64)
+        if (R is not None and R.shape != (m, pw)) or (seed is not None and seed.shape != (4,)):
+            raise ValueError(f"msm_multi: R {None if R is None else R.shape} for {m} MSMs, seed {None if seed is None else seed.shape}")
+        out = (np.zeros((m, pw), np.uint64), np.zeros(m, np.uint8), np.zeros((n, pw), np.uint64), np.zeros((n, pw), np.uint64),
+               np.zeros((m, pw), np.uint64), np.zeros(m, np.uint8), np.zeros(m, np.uint32), np.zeros(m, np.uint16))
+        return n, m, scalars, x, seg, R, seed, out
+
+    def msm_multi_chain(self, kind, scalars, x, seg_len, R=None, seed=None, max_attempts=4):
+        """kind 0 = G1, 1 = G2; m MSMs stored one after the other, MSM j with seg_len[j] of the n inputs scalars [n,4], x [n, 8 | 16];
+        R [m, 8 | 16] supplied points, or None for points drawn from seed [4] (canonical Goldilocks elements) and redrawn, up to
+        max_attempts times, for the MSMs that cannot be proven -> MsmMulti without proofs (bn254s_msm_multi_chain, on the device):
+        offsets[i] = R_j + (the sum of MSM j before input i), outputs[i] = offsets[i] + s_i x_i, results[j] = the sum of MSM j
+        (zeros and finite[j] = 0 where it is the point at infinity), R[j] the point used, attempts[j] the attempt that gave it.
+        An MSM that cannot be proven is a result: bad_link[j] / bad_step[j] name its first hitting link and step (MSM_LINK_NONE /
+        JOB_STEP_NONE otherwise), its rows of offsets and outputs are zeros, attempts[j] = max_attempts for drawn points."""
+        n, m, scalars, x, seg, R, seed, out = self._msm_multi_arrays(kind, scalars, x, seg_len, R, seed)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.bn254s_msm_multi_chain(self._h, kind, vp(scalars), vp(x), vp(seg), m, n, vp(R), vp(seed), max_attempts,
+                                                     *(vp(a) for a in out)), "bn254s_msm_multi_chain")
+        return MsmMulti(*out, None)
+
+    def msm_multi(self, kind, scalars, x, seg_len, R=None, seed=None, max_attempts=4, per_proof=128, params: Optional[Params] = None):
+        """-> MsmMulti with proofs: the front-end plus prove_batch(kind, scalars, x, offsets) of the n links, cut by per_proof
+        regardless of MSM boundaries, the outputs of the proofs checked word for word against the chain's (bn254s_msm_multi).  An
+        MSM that cannot be proven raises (-4, the message names it, its link, step and row) before any proof.  Check the result
+        with verify_msm_multi."""
+        params = params or default_params()
+        n, m, scalars, x, seg, R, seed, out = self._msm_multi_arrays(kind, scalars, x, seg_len, R, seed)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        slots = _slots(n, per_proof)
+        self._check(self._lib.bn254s_msm_multi(self._h, kind, C.byref(params), vp(scalars), vp(x), vp(seg), m, n, vp(R), vp(seed),
+                                               max_attempts, per_proof, *(vp(a) for a in out), slots), "bn254s_msm_multi")
+        return MsmMulti(*out, _proofs(self._lib, slots))
+
     def ctl_values(self, kind, scalars, x, offset, outputs):
         """(input rows [n, 81|145|33], output rows [n, 33|65|17]): the extra looking values of the two CTLs."""
         n = scalars.shape[0]
@@ -1329,6 +1378,49 @@ def verify_g2_msm(scalars, x, R, result, offsets, proofs, per_proof, ctx: Option
 
     _verify_msm("g2_msm", 1, 16, synth.g2_from_words, neg, synth.g2_add, scalars, x, R, result, offsets, proofs, per_proof, ctx,
                 params)
+
+
+def verify_msm_multi(kind, scalars, x, seg_len, R, results, finite, offsets, outputs, proofs, per_proof, ctx: Optional[Context] = None,
+                     params: Optional[Params] = None):
+    """Checks a msm_multi (kind 0 = G1, 1 = G2): the outputs of proof k are outputs[lo .. hi - 1] for its jobs; offsets at the head
+    of MSM j is R_j and offsets[i + 1] == outputs[i] inside an MSM; results[j] == outputs[last_j] - R_j in Python integer
+    arithmetic (tools/synth.py) - a second route to the result, which the device takes from the scan - with finite[j] == 0 and
+    zero words exactly where the two are equal; and every proof (Context.verify with a context, else verify_host) against its
+    jobs (s_i, x_i, offsets[i]).  Returns None or raises VerifyError naming the first broken link, MSM or rejected proof."""
+    from tools import job_outputs_ref as jr
+
+    tag, w = "msm_multi", {0: 8, 1: 16}[kind]
+    scalars, x, R, results, offsets, outputs = (np.ascontiguousarray(a, dtype=np.uint64) for a in (scalars, x, R, results, offsets, outputs))
+    seg = [int(v) for v in np.asarray(seg_len).reshape(-1)]
+    finite = np.asarray(finite).reshape(-1)
+    n, m = scalars.shape[0], len(seg)
+    if (x.shape != (n, w) or offsets.shape != (n, w) or outputs.shape != (n, w) or R.shape != (m, w) or results.shape != (m, w) or
+            finite.shape != (m,) or min(seg, default=0) < 1 or sum(seg) != n):
+        raise VerifyError(f"{tag}: shapes: scalars {scalars.shape}, x {x.shape}, offsets {offsets.shape}, outputs {outputs.shape}, "
+                          f"R {R.shape}, results {results.shape}, finite {finite.shape}, seg_len sums to {sum(seg)}")
+    for k, pr, lo, hi, outs in _proof_slices(tag, proofs, n, per_proof, w):
+        bad = np.nonzero(np.any(outs != outputs[lo:hi], axis=1))[0]
+        if bad.size:
+            raise VerifyError(f"{tag}: output {lo + int(bad[0])} of proof {k} != outputs[{lo + int(bad[0])}]")
+    add, neg = jr._law(kind)
+    first = 0
+    for j, ln in enumerate(seg):
+        last = first + ln - 1
+        if not np.array_equal(offsets[first], R[j]):
+            raise VerifyError(f"{tag}: offsets[{first}] != R_{j} (the head of msm {j})")
+        bad = np.nonzero(np.any(offsets[first + 1:last + 1] != outputs[first:last], axis=1))[0]
+        if bad.size:
+            t = int(bad[0])
+            raise VerifyError(f"{tag}: offsets[{first + t + 1}] != outputs[{first + t}] (link {t} -> {t + 1} of msm {j})")
+        want = add(jr.from_words(kind, outputs[last]), neg(jr.from_words(kind, R[j])))
+        if bool(finite[j]) != (want is not None):
+            raise VerifyError(f"{tag}: finite[{j}] is {int(finite[j])}, outputs[{last}] - R_{j} is "
+                              f"{'finite' if want is not None else 'the point at infinity'}")
+        if [int(v) for v in results[j]] != jr.to_words(kind, want):
+            raise VerifyError(f"{tag}: results[{j}] != outputs[{last}] - R_{j}")
+        first += ln
+    for k, pr, lo, hi, _ in _proof_slices(tag, proofs, n, per_proof, w):
+        _verify_slice(tag, kind, k, pr, lo, hi, scalars, x, offsets, ctx, params)
 
 
 def verify_g1_recover(xs, points, flags, fq_jobs, proofs, per_proof, ctx: Optional[Context] = None, params: Optional[Params] = None):
