@@ -1,4 +1,5 @@
-// The device halves of the proof-free front-ends for callers whose jobs are on the device already (scalar_mul.hip), as
+// The device halves of the proof-free front-ends for callers whose jobs are on the device already (scalar_mul.hip, msm.hip and the
+// rounds they share, offset_draw.h), as
 // g2_cofactor.h does it for cofactor clearing: each launches its kernels on the context's stream and returns without waiting.
 // All counts are below UINT_MAX; every pointer is device memory.
 #pragma once

@@ -13,13 +13,15 @@
 //      complete addition law (k_msm_products).  On G2, s_i is used as the full 256-bit value, never reduced mod r: a point on
 //      the twist need not lie in the r-torsion subgroup (map_to_g2 proves such points before cofactor clearing), and the G2
 //      trace computes s_i x_i bit by bit, so the chain must do the same;
-//   2. an inclusive scan over F_0 = R, F_{i+1} = P_i (n + 1 points): blocks of 256 with pt_scan256, the block totals scanned one
-//      level up (as many levels as needed: three for n up to 2^24), each block's prefix added back on the way down;
-//   3. affine normalisation with one batched inversion over Fq: G1 inverts the n + 1 Z coordinates directly; G2 takes their
-//      norms (k_g2_msm_norms), inverts the norms, and gets Z^-1 from the inverse norm (fq2_inv_from_norm_inv).  An infinite
-//      offset_i (i >= 1) is reported with the first such index (the reference's G1Target / G2Target cannot be infinity either);
-//   4. msm = offset_n - R (k_msm_finish, the twin of k_m2g_finish): offset_n == R is an error (the result would be infinity),
-//      offset_n == -R doubles (the circuit's add allows it).
+//   2. an inclusive scan over F_0 = R, F_{i+1} = P_i (n + 1 points; launch_scan): blocks of 256 with pt_scan256
+//      (k_msm_scan_blocks<C, false>), the block totals scanned one level up (as many levels as needed: three for n up to 2^24),
+//      each block's prefix added back on the way down (k_msm_scan_add<C, false>);
+//   3. affine normalisation with one batched inversion over Fq (launch_z_inverses, k_msm_affine): G1 inverts the n + 1 Z
+//      coordinates directly; G2 takes their norms (k_g2_msm_norms), inverts the norms, and gets Z^-1 from the inverse norm
+//      (fq2_inv_from_norm_inv).  An infinite offset_i (i >= 1) is reported with the first such index (the reference's G1Target /
+//      G2Target cannot be infinity either);
+//   4. msm = offset_n - R (k_msm_finish on pt_sub_slope / pt_sub_point, job_curve.h, like k_smul_sub): offset_n == R is an error
+//      (the result would be infinity), offset_n == -R doubles (the circuit's add allows it).
 // The complete addition law is used throughout, so equal partial sums double and opposite ones give infinity exactly where the
 // sequential fold meets them.  Everything runs on the context's own stream and pooled buffers, like bn254s_map_to_g2.
 //
@@ -28,19 +30,21 @@
 // the 256-lane reduction after it is 8 additions deep, where a fused loop is 256 dependent doublings plus additions per input.
 //
 // The lower half of the file is many MSMs at once as one segmented chain with R outside the scan (bn254s_msm_multi_chain,
-// bn254s_msm_multi): the same products, a segmented scan, and per attempt round the drawn R_j, the links, one batched inversion
-// and the job check of every link; it has its own header comment.
+// bn254s_msm_multi): the same products, the same scan kernels with head flags (SEG), and per attempt round (draw_rounds,
+// offset_draw.h) the drawn R_j, the links, one batched inversion and the job check of every link; it has its own header comment.
 //
-// What differs between the curves is in the traits G1 / G2 below (on top of CurveG1 / CurveG2, trace_common.h); the coordinate
-// field is reached through the fe_* overloads (fq_dev.h, trace_common.h), the points through the pt_* / lds_* overloads
+// What differs between the curves is in the traits G1 / G2 (job_curve.h: the ones of job_outputs.hip, job_check.hip and
+// scalar_mul.hip) and, for what only an MSM needs, in MsmG1 / MsmG2 below: the kernels are written over the first, the host
+// functions over the second.  The coordinate field is reached through the fe_* overloads (fq_dev.h, trace_common.h), the points through the pt_* / lds_* overloads
 // (chain_scan.h) and their SoA arrays through pa_load / pa_store (trace_common.h).
 #include <climits>
 #include <cstring>
 #include <string>
 #include <type_traits>
 #include <vector>
-#include "g2_endo.h"
+#include "job_curve.h"
 #include "job_device.h"
+#include "offset_draw.h"
 #include "proven_jobs.h"
 #include "trace_common.h"
 #include "trace.h"
@@ -48,8 +52,9 @@
 
 namespace {
 
-struct G1 : CurveG1 {
-  static constexpr int KIND = 0;  // job kind of bn254s_prove_batch
+// What only the MSMs need to know of a curve, beside the traits G1 / G2 that the kernels are written over (Curve)
+struct MsmG1 {
+  using Curve = G1;
   static constexpr size_t CHUNK = 16384;  // inputs per product launch: 3 x 4 x NPTS words = 49 KB of D_k per input, 808 MB at most
   static constexpr const char *TAG = "g1_msm", *LARGEST = "G1 proof", *POOL = "msm", *POOL_PTS = "msm.pts";
   static constexpr size_t pts_words(size_t pcnt) { return 3 * 4 * pcnt; }
@@ -60,8 +65,8 @@ struct G1 : CurveG1 {
     launch_g1_dbl_chain(d_x, m, pts, pts + 4 * cnt, pts + 8 * cnt, st);
   }
 };
-struct G2 : CurveG2 {
-  static constexpr int KIND = 1;
+struct MsmG2 {
+  using Curve = G2;
   // D_k (3 x 2 x 4 x NPTS words) and the chain's znorm (4 x NPTS words) are 28 x 514 x 8 B = 115 KB per input, 943 MB for a chunk
   static constexpr size_t CHUNK = 8192;
   static constexpr const char *TAG = "g2_msm", *LARGEST = "G2 proof", *POOL = "g2msm", *POOL_PTS = "g2msm.pts";
@@ -73,15 +78,12 @@ struct G2 : CurveG2 {
 };
 
 // A level of the scan is cnt points in the SoA form of pa_load / pa_store (trace_common.h), like the doubling chains' arrays.
-
 // F_0 = R (canonical affine words -> Jacobian, Montgomery)
 template <class C>
 __global__ __launch_bounds__(64) void k_msm_init(const u64* __restrict__ R, u64* __restrict__ lv, size_t cnt) {
   if (threadIdx.x != 0) return;
   typename C::P p;
-  fe_from_canonical(R, p.x);
-  fe_from_canonical(R + C::FW, p.y);
-  fe_one(p.z);
+  C::load(R, p);  // (its answer, whether R is on the curve, is not asked for)
   pa_store(lv, cnt, 0, p);
 }
 
@@ -111,27 +113,76 @@ __global__ __launch_bounds__(256) void k_msm_products(const u64* __restrict__ sc
 }
 
 // Inclusive scan of each block of 256 points of a level in place; lane 255's sum is the block total, element b of the next
-// level (up == nullptr at the top level, which is a single block).
-template <class C>
-__global__ __launch_bounds__(256) void k_msm_scan_blocks(u64* __restrict__ lv, size_t cnt, u64* __restrict__ up, size_t up_cnt) {
+// level (up == nullptr at the top level, which is a single block).  SEG: the segmented scan of (flag, point), flags[e] set where
+// element e is the head of an MSM; a lane's flag becomes "a head at or before it in this block" and lane 255's pair is the block
+// total with "this block contains a head".  The plain scan has no flags: both flag pointers are nullptr and never read.
+template <class C, bool SEG>
+__global__ __launch_bounds__(256) void k_msm_scan_blocks(u64* __restrict__ lv, unsigned* __restrict__ flags, size_t cnt, u64* __restrict__ up,
+                                                         unsigned* __restrict__ up_flags, size_t up_cnt) {
   using P = typename C::P;
   __shared__ u64 sh[3 * C::FW * 256];
   const int k = threadIdx.x;
   const size_t e = (size_t)blockIdx.x * 256 + k;
   P f = e < cnt ? pa_load<P>(lv, cnt, e) : pt_infinity((const P*)nullptr);
-  pt_scan256(f, sh, k);
-  if (e < cnt) pa_store(lv, cnt, e, f);
-  if (up && k == 255) pa_store(up, up_cnt, blockIdx.x, f);
+  unsigned flag = 0;
+  if constexpr (SEG) {
+    __shared__ unsigned shf[256];
+    flag = e < cnt ? flags[e] : 0u;
+    pt_seg_scan256(f, flag, sh, shf, k);
+  } else {
+    pt_scan256(f, sh, k);
+  }
+  if (e < cnt) {
+    pa_store(lv, cnt, e, f);
+    if constexpr (SEG) flags[e] = flag;
+  }
+  if (up && k == 255) {
+    pa_store(up, up_cnt, blockIdx.x, f);
+    if constexpr (SEG) up_flags[blockIdx.x] = flag;
+  }
 }
 
-// After the level above is scanned, its element b is the sum of blocks 0..b of this level: block b + 1 adds it to its elements.
-template <class C>
-__global__ __launch_bounds__(256) void k_msm_scan_add(u64* __restrict__ lv, size_t cnt, const u64* __restrict__ up, size_t up_cnt) {
+// After the level above is scanned, its element b is the sum of blocks 0..b of this level (SEG: from the last head in them on):
+// block b + 1 adds it to its elements (SEG: to the lanes before its first head).
+template <class C, bool SEG>
+__global__ __launch_bounds__(256) void k_msm_scan_add(u64* __restrict__ lv, const unsigned* __restrict__ flags, size_t cnt,
+                                                      const u64* __restrict__ up, size_t up_cnt) {
   using P = typename C::P;
   const size_t b = (size_t)blockIdx.x + 1, e = b * 256 + threadIdx.x;
   if (e >= cnt) return;
+  if constexpr (SEG)
+    if (flags[e]) return;
   const P pre = pa_load<P>(up, up_cnt, b - 1), f = pa_load<P>(lv, cnt, e);
   pa_store(lv, cnt, e, pt_add_complete(pre, f));
+}
+
+// The levels of a scan over n points: level 0 = the n points, level l + 1 = the block totals of level l, until one block remains
+// (three levels for n up to 2^24).  at / fat: where a level starts among the point words / the flags of all levels.
+struct ScanLevels {
+  std::vector<size_t> cnt, at, fat;
+  size_t words, flags;
+  ScanLevels(size_t n, size_t jw) : cnt{n}, at{0}, fat{0}, words(jw * n), flags(n) {
+    while (cnt.back() > 256) {
+      cnt.push_back((cnt.back() + 255) / 256);
+      at.push_back(words);
+      fat.push_back(flags);
+      words += jw * cnt.back();
+      flags += cnt.back();
+    }
+  }
+};
+
+// the up-sweep and the down-sweep; d_flags: the flags of all levels, those of level 0 filled in (SEG), or nullptr
+template <class C, bool SEG>
+void launch_scan(const ScanLevels& lv, u64* d_lv, unsigned* d_flags, hipStream_t st) {
+  const size_t top = lv.cnt.size() - 1;
+  auto pts = [&](size_t l) { return l <= top ? d_lv + lv.at[l] : nullptr; };
+  auto flg = [&](size_t l) { return SEG && l <= top ? d_flags + lv.fat[l] : nullptr; };
+  for (size_t l = 0; l <= top; l++)
+    k_msm_scan_blocks<C, SEG><<<(unsigned)((lv.cnt[l] + 255) / 256), 256, 0, st>>>(pts(l), flg(l), lv.cnt[l], pts(l + 1), flg(l + 1),
+                                                                                 l < top ? lv.cnt[l + 1] : 0);
+  for (size_t l = top; l-- > 0;)
+    k_msm_scan_add<C, SEG><<<(unsigned)((lv.cnt[l] + 255) / 256 - 1), 256, 0, st>>>(pts(l), flg(l), lv.cnt[l], pts(l + 1), lv.cnt[l + 1]);
 }
 
 // G2 only: zn[e] = norm(Z_e) of level 0 (zero exactly when offset_e is infinity), the input of the batched inversion
@@ -143,61 +194,66 @@ __global__ __launch_bounds__(64) void k_g2_msm_norms(const u64* __restrict__ lv,
   st_fq(zn, cnt, e, fq2_norm(z));
 }
 
-// offsets_i in canonical affine words (out[2 FW i ..]); zni = the batched inverses of the Z words of level 0 (G1) or of their
-// norms (G2).  An infinite offset writes nothing and lowers *inf_idx to its index.
+// The batched inverses zi of the Z of cnt points (G1: the Z plane is an Fq vector already) or of their norms zn (G2: the batched
+// inversion works on Fq)
+template <class C>
+void launch_z_inverses(const u64* pts, size_t cnt, u64* d_zn, u64* d_zi, hipStream_t st) {
+  if constexpr (std::is_same<typename C::F, fq2>::value) {
+    k_g2_msm_norms<<<(unsigned)((cnt + 63) / 64), 64, 0, st>>>(pts, cnt, d_zn);
+    launch_fq_batch_inv(d_zn, d_zi, cnt, st);
+  } else {
+    launch_fq_batch_inv(pts + 2 * C::FW * cnt, d_zi, cnt, st);
+  }
+}
+
+// Element e of the cnt points pts in canonical affine words w[PW]; zni: launch_z_inverses of pts.  false, and nothing written,
+// for the point at infinity.
+template <class C>
+__device__ __forceinline__ bool affine_words(const u64* __restrict__ pts, const u64* __restrict__ zni, size_t cnt, size_t e, u64* w) {
+  using F = typename C::F;
+  F x, y, z;
+  fe_ld(pts + 2 * C::FW * cnt, cnt, e, z);
+  if (fe_is_zero(z)) return false;
+  const F zi = fe_inv_from_norm_inv(z, ld_fq(zni, cnt, e)), z2 = fe_sqr(zi);
+  fe_ld(pts, cnt, e, x);
+  fe_ld(pts + C::FW * cnt, cnt, e, y);
+  fe_store_canonical(w, fe_mul(x, z2));
+  fe_store_canonical(w + C::FW, fe_mul(fe_mul(y, z2), zi));
+  return true;
+}
+
+// offsets_i in canonical affine words (out[PW i ..]) from level 0 and its Z inverses.  An infinite offset writes nothing and
+// lowers *inf_idx to its index.
 template <class C>
 __global__ __launch_bounds__(64) void k_msm_affine(const u64* __restrict__ lv, size_t cnt, const u64* __restrict__ zni,
                                                    u64* __restrict__ out, unsigned* __restrict__ inf_idx) {
-  using F = typename C::F;
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= cnt) return;
-  F x, y, z;
-  fe_ld(lv + 2 * C::FW * cnt, cnt, e, z);
-  if (fe_is_zero(z)) {
-    atomicMin(inf_idx, (unsigned)e);
-    return;
-  }
-  const F zi = fe_inv_from_norm_inv(z, ld_fq(zni, cnt, e)), z2 = fe_sqr(zi);
-  fe_ld(lv, cnt, e, x);
-  fe_ld(lv + C::FW * cnt, cnt, e, y);
-  fe_store_canonical(out + 2 * C::FW * e, fe_mul(x, z2));
-  fe_store_canonical(out + 2 * C::FW * e + C::FW, fe_mul(fe_mul(y, z2), zi));
+  if (!affine_words<C>(lv, zni, cnt, e, out + C::PW * e)) atomicMin(inf_idx, (unsigned)e);
 }
 
-// result = offset_n - R (affine; offset_n == -R doubles, offset_n == R is reported).  Nothing to do after an infinite offset.
-// The doubling needs y1 != 0, i.e. offset_n is not a point of order 2.  G1 has odd (prime) order.  On the twist,
-// #E'(Fq2) = r (2p - r) is odd, so it has no point of order 2 either, whether or not offset_n lies in the r-torsion subgroup.
+// result = offset_n - R (pt_sub_slope, job_curve.h): offset_n == R is reported, offset_n == -R doubles, as does every other R that
+// shares its x with offset_n (the chain does not ask for points of the curve).  Nothing to do after an infinite offset.
+// The cases are told apart in the field, after fe_from_canonical: an R with a coordinate not below p, which the chain call does
+// not refuse, counts as the residue it stands for (offset_n == R is then reported for it too).
+// (The doubling needs y1 != 0: G1 has prime order and #E'(Fq2) = r (2p - r) is odd, so neither has a point of order 2.)
 template <class C>
 __global__ __launch_bounds__(64) void k_msm_finish(const u64* __restrict__ o, const u64* __restrict__ R, u64* __restrict__ res,
                                                    int* __restrict__ err, const unsigned* __restrict__ inf_idx) {
   using F = typename C::F;
   if (threadIdx.x != 0 || *inf_idx != UINT_MAX) return;
-  bool same_x = true, same_y = true;
-  for (int l = 0; l < C::FW; l++) {
-    same_x &= o[l] == R[l];
-    same_y &= o[C::FW + l] == R[C::FW + l];
-  }
-  if (same_x && same_y) {
-    *err = BN254S_E_INVALID_POINT;
-    return;
-  }
-  F x1, y1, x2, y2, num, den;
+  F x1, y1, x2, y2, num, den, x3, y3;
   fe_from_canonical(o, x1);
   fe_from_canonical(o + C::FW, y1);
   fe_from_canonical(R, x2);
   fe_from_canonical(R + C::FW, y2);
-  y2 = fe_neg(y2);
-  if (same_x) {  // o == -R: the tangent at o
-    const F x1s = fe_sqr(x1);
-    num = fe_add(fe_add(x1s, x1s), x1s);
-    den = fe_add(y1, y1);
-  } else {
-    num = fe_sub(y2, y1);
-    den = fe_sub(x2, x1);
+  const int which = pt_sub_slope(x1, y1, x2, y2, num, den);
+  if (which == SUB_EQUAL) {
+    *err = BN254S_E_INVALID_POINT;
+    return;
   }
-  const F lam = fe_mul(num, fe_inv(den));
-  const F x3 = fe_sub(fe_sub(fe_sqr(lam), x1), x2);
-  const F y3 = fe_sub(fe_mul(lam, fe_sub(x1, x3)), y1);
+  if (which == SUB_SAME_X) pt_tangent(x1, y1, num, den);  // (an R off the curve) the tangent at offset_n all the same
+  pt_sub_point(x1, y1, x2, num, den, x3, y3);
   fe_store_canonical(res, x3);
   fe_store_canonical(res + C::FW, y3);
 }
@@ -207,35 +263,39 @@ bool msm_args_ok(const uint64_t* scalars, const uint64_t* x, const uint64_t* off
   return scalars && x && offset && n > 0 && n < (size_t)UINT_MAX;
 }
 
+// The products of the n inputs, chunk by chunk through the D_k in d_pts (M::pts_words(products_pcnt<M>(n)) words), as elements
+// first .. first + n - 1 of a level 0 of cnt points
+template <class M>
+size_t products_pcnt(size_t n) {
+  return (size_t)NPTS * (n < M::CHUNK ? n : M::CHUNK);
+}
+template <class M>
+void launch_products(const u64* d_s, const u64* d_x, size_t n, u64* d_pts, u64* d_lv, size_t cnt, size_t first, hipStream_t st) {
+  using C = typename M::Curve;
+  for (size_t base = 0; base < n; base += M::CHUNK) {
+    const int m = (int)(n - base < M::CHUNK ? n - base : M::CHUNK);
+    M::dbl_chain(d_x + C::PW * base, m, d_pts, products_pcnt<M>(n), st);
+    k_msm_products<C><<<(unsigned)m, 256, 0, st>>>(d_s + 4 * base, m, d_pts, d_lv, cnt, first + base);
+  }
+}
+
 // The chain into host memory: offs[(n + 1) x PW], res[PW].
-template <class C>
+template <class M>
 int msm_chain(bn254s_ctx* c, const uint64_t* scalars, const uint64_t* x, const uint64_t* R, size_t n, uint64_t* offs, uint64_t* res) {
-  constexpr size_t PW = 2 * C::FW, JW = 3 * C::FW;  // words of an affine / a Jacobian point
+  using C = typename M::Curve;
+  constexpr size_t PW = C::PW, JW = 3 * C::FW;  // words of an affine / a Jacobian point
   constexpr bool g2 = std::is_same<typename C::F, fq2>::value;
-  const std::string tag = C::TAG;
+  const std::string tag = M::TAG;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  // levels of the scan: level 0 = the n + 1 points F, level l + 1 = the block totals of level l, until one block remains
-  std::vector<size_t> cnt{n + 1}, at{0};
-  size_t lv_words = JW * (n + 1);
-  while (cnt.back() > 256) {
-    cnt.push_back((cnt.back() + 255) / 256);
-    at.push_back(lv_words);
-    lv_words += JW * cnt.back();
-  }
-  const size_t m_max = n < C::CHUNK ? n : C::CHUNK, pcnt = (size_t)NPTS * m_max;
-  u64* d = c->words(C::POOL, 4 * n /* s */ + PW * n /* x */ + PW /* R */ + lv_words + (g2 ? 2 : 1) * 4 * (n + 1) /* [zn,] zi */ +
-                                 PW * (n + 1) /* out */ + PW /* result */ + 2 /* err, inf_idx */);
-  u64* d_pts = c->words(C::POOL_PTS, C::pts_words(pcnt));
+  const size_t cnt0 = n + 1;  // level 0 = the n + 1 points F
+  const ScanLevels levels(cnt0, JW);
+  u64* d = c->words(M::POOL, 4 * n /* s */ + PW * n /* x */ + PW /* R */ + levels.words + (g2 ? 2 : 1) * 4 * cnt0 /* [zn,] zi */ +
+                                 PW * cnt0 /* out */ + PW /* result */ + 2 /* err, inf_idx */);
+  u64* d_pts = c->words(M::POOL_PTS, M::pts_words(products_pcnt<M>(n)));
   if (!d || !d_pts) return BN254S_E_OOM;
-  u64* d_s = d;
-  u64* d_x = d_s + 4 * n;
-  u64* d_R = d_x + PW * n;
-  u64* d_lv = d_R + PW;
-  u64* d_zn = d_lv + lv_words;  // (G2 only)
-  u64* d_zi = d_zn + (g2 ? 4 * (n + 1) : 0);
-  u64* d_out = d_zi + 4 * (n + 1);
-  u64* d_res = d_out + PW * (n + 1);
+  u64 *d_s = d, *d_x = d_s + 4 * n, *d_R = d_x + PW * n, *d_lv = d_R + PW, *d_zn = d_lv + levels.words /* (G2 only) */;
+  u64 *d_zi = d_zn + (g2 ? 4 * cnt0 : 0), *d_out = d_zi + 4 * cnt0, *d_res = d_out + PW * cnt0;
   int* d_err = (int*)(d_res + PW);
   unsigned* d_inf = (unsigned*)(d_err + 1);
   HIP_TRY(c, hipMemsetAsync(d_err, 0, 4, st));
@@ -243,30 +303,15 @@ int msm_chain(bn254s_ctx* c, const uint64_t* scalars, const uint64_t* x, const u
   HIP_TRY(c, hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_x, x, n * PW * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_R, R, PW * 8, hipMemcpyHostToDevice, st));
-  k_msm_init<C><<<1, 64, 0, st>>>(d_R, d_lv, cnt[0]);
-  for (size_t base = 0; base < n; base += C::CHUNK) {
-    const int m = (int)(n - base < C::CHUNK ? n - base : C::CHUNK);
-    C::dbl_chain(d_x + PW * base, m, d_pts, pcnt, st);
-    k_msm_products<C><<<(unsigned)m, 256, 0, st>>>(d_s + 4 * base, m, d_pts, d_lv, cnt[0], base + 1);
-  }
-  const size_t top = cnt.size() - 1;
-  for (size_t l = 0; l <= top; l++)
-    k_msm_scan_blocks<C><<<(unsigned)((cnt[l] + 255) / 256), 256, 0, st>>>(d_lv + at[l], cnt[l], l < top ? d_lv + at[l + 1] : nullptr,
-                                                                         l < top ? cnt[l + 1] : 0);
-  for (size_t l = top; l-- > 0;)
-    k_msm_scan_add<C><<<(unsigned)((cnt[l] + 255) / 256 - 1), 256, 0, st>>>(d_lv + at[l], cnt[l], d_lv + at[l + 1], cnt[l + 1]);
-  const unsigned g0 = (unsigned)((cnt[0] + 63) / 64);
-  if (g2) {  // the batched inversion works on Fq: invert the norms of Z
-    k_g2_msm_norms<<<g0, 64, 0, st>>>(d_lv, cnt[0], d_zn);
-    launch_fq_batch_inv(d_zn, d_zi, cnt[0], st);
-  } else {  // the Z plane of level 0 is an Fq vector already
-    launch_fq_batch_inv(d_lv + 8 * cnt[0], d_zi, cnt[0], st);
-  }
-  k_msm_affine<C><<<g0, 64, 0, st>>>(d_lv, cnt[0], d_zi, d_out, d_inf);
+  k_msm_init<C><<<1, 64, 0, st>>>(d_R, d_lv, cnt0);
+  launch_products<M>(d_s, d_x, n, d_pts, d_lv, cnt0, 1, st);
+  launch_scan<C, false>(levels, d_lv, nullptr, st);
+  launch_z_inverses<C>(d_lv, cnt0, d_zn, d_zi, st);
+  k_msm_affine<C><<<(unsigned)((cnt0 + 63) / 64), 64, 0, st>>>(d_lv, cnt0, d_zi, d_out, d_inf);
   k_msm_finish<C><<<1, 64, 0, st>>>(d_out + PW * n, d_R, d_res, d_err, d_inf);
   HIP_TRY(c, hipGetLastError());
   int h_err[2];
-  HIP_TRY(c, hipMemcpyAsync(offs, d_out, (n + 1) * PW * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(offs, d_out, cnt0 * PW * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(res, d_res, PW * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(h_err, d_err, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
@@ -284,17 +329,17 @@ int msm_chain(bn254s_ctx* c, const uint64_t* scalars, const uint64_t* x, const u
 }
 
 // The chain, its proofs (bn254s_prove_batch of the n links) and the check that the two agree.
-template <class C>
+template <class M>
 int msm(bn254s_ctx* c, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, size_t n,
         size_t per_proof, uint64_t* result, uint64_t* offsets_out, bn254s_proof** proofs) {
-  constexpr size_t PW = 2 * C::FW;
-  const std::string tag = C::TAG;
-  int rc = proven_args(c, tag, C::LARGEST, msm_args_ok(scalars, x, offset, n) && result, params, proofs, n, per_proof);
+  constexpr size_t PW = M::Curve::PW;
+  const std::string tag = M::TAG;
+  int rc = proven_args(c, tag, M::LARGEST, msm_args_ok(scalars, x, offset, n) && result, params, proofs, n, per_proof);
   if (rc != BN254S_OK) return rc;
   std::vector<u64> offs(PW * (n + 1)), outs;
-  rc = msm_chain<C>(c, scalars, x, offset, n, offs.data(), result);
+  rc = msm_chain<M>(c, scalars, x, offset, n, offs.data(), result);
   if (rc != BN254S_OK) return rc;
-  rc = prove_and_collect(c, tag, C::KIND, params, scalars, x, offs.data(), n, per_proof, proofs, outs);
+  rc = prove_and_collect(c, tag, M::Curve::KIND, params, scalars, x, offs.data(), n, per_proof, proofs, outs);
   if (rc != BN254S_OK) return rc;
   // linkage: the trace generator computes s_i x_i + offset_i on its own; it must land on offset_{i+1}
   for (size_t j = 0; j < n; j++)
@@ -311,109 +356,39 @@ int msm(bn254s_ctx* c, const bn254s_params* params, const uint64_t* scalars, con
 // m MSMs, MSM j the inputs first[j] .. first[j + 1] - 1 of n.  R is not in the scan:
 //   1. k_mm_check      x_i and (where they are supplied) R_j on their curve
 //   2. k_msm_products  P_i = s_i x_i, element i of level 0 (n points, no F_0)
-//   3. k_mm_scan_blocks / k_mm_scan_add: the segmented inclusive scan of (head flag, P_i), I_i = the sum from the head of i's MSM to i
-//   4. per attempt round (one for supplied R):
-//        k_mm_draw, hash_to_g1 | hash_to_g2, k_mm_take   R_j of the listed MSMs (round 0: all; later: the ones just rejected)
+//   3. k_mm_heads, k_msm_scan_blocks<C, true> / k_msm_scan_add<C, true>: the segmented inclusive scan of (head flag, P_i), I_i = the
+//      sum from the head of i's MSM to i
+//   4. per attempt round (draw_rounds, offset_draw.h; one round and nothing drawn for supplied R):
+//        k_draw_inputs, hash_to_g1 | hash_to_g2, k_mm_take   R_j of the listed MSMs (round 0: all; later: the ones just rejected)
 //        k_mm_link     element i = R_seg(i) + I_i (the output of link i); elements n .. n + m - 1 = the last I of each MSM (its result)
-//        [k_g2_msm_norms,] launch_fq_batch_inv over the n + m Z
+//        launch_z_inverses over the n + m Z
 //        k_mm_affine   outputs, offsets (R_j at a head, else the output before), results and finite flags in canonical words
 //        k_job_check of the n links, k_mm_min: the smallest (t << 16 | step) that hits per MSM
 //        k_mm_accept   a listed MSM without a hit is accepted; the others are marked and counted -> the control words go to the host
-//        k_mm_compact  the list of the marked MSMs, their attempt raised by one
+//        k_draw_compact  the list of the marked MSMs, their attempt raised by one
 //   5. k_mm_final      bad_link / bad_step / attempts per MSM; the rows of an unprovable MSM are cleared
 // Every round links and checks all n jobs, also those of MSMs accepted before: their R_j has not moved, so their rows come out the
 // same, and a round after the first happens only for inputs crafted against a hashed point.
 // Where an output is infinite its link hits (at the top set bit of s_i), so the MSM is bad from that link or an earlier one on; the
 // next link gets R_j as the offset it is checked with, which keeps the job check on point words and cannot lower the minimum.
 
-constexpr int MM_MAX_ATTEMPTS = 8;
 constexpr u64 MM_DOMAIN = 0x626D6D00;  // "bmm\0" + kind: the last hash input
-constexpr u64 MM_GL_ORDER = 0xFFFFFFFF00000001ULL;
 constexpr unsigned long long MM_MIN_NONE = ~0ULL;
-// The control words: 32 u32, cleared before round 0 but for the four bad words, which start at UINT_MAX.
-enum { MM_COUNT = 0 /* [8]: MSMs rejected in round r */, MM_ERR = 8, MM_BAD = 10 /* [2]: x, R off the curve */,
-       MM_CHK_BAD = 12 /* [2]: what k_job_check says of x and of the offsets */, MM_LIST = 16 /* [8]: length of the list built after round r */,
-       MM_WORDS = 32 };
-enum { MM_ERR_DRAW = 1 /* self-check of the hash-to-curve kernels */ };
-
-struct MmSeed {
-  u64 w[4];
-};
-
-__device__ __forceinline__ bool mm_on_curve(const fq& x, const fq& y) {  // y^2 == x^3 + 3
-  const fq one = fq_one();
-  return fq_eq(fq_sqr(y), fq_add(fq_mul(fq_sqr(x), x), fq_add(one, fq_dbl(one))));
-}
-__device__ __forceinline__ bool mm_on_curve(const fq2& x, const fq2& y) { return g2_on_twist(x, y); }
 
 // bad[0] (bad[1]): the smallest i (j) whose x_i (R_j) is off the curve; R == nullptr: drawn points, checked by their own kernels
 template <class C>
 __global__ __launch_bounds__(64) void k_mm_check(const u64* __restrict__ x, size_t n, const u64* __restrict__ R, size_t m,
                                                  unsigned* __restrict__ bad) {
-  using F = typename C::F;
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= n + (R ? m : 0)) return;
-  const u64* w = e < n ? x + 2 * C::FW * e : R + 2 * C::FW * (e - n);
-  F px, py;
-  fe_from_canonical(w, px);
-  fe_from_canonical(w + C::FW, py);
-  if (!mm_on_curve(px, py)) atomicMin(bad + (e < n ? 0 : 1), (unsigned)(e < n ? e : e - n));
+  typename C::P p;
+  if (!C::load(e < n ? x + C::PW * e : R + C::PW * (e - n), p)) atomicMin(bad + (e < n ? 0 : 1), (unsigned)(e < n ? e : e - n));
 }
 
 // the head flags of level 0
 __global__ __launch_bounds__(256) void k_mm_heads(const unsigned* __restrict__ seg_of, size_t n, unsigned* __restrict__ flags) {
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e < n) flags[e] = e == 0 || seg_of[e] != seg_of[e - 1];
-}
-
-// Segmented inclusive scan of each block of 256 (flag, point) of a level in place: a lane's flag becomes "a head at or before it in
-// this block".  Lane 255's pair is the block total with "this block contains a head", element b of the next level.
-template <class C>
-__global__ __launch_bounds__(256) void k_mm_scan_blocks(u64* __restrict__ lv, unsigned* __restrict__ flags, size_t cnt, u64* __restrict__ up,
-                                                        unsigned* __restrict__ up_flags, size_t up_cnt) {
-  using P = typename C::P;
-  __shared__ u64 sh[3 * C::FW * 256];
-  __shared__ unsigned shf[256];
-  const int k = threadIdx.x;
-  const size_t e = (size_t)blockIdx.x * 256 + k;
-  P f = e < cnt ? pa_load<P>(lv, cnt, e) : pt_infinity((const P*)nullptr);
-  unsigned flag = e < cnt ? flags[e] : 0u;
-  pt_seg_scan256(f, flag, sh, shf, k);
-  if (e < cnt) {
-    pa_store(lv, cnt, e, f);
-    flags[e] = flag;
-  }
-  if (up && k == 255) {
-    pa_store(up, up_cnt, blockIdx.x, f);
-    up_flags[blockIdx.x] = flag;
-  }
-}
-
-// After the level above is scanned, its element b is the sum from the last head in blocks 0 .. b to the end of block b: block b + 1
-// adds it to the lanes before its first head.
-template <class C>
-__global__ __launch_bounds__(256) void k_mm_scan_add(u64* __restrict__ lv, const unsigned* __restrict__ flags, size_t cnt,
-                                                     const u64* __restrict__ up, size_t up_cnt) {
-  using P = typename C::P;
-  const size_t b = (size_t)blockIdx.x + 1, e = b * 256 + threadIdx.x;
-  if (e >= cnt || flags[e]) return;
-  const P pre = pa_load<P>(up, up_cnt, b - 1), f = pa_load<P>(lv, cnt, e);
-  pa_store(lv, cnt, e, pt_add_complete(pre, f));
-}
-
-// in: cnt x 8 Goldilocks elements; list: the cnt listed MSMs, or nullptr for MSMs 0 .. cnt - 1
-__global__ __launch_bounds__(256) void k_mm_draw(MmSeed seed, int kind, const unsigned* __restrict__ list,
-                                                 const unsigned char* __restrict__ attempts, size_t cnt, u64* __restrict__ in) {
-  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= cnt) return;
-  const u64 j = list ? list[k] : k;
-  u64* o = in + 8 * k;
-#pragma unroll
-  for (int w = 0; w < 4; w++) o[w] = seed.w[w];
-  o[4] = j & 0xFFFFFFFFu;
-  o[5] = j >> 32;
-  o[6] = attempts[j];
-  o[7] = MM_DOMAIN + (u64)kind;
 }
 
 // R_j of the listed MSMs from the drawn points.  A drawn point that is infinity (G2: the cleared image) fails the attempt: R_j
@@ -423,7 +398,7 @@ __global__ __launch_bounds__(256) void k_mm_take(const unsigned* __restrict__ li
                                                  unsigned char* __restrict__ fail, unsigned* __restrict__ ctl) {
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= cnt) return;
-  if (k == 0 && (*at.err != 0 || (at.bad && *at.bad != UINT_MAX))) atomicCAS(ctl + MM_ERR, 0u, (unsigned)MM_ERR_DRAW);
+  if (k == 0) draw_self_check(at, ctl);
   const size_t j = list ? list[k] : k;
   const bool inf = at.finite && !at.finite[k];
   const u64* src = inf ? x + (size_t)pw * first[j] : at.points + (size_t)pw * k;
@@ -442,15 +417,12 @@ __global__ __launch_bounds__(64) void k_mm_link(const u64* __restrict__ lv, size
     pa_store(ob, n + m, e, pa_load<P>(lv, n, (size_t)first[e - n + 1] - 1));
     return;
   }
-  const u64* r = R + 2 * C::FW * (size_t)seg_of[e];
   P p;
-  fe_from_canonical(r, p.x);
-  fe_from_canonical(r + C::FW, p.y);
-  fe_one(p.z);
+  C::load(R + C::PW * (size_t)seg_of[e], p);  // (on the curve: k_mm_check, or the hash-to-curve kernels' own checks)
   pa_store(ob, n + m, e, pt_add_complete(p, pa_load<P>(lv, n, e)));
 }
 
-// zni: the batched inverses of the Z words of ob (G1) or of their norms (G2).  Lane i < n writes outputs[i] and the offset of the
+// zni: launch_z_inverses of ob.  Lane i < n writes outputs[i] and the offset of the
 // next link of its MSM (R_j in its place where the output is infinite, see above), and offsets[i] = R_j where i is a head; lane
 // n + j writes results[j] and finite[j].  Every row is written by exactly one lane.
 template <class C>
@@ -458,23 +430,14 @@ __global__ __launch_bounds__(64) void k_mm_affine(const u64* __restrict__ ob, co
                                                   const unsigned* __restrict__ seg_of, const unsigned* __restrict__ first,
                                                   const u64* __restrict__ R, u64* __restrict__ outputs, u64* __restrict__ offsets,
                                                   u64* __restrict__ results, unsigned char* __restrict__ finite) {
-  using F = typename C::F;
-  constexpr int PW = 2 * C::FW;
+  constexpr int PW = C::PW;
   const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x, cnt = n + m;
   if (e >= cnt) return;
   u64 w[PW];
-  F x, y, z;
-  fe_ld(ob + 2 * C::FW * cnt, cnt, e, z);
-  const bool inf = fe_is_zero(z);
+  const bool inf = !affine_words<C>(ob, zni, cnt, e, w);
   if (inf) {
 #pragma unroll
     for (int l = 0; l < PW; l++) w[l] = 0;
-  } else {
-    const F zi = fe_inv_from_norm_inv(z, ld_fq(zni, cnt, e)), z2 = fe_sqr(zi);
-    fe_ld(ob, cnt, e, x);
-    fe_ld(ob + C::FW * cnt, cnt, e, y);
-    fe_store_canonical(w, fe_mul(x, z2));
-    fe_store_canonical(w + C::FW, fe_mul(fe_mul(y, z2), zi));
   }
   if (e >= n) {
 #pragma unroll
@@ -514,16 +477,7 @@ __global__ __launch_bounds__(256) void k_mm_accept(const unsigned* __restrict__ 
   const size_t j = list ? list[k] : k;
   if (fail[j]) minw[j] = BN254S_JOB_STEP_NONE;  // link 0, no step
   rejected[j] = minw[j] != MM_MIN_NONE;
-  if (rejected[j]) atomicAdd(ctl + MM_COUNT + round, 1u);
-}
-
-// list: the marked MSMs (in no particular order: everything an MSM gets depends on its own index alone), *len their number
-__global__ __launch_bounds__(256) void k_mm_compact(const unsigned char* __restrict__ rejected, size_t m, unsigned char* __restrict__ attempts,
-                                                    unsigned* __restrict__ list, unsigned* __restrict__ len) {
-  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m || !rejected[j]) return;
-  attempts[j]++;
-  list[atomicAdd(len, 1u)] = (unsigned)j;
+  if (rejected[j]) atomicAdd(ctl + CTL_COUNT + round, 1u);
 }
 
 // Lane i < n clears the rows of link i where its MSM is unprovable; lane n + j writes bad_link[j], bad_step[j] and, for drawn
@@ -546,14 +500,6 @@ __global__ __launch_bounds__(256) void k_mm_final(size_t n, size_t m, int pw, co
   if (drawn && rejected[j]) attempts[j]++;
 }
 
-inline bool mm_coords_ok(bn254s_ctx* c, const char* tag, const char* name, int kind, const uint64_t* w, size_t cnt) {
-  const int nc = kind == 0 ? 2 : 4;
-  if (c) return coords_below_p(c, tag, name, kind == 0 ? COORD_G1 : COORD_G2, nc, w, cnt);
-  for (size_t i = 0; i < cnt * nc; i++)
-    if (!fq_below_p(w + 4 * i)) return false;
-  return true;
-}
-
 // The predicate of both entry points on their own arguments, every check that needs no device.
 bool mm_args_ok(bn254s_ctx* c, const char* tag, int kind, const uint64_t* scalars, const uint64_t* x, const size_t* seg_len, size_t m,
                 size_t n, const uint64_t* R, const uint64_t* seed, int max_attempts, const void* results, const void* finite,
@@ -567,12 +513,10 @@ bool mm_args_ok(bn254s_ctx* c, const char* tag, int kind, const uint64_t* scalar
     sum += seg_len[j];
   }
   if (sum != n) return false;
-  if (!R) {
-    if (max_attempts < 1 || max_attempts > MM_MAX_ATTEMPTS) return false;
-    for (int w = 0; w < 4; w++)
-      if (seed[w] >= MM_GL_ORDER) return false;
-  }
-  return mm_coords_ok(c, tag, "x", kind, x, n) && (!R || mm_coords_ok(c, tag, "R", kind, R, m));
+  if (!R && (max_attempts < 1 || max_attempts > DRAW_MAX_ATTEMPTS || !seed_canonical(seed))) return false;
+  const char* const* coord = kind == 0 ? COORD_G1 : COORD_G2;
+  const int nc = (int)point_words(kind) / 4;
+  return coords_below_p(c, tag, "x", coord, nc, x, n) && (!R || coords_below_p(c, tag, "R", coord, nc, R, m));
 }
 
 // what the front-end answers, in host memory (bad_step and attempts always, unlike the optional arguments of the entry points)
@@ -584,15 +528,15 @@ struct MmOut {
 };
 
 // The front-end into host memory.  Nothing is written on an error.
-template <class C>
+template <class M>
 int mm_front(bn254s_ctx* c, const char* tag, const uint64_t* scalars, const uint64_t* x, const size_t* seg_len, size_t m, size_t n,
              const uint64_t* R, const uint64_t* seed, int max_attempts, const MmOut& o) {
-  constexpr size_t PW = 2 * C::FW, JW = 3 * C::FW;
+  using C = typename M::Curve;
+  constexpr size_t PW = C::PW, JW = 3 * C::FW;
   constexpr bool g2 = std::is_same<typename C::F, fq2>::value;
   constexpr int kind = C::KIND;
   const std::string who = std::string(tag) + ": ";
   const bool drawn = R == nullptr;
-  if (!drawn) max_attempts = 1;
   std::vector<unsigned> h_seg(n), h_first(m + 1);
   for (size_t j = 0, i = 0; j < m; j++) {
     h_first[j] = (unsigned)i;
@@ -601,24 +545,15 @@ int mm_front(bn254s_ctx* c, const char* tag, const uint64_t* scalars, const uint
   h_first[m] = (unsigned)n;
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
-  // levels of the scan: level 0 = the n products, level l + 1 = the block totals of level l, until one block remains
-  std::vector<size_t> cnt{n}, at{0}, fat{0};
-  size_t lv_words = JW * n, fl = n;
-  while (cnt.back() > 256) {
-    cnt.push_back((cnt.back() + 255) / 256);
-    at.push_back(lv_words);
-    fat.push_back(fl);
-    lv_words += JW * cnt.back();
-    fl += cnt.back();
-  }
-  const size_t m_max = n < C::CHUNK ? n : C::CHUNK, pcnt = (size_t)NPTS * m_max, tot = n + m, mb = (m + 7) / 8 /* words of m bytes */;
-  const size_t hw = !drawn ? 0 : kind == 0 ? bn254s_hash_to_g1_device_words(m) : bn254s_hash_to_g2_device_words(m);
+  const ScanLevels levels(n, JW);  // level 0 = the n products
+  const size_t lv_words = levels.words, fl = levels.flags, tot = n + m, mb = (m + 7) / 8 /* words of m bytes */;
+  const size_t hw = drawn ? draw_device_words(kind, m) : 0;
   u64* d = c->words("msm.multi", 4 * n /* s */ + PW * n /* x */ + PW * m /* R */ + lv_words + JW * tot /* ob */ +
                                      (g2 ? 2 : 1) * 4 * tot /* [zn,] zi */ + 2 * PW * n /* outputs, offsets */ + PW * m /* results */ +
                                      8 * m /* hash inputs */ + hw + m /* minw */ + (fl + 1) / 2 /* flags */ + (n + 1) / 2 /* seg_of */ +
                                      (m + 2) / 2 /* first */ + 2 * ((m + 1) / 2) /* list, bad_link */ + (n + 3) / 4 /* step */ +
-                                     (m + 3) / 4 /* bad_step */ + 4 * mb /* attempts, rejected, fail, finite */ + MM_WORDS / 2);
-  u64* d_pts = c->words(C::POOL_PTS, C::pts_words(pcnt));
+                                     (m + 3) / 4 /* bad_step */ + 4 * mb /* attempts, rejected, fail, finite */ + CTL_WORDS / 2);
+  u64* d_pts = c->words(M::POOL_PTS, M::pts_words(products_pcnt<M>(n)));
   if (!d || !d_pts) return BN254S_E_OOM;
   u64 *d_s = d, *d_x = d_s + 4 * n, *d_R = d_x + PW * n, *d_lv = d_R + PW * m, *d_ob = d_lv + lv_words, *d_zn = d_ob + JW * tot;
   u64 *d_zi = d_zn + (g2 ? 4 * tot : 0), *d_out = d_zi + 4 * tot, *d_off = d_out + PW * n, *d_res = d_off + PW * n, *d_in = d_res + PW * m;
@@ -634,93 +569,59 @@ int mm_front(bn254s_ctx* c, const char* tag, const uint64_t* scalars, const uint
   unsigned char* d_att = (unsigned char*)(d_bstep + 4 * ((m + 3) / 4));
   unsigned char *d_rej = d_att + 8 * mb, *d_fail = d_rej + 8 * mb, *d_fin = d_fail + 8 * mb;
   unsigned* d_ctl = (unsigned*)(d_fin + 8 * mb);
-  HIP_TRY(c, hipMemsetAsync(d_ctl, 0, MM_WORDS * 4, st));
-  HIP_TRY(c, hipMemsetAsync(d_ctl + MM_BAD, 0xFF, 16, st));  // bad and chk_bad
-  HIP_TRY(c, hipMemsetAsync(d_att, 0, 3 * 8 * mb, st));      // attempts, rejected and fail
+  int rc = draw_ctl_clear(c, d_ctl);
+  if (rc != BN254S_OK) return rc;
+  HIP_TRY(c, hipMemsetAsync(d_att, 0, 3 * 8 * mb, st));  // attempts, rejected and fail
   HIP_TRY(c, hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_x, x, n * PW * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_seg, h_seg.data(), n * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_first, h_first.data(), (m + 1) * 4, hipMemcpyHostToDevice, st));
   if (!drawn) HIP_TRY(c, hipMemcpyAsync(d_R, R, m * PW * 8, hipMemcpyHostToDevice, st));
-  k_mm_check<C><<<(unsigned)((tot + 63) / 64), 64, 0, st>>>(d_x, n, drawn ? nullptr : d_R, m, d_ctl + MM_BAD);
+  k_mm_check<C><<<(unsigned)((tot + 63) / 64), 64, 0, st>>>(d_x, n, drawn ? nullptr : d_R, m, d_ctl + CTL_BAD);
   k_mm_heads<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(d_seg, n, d_flags);
-  for (size_t base = 0; base < n; base += C::CHUNK) {
-    const int mc = (int)(n - base < C::CHUNK ? n - base : C::CHUNK);
-    C::dbl_chain(d_x + PW * base, mc, d_pts, pcnt, st);
-    k_msm_products<C><<<(unsigned)mc, 256, 0, st>>>(d_s + 4 * base, mc, d_pts, d_lv, n, base);
-  }
-  const size_t top = cnt.size() - 1;
-  for (size_t l = 0; l <= top; l++)
-    k_mm_scan_blocks<C><<<(unsigned)((cnt[l] + 255) / 256), 256, 0, st>>>(d_lv + at[l], d_flags + fat[l], cnt[l],
-                                                                        l < top ? d_lv + at[l + 1] : nullptr,
-                                                                        l < top ? d_flags + fat[l + 1] : nullptr, l < top ? cnt[l + 1] : 0);
-  for (size_t l = top; l-- > 0;)
-    k_mm_scan_add<C><<<(unsigned)((cnt[l] + 255) / 256 - 1), 256, 0, st>>>(d_lv + at[l], d_flags + fat[l], cnt[l], d_lv + at[l + 1],
-                                                                         cnt[l + 1]);
+  launch_products<M>(d_s, d_x, n, d_pts, d_lv, n, 0, st);
+  launch_scan<C, true>(levels, d_lv, d_flags, st);
   HIP_TRY(c, hipGetLastError());
-  const MmSeed sd = drawn ? MmSeed{{seed[0], seed[1], seed[2], seed[3]}} : MmSeed{{0, 0, 0, 0}};
-  const char* curve = kind == 0 ? "the curve y^2 = x^3 + 3" : "the twist curve y^2 = x^3 + b'";
+  const char* curve = curve_name(kind);
   const unsigned gt = (unsigned)((tot + 63) / 64);
-  unsigned h_ctl[MM_WORDS];
-  size_t listed = m;  // MSMs of the round
-  for (int round = 0;; round++) {
-    const unsigned* list = round ? d_list : nullptr;
+  // a round: R_j of the listed MSMs (drawn points only), then every link, its affine rows and its job check, and who keeps its R_j
+  auto body = [&](int round, const unsigned* list, size_t listed, const HashedPoints& at) -> int {
     const unsigned gl = (unsigned)((listed + 255) / 256);
-    if (drawn) {
-      k_mm_draw<<<gl, 256, 0, st>>>(sd, kind, list, d_att, listed, d_in);
-      HIP_TRY(c, hipGetLastError());
-      HashedPoints hp;
-      const int rc = kind == 0 ? bn254s_hash_to_g1_device(c, d_in, listed, 8, d_hash, &hp) : bn254s_hash_to_g2_device(c, d_in, listed, 8, d_hash, &hp);
-      if (rc != BN254S_OK) return rc;
-      k_mm_take<<<gl, 256, 0, st>>>(list, listed, (int)PW, hp, d_x, d_first, d_R, d_fail, d_ctl);
-    }
+    if (drawn) k_mm_take<<<gl, 256, 0, st>>>(list, listed, (int)PW, at, d_x, d_first, d_R, d_fail, d_ctl);
     HIP_TRY(c, hipMemsetAsync(d_min, 0xFF, m * 8, st));
     k_mm_link<C><<<gt, 64, 0, st>>>(d_lv, n, m, d_seg, d_first, d_R, d_ob);
-    if (g2) {  // the batched inversion works on Fq: invert the norms of Z
-      k_g2_msm_norms<<<gt, 64, 0, st>>>(d_ob, tot, d_zn);
-      launch_fq_batch_inv(d_zn, d_zi, tot, st);
-    } else {
-      launch_fq_batch_inv(d_ob + 8 * tot, d_zi, tot, st);
-    }
+    launch_z_inverses<C>(d_ob, tot, d_zn, d_zi, st);
     k_mm_affine<C><<<gt, 64, 0, st>>>(d_ob, d_zi, n, m, d_seg, d_first, d_R, d_out, d_off, d_res, d_fin);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemsetAsync(d_step, 0xFF, n * 2, st));  // (a job k_job_check finds off its curve writes no step)
-    const int rc = bn254s_job_check_device(c, kind, d_s, d_x, d_off, n, d_step, d_ctl + MM_CHK_BAD);
+    const int rc = bn254s_job_check_device(c, kind, d_s, d_x, d_off, n, d_step, d_ctl + CTL_CHK_BAD);
     if (rc != BN254S_OK) return rc;
     k_mm_min<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(d_step, n, d_seg, d_first, d_min);
     k_mm_accept<<<gl, 256, 0, st>>>(list, listed, d_min, d_fail, d_rej, d_ctl, round);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(h_ctl, d_ctl, sizeof h_ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (h_ctl[MM_BAD] != UINT_MAX || h_ctl[MM_BAD + 1] != UINT_MAX) {  // x before R
-      const bool is_x = h_ctl[MM_BAD] != UINT_MAX;
-      c->set_err(who + (is_x ? "x_" : "R_") + std::to_string(h_ctl[MM_BAD + (is_x ? 0 : 1)]) + " is not on " + curve);
+    return BN254S_OK;
+  };
+  auto check = [&](const unsigned* h_ctl) -> int {
+    if (h_ctl[CTL_BAD] != UINT_MAX || h_ctl[CTL_BAD + 1] != UINT_MAX) {  // x before R
+      const bool is_x = h_ctl[CTL_BAD] != UINT_MAX;
+      c->set_err(who + (is_x ? "x_" : "R_") + std::to_string(h_ctl[CTL_BAD + (is_x ? 0 : 1)]) + " is not on " + curve);
       return BN254S_E_INVALID_ARG;
     }
-    if (h_ctl[MM_ERR]) {
+    if (h_ctl[CTL_ERR]) {
       c->set_err(who + "a drawn offset failed the self-check of its hash-to-curve kernel (device self-check)");
       return BN254S_E_INTERNAL;
     }
-    if (h_ctl[MM_CHK_BAD] != UINT_MAX || h_ctl[MM_CHK_BAD + 1] != UINT_MAX) {
-      const bool is_x = h_ctl[MM_CHK_BAD] != UINT_MAX;
-      c->set_err(who + "the job check found " + (is_x ? "x_" : "the offset of link ") + std::to_string(h_ctl[MM_CHK_BAD + (is_x ? 0 : 1)]) +
+    if (h_ctl[CTL_CHK_BAD] != UINT_MAX || h_ctl[CTL_CHK_BAD + 1] != UINT_MAX) {
+      const bool is_x = h_ctl[CTL_CHK_BAD] != UINT_MAX;
+      c->set_err(who + "the job check found " + (is_x ? "x_" : "the offset of link ") + std::to_string(h_ctl[CTL_CHK_BAD + (is_x ? 0 : 1)]) +
                  " off " + curve + " (device self-check)");
       return BN254S_E_INTERNAL;
     }
-    const unsigned count = h_ctl[MM_COUNT + round];
-    if (count == 0 || round + 1 == max_attempts) break;
-    k_mm_compact<<<(unsigned)((m + 255) / 256), 256, 0, st>>>(d_rej, m, d_att, d_list, d_ctl + MM_LIST + round);
-    HIP_TRY(c, hipGetLastError());
-    unsigned len = 0;  // (this path is the rare one: a second small copy costs nothing that matters)
-    HIP_TRY(c, hipMemcpyAsync(&len, d_ctl + MM_LIST + round, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (len != count) {  // the next round would read list entries nobody wrote
-      c->set_err(who + "the list built after round " + std::to_string(round) + " has " + std::to_string(len) + " MSMs, " +
-                 std::to_string(count) + " were rejected (device self-check)");
-      return BN254S_E_INTERNAL;
-    }
-    listed = count;
-  }
+    return BN254S_OK;
+  };
+  rc = draw_rounds(c, who, "MSMs", kind, MM_DOMAIN, drawn ? seed : nullptr, max_attempts, m, DrawBuffers{d_in, d_hash, d_att, d_rej, d_list, d_ctl},
+                   body, check);
+  if (rc != BN254S_OK) return rc;
   k_mm_final<<<(unsigned)((tot + 255) / 256), 256, 0, st>>>(n, m, (int)PW, d_seg, d_rej, d_min, d_out, d_off, d_blink, d_bstep, d_att, drawn);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(o.results, d_res, m * PW * 8, hipMemcpyDeviceToHost, st));
@@ -757,8 +658,8 @@ struct MmHost {
 
 int mm_front_kind(bn254s_ctx* c, const char* tag, int kind, const uint64_t* scalars, const uint64_t* x, const size_t* seg_len, size_t m,
                   size_t n, const uint64_t* R, const uint64_t* seed, int max_attempts, const MmOut& o) {
-  return kind == 0 ? mm_front<G1>(c, tag, scalars, x, seg_len, m, n, R, seed, max_attempts, o)
-                   : mm_front<G2>(c, tag, scalars, x, seg_len, m, n, R, seed, max_attempts, o);
+  return kind == 0 ? mm_front<MsmG1>(c, tag, scalars, x, seg_len, m, n, R, seed, max_attempts, o)
+                   : mm_front<MsmG2>(c, tag, scalars, x, seg_len, m, n, R, seed, max_attempts, o);
 }
 
 }  // namespace
@@ -820,20 +721,20 @@ extern "C" int bn254s_msm_multi(bn254s_ctx* c, int kind, const bn254s_params* pa
 extern "C" int bn254s_g1_msm_chain(bn254s_ctx* c, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, size_t n,
                                    uint64_t* offsets_out, uint64_t* result) {
   if (!c || !msm_args_ok(scalars, x, offset, n) || !offsets_out || !result) return BN254S_E_INVALID_ARG;
-  return msm_chain<G1>(c, scalars, x, offset, n, offsets_out, result);
+  return msm_chain<MsmG1>(c, scalars, x, offset, n, offsets_out, result);
 }
 extern "C" int bn254s_g2_msm_chain(bn254s_ctx* c, const uint64_t* scalars, const uint64_t* x, const uint64_t* offset, size_t n,
                                    uint64_t* offsets_out, uint64_t* result) {
   if (!c || !msm_args_ok(scalars, x, offset, n) || !offsets_out || !result) return BN254S_E_INVALID_ARG;
-  return msm_chain<G2>(c, scalars, x, offset, n, offsets_out, result);
+  return msm_chain<MsmG2>(c, scalars, x, offset, n, offsets_out, result);
 }
 extern "C" int bn254s_g1_msm(bn254s_ctx* c, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
                              const uint64_t* offset, size_t n, size_t per_proof, uint64_t* result, uint64_t* offsets_out,
                              bn254s_proof** proofs) {
-  return msm<G1>(c, params, scalars, x, offset, n, per_proof, result, offsets_out, proofs);
+  return msm<MsmG1>(c, params, scalars, x, offset, n, per_proof, result, offsets_out, proofs);
 }
 extern "C" int bn254s_g2_msm(bn254s_ctx* c, const bn254s_params* params, const uint64_t* scalars, const uint64_t* x,
                              const uint64_t* offset, size_t n, size_t per_proof, uint64_t* result, uint64_t* offsets_out,
                              bn254s_proof** proofs) {
-  return msm<G2>(c, params, scalars, x, offset, n, per_proof, result, offsets_out, proofs);
+  return msm<MsmG2>(c, params, scalars, x, offset, n, per_proof, result, offsets_out, proofs);
 }

@@ -29,12 +29,13 @@ constexpr const char* const COORD_G2[4] = {"x.c0", "x.c1", "y.c0", "y.c1"};
 
 // w: n items of ncoord coordinates.  The first coordinate that is not below p names itself in the context's error text,
 // "<tag>: <name>_<i> has <coord> not below p" ("<tag>: <name>_<i> is not below p" for ncoord == 1); true if all are fine.
+// c == nullptr (the shape checks of a call without a context): the same answer without a text.
 inline bool coords_below_p(bn254s_ctx* c, const std::string& tag, const char* name, const char* const* coord, int ncoord,
                            const uint64_t* w, size_t n) {
   for (size_t i = 0; i < n; i++)
     for (int k = 0; k < ncoord; k++)
       if (!fq_below_p(w + 4 * (ncoord * i + k))) {
-        c->set_err(tag + ": " + name + "_" + std::to_string(i) + (ncoord > 1 ? std::string(" has ") + coord[k] : " is") + " not below p");
+        if (c) c->set_err(tag + ": " + name + "_" + std::to_string(i) + (ncoord > 1 ? std::string(" has ") + coord[k] : " is") + " not below p");
         return false;
       }
   return true;

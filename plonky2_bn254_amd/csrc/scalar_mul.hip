@@ -6,14 +6,11 @@
 //   offset_i^(a) = hash_to_g1 | hash_to_g2 (seed[0..3], i mod 2^32, i >> 32, a, 0x62736D00 + kind),  a = 0, 1, ...
 //   job i takes the smallest a < max_attempts whose (s_i, x_i, offset_i^(a)) the traces can prove (job_check.hip)
 //   output_i = s_i x_i + offset_i,  product_i = output_i - offset_i
-// Rounds, one per attempt, over a list of jobs (round 0: all of them; later: the jobs just rejected, a handful at most):
-//   k_smul_draw      the eight hash inputs of every listed job
-//   [hash_to_g1 / hash_to_g2 of the inputs: map_to_g1.hip, map_to_g2.hip through job_device.h]
+// Rounds, one per attempt, over a list of jobs (round 0: all of them; later: the jobs just rejected, a handful at most), run by
+// draw_rounds (offset_draw.h: k_draw_inputs, the hash, k_draw_compact), which msm.hip uses for its MSMs too.  A round here:
 //   k_smul_gather    rounds after the first: the scalars and x of the listed jobs side by side
 //   [k_job_check of the listed jobs with the drawn points as their offsets: job_check.hip]
 //   k_smul_accept    a provable job keeps its drawn point as its offset; every other one is marked and counted
-//   -> the count of the round, 4 bytes, is all the host reads; if it is not zero and an attempt is left:
-//   k_smul_compact   the list of the marked jobs, their attempt raised by one
 // then
 //   [k_job_outputs: s x + offset by the window ladder, job_outputs.hip]
 //   k_smul_sub       output - offset: equal (O), opposite (a doubling) and general, one inversion, canonical words, on-curve self-check
@@ -28,40 +25,17 @@
 #include <vector>
 #include "job_curve.h"
 #include "job_device.h"
+#include "offset_draw.h"
 #include "proven_jobs.h"
 
 namespace {
 
-constexpr int SMUL_MAX_ATTEMPTS = 8;
 constexpr u64 SMUL_DOMAIN = 0x62736D00;  // "bsm\0" + kind: the last hash input
-constexpr u64 GL_ORDER = 0xFFFFFFFF00000001ULL;
 constexpr unsigned SMUL_STEP_UNSET = 0xFEFE;  // what the step of a job is before k_job_check writes it (it writes none for a bad point)
 
-// The control words: 32 u32, cleared before round 0 but for bad, which starts at UINT_MAX.
-enum { CTL_COUNT = 0 /* [8]: jobs rejected in round r */, CTL_ERR = 8, CTL_BAD = 10 /* [2]: x, offset off the curve */,
-       CTL_LIST = 16 /* [8]: length of the list built after round r */, CTL_WORDS = 32 };
-enum { SMUL_ERR_DRAW = 1 /* self-check of the hash-to-curve kernels */, SMUL_ERR_DRAW_INF = 2 /* a drawn G2 point is O */,
-       SMUL_ERR_OUT_INF = 3 /* the output of a provable job is O */, SMUL_ERR_OPPOSITE = 4 /* equal x, y neither equal nor opposite */,
-       SMUL_ERR_CURVE = 5 /* the product is off its curve */ };
-
-struct SmulSeed {
-  u64 w[4];
-};
-
-// in: m x 8 Goldilocks elements; list: the m listed jobs, or nullptr for jobs 0 .. m - 1
-__global__ __launch_bounds__(256) void k_smul_draw(SmulSeed seed, int kind, const unsigned* __restrict__ list,
-                                                   const unsigned char* __restrict__ attempts, size_t m, u64* __restrict__ in) {
-  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= m) return;
-  const u64 i = list ? list[j] : j;
-  u64* o = in + 8 * j;
-#pragma unroll
-  for (int w = 0; w < 4; w++) o[w] = seed.w[w];
-  o[4] = i & 0xFFFFFFFFu;
-  o[5] = i >> 32;
-  o[6] = attempts[i];
-  o[7] = SMUL_DOMAIN + (u64)kind;
-}
+// CTL_ERR beyond CTL_ERR_DRAW (offset_draw.h)
+enum { SMUL_ERR_DRAW_INF = 2 /* a drawn G2 point is O */, SMUL_ERR_OUT_INF = 3 /* the output of a provable job is O */,
+       SMUL_ERR_OPPOSITE = 4 /* equal x, y neither equal nor opposite */, SMUL_ERR_CURVE = 5 /* the product is off its curve */ };
 
 // cs, cx: m x 4, m x pw words, the scalars and x of the listed jobs
 __global__ __launch_bounds__(256) void k_smul_gather(const unsigned* __restrict__ list, size_t m, int pw, const u64* __restrict__ scalars,
@@ -81,7 +55,7 @@ __global__ __launch_bounds__(256) void k_smul_accept(const unsigned* __restrict_
                                                      unsigned short* __restrict__ last_step, unsigned* __restrict__ ctl, int round) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= m) return;
-  if (j == 0 && (*at.err != 0 || (at.bad && *at.bad != UINT_MAX))) atomicCAS(ctl + CTL_ERR, 0u, (unsigned)SMUL_ERR_DRAW);
+  if (j == 0) draw_self_check(at, ctl);
   if (at.finite && !at.finite[j]) atomicCAS(ctl + CTL_ERR, 0u, (unsigned)SMUL_ERR_DRAW_INF);
   const size_t i = list ? list[j] : j;
   const unsigned st = step[j];
@@ -95,20 +69,9 @@ __global__ __launch_bounds__(256) void k_smul_accept(const unsigned* __restrict_
   atomicAdd(ctl + CTL_COUNT + round, 1u);
 }
 
-// list: the marked jobs (in no particular order: everything a job gets depends on its own index alone), *len their number
-__global__ __launch_bounds__(256) void k_smul_compact(const unsigned char* __restrict__ rejected, size_t n, unsigned char* __restrict__ attempts,
-                                                      unsigned* __restrict__ list, unsigned* __restrict__ len) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || !rejected[i]) return;
-  attempts[i]++;
-  list[atomicAdd(len, 1u)] = (unsigned)i;
-}
-
-// product = output - offset for affine, canonical points of the curve C; out_finite: what k_job_outputs said of the output.
-//   output == offset    the product is O: zero words, finite = 0  (s x = O)
-//   output == -offset   the subtraction doubles the output: lambda = 3 x^2 / 2 y  (y != 0: both group orders are odd)
-//   otherwise           lambda = (-y2 - y1) / (x2 - x1)
-// and one inversion for the two finite cases.  The product must be on the curve again.
+// product = output - offset for affine, canonical points of the curve C (pt_sub_slope, pt_sub_point: job_curve.h); out_finite: what
+// k_job_outputs said of the output.  output == offset: the product is O, zero words and finite = 0 (s x = O).  Otherwise the
+// product must be on the curve again.
 template <class C>
 __global__ __launch_bounds__(64) void k_smul_sub(const u64* __restrict__ output, const u64* __restrict__ offset,
                                                  const unsigned char* __restrict__ out_finite, size_t n, u64* __restrict__ product,
@@ -120,32 +83,24 @@ __global__ __launch_bounds__(64) void k_smul_sub(const u64* __restrict__ output,
     atomicCAS(ctl + CTL_ERR, 0u, (unsigned)SMUL_ERR_OUT_INF);
     return;
   }
-  using F = decltype(typename C::E().x);
-  F x1, y1, x2, y2;
+  typename C::F x1, y1, x2, y2, num, den, x3, y3;
   fe_from_canonical(output + C::PW * k, x1);
   fe_from_canonical(output + C::PW * k + C::FW, y1);
   fe_from_canonical(offset + C::PW * k, x2);
   fe_from_canonical(offset + C::PW * k + C::FW, y2);
-  F num = fe_sub(fe_neg(y2), y1), den = fe_sub(x2, x1);
-  if (fe_is_zero(den)) {
-    if (fe_is_zero(fe_sub(y1, y2))) {
-      finite[k] = 0;
+  const int which = pt_sub_slope(x1, y1, x2, y2, num, den);
+  if (which == SUB_EQUAL) {
+    finite[k] = 0;
 #pragma unroll
-      for (int w = 0; w < C::PW; w++) o[w] = 0;
-      return;
-    }
-    if (!fe_is_zero(fe_add(y1, y2))) {
-      atomicCAS(ctl + CTL_ERR, 0u, (unsigned)SMUL_ERR_OPPOSITE);
-      return;
-    }
-    const F xx = fe_sqr(x1);
-    num = fe_add(fe_add(xx, xx), xx);
-    den = fe_add(y1, y1);
+    for (int w = 0; w < C::PW; w++) o[w] = 0;
+    return;
   }
-  const F lam = fe_mul(num, fe_inv(den));
-  const F x3 = fe_sub(fe_sub(fe_sqr(lam), x1), x2);
-  const F y3 = fe_sub(fe_mul(lam, fe_sub(x1, x3)), y1);
-  if (!jo_on_curve(x3, y3)) {
+  if (which == SUB_SAME_X) {
+    atomicCAS(ctl + CTL_ERR, 0u, (unsigned)SMUL_ERR_OPPOSITE);
+    return;
+  }
+  pt_sub_point(x1, y1, x2, num, den, x3, y3);
+  if (!on_curve(x3, y3)) {
     atomicCAS(ctl + CTL_ERR, 0u, (unsigned)SMUL_ERR_CURVE);
     return;
   }
@@ -156,7 +111,7 @@ __global__ __launch_bounds__(64) void k_smul_sub(const u64* __restrict__ output,
 
 const char* smul_err_text(unsigned e) {
   switch (e) {
-    case SMUL_ERR_DRAW: return "a drawn offset failed the self-check of its hash-to-curve kernel";
+    case CTL_ERR_DRAW: return "a drawn offset failed the self-check of its hash-to-curve kernel";
     case SMUL_ERR_DRAW_INF: return "a drawn offset is the point at infinity";
     case SMUL_ERR_OUT_INF: return "the output of a provable job is the point at infinity";
     case SMUL_ERR_OPPOSITE: return "an output shares x with its offset and is neither it nor its negative";
@@ -164,28 +119,14 @@ const char* smul_err_text(unsigned e) {
   }
 }
 
-inline bool gl_canonical(const uint64_t* seed) {
-  for (int w = 0; w < 4; w++)
-    if (seed[w] >= GL_ORDER) return false;
-  return true;
-}
-
 // The predicate of both entry points on their own arguments, every check that needs no device.  The first coordinate of x that
 // is not below p names itself where there is a context to hold the text.
 bool smul_args_ok(bn254s_ctx* c, const char* tag, int kind, const uint64_t* scalars, const uint64_t* x, size_t n, const uint64_t* seed,
                   int max_attempts, const void* products, const void* finite, const void* offsets) {
   if (kind < 0 || kind > 1 || !scalars || !x || !seed || !products || !finite || !offsets || n == 0 || n >= (size_t)UINT_MAX ||
-      max_attempts < 1 || max_attempts > SMUL_MAX_ATTEMPTS || !gl_canonical(seed))
+      max_attempts < 1 || max_attempts > DRAW_MAX_ATTEMPTS || !seed_canonical(seed))
     return false;
-  const int nc = (int)point_words(kind) / 4;
-  const char* const* coord = kind == 0 ? COORD_G1 : COORD_G2;
-  for (size_t i = 0; i < n; i++)
-    for (int k = 0; k < nc; k++)
-      if (!fq_below_p(x + 4 * (nc * i + k))) {
-        if (c) c->set_err(std::string(tag) + ": x_" + std::to_string(i) + " has " + coord[k] + " not below p");
-        return false;
-      }
-  return true;
+  return coords_below_p(c, tag, "x", kind == 0 ? COORD_G1 : COORD_G2, (int)point_words(kind) / 4, x, n);
 }
 
 // The front-end into host memory: products, offsets, outputs [n x PW], finite and attempts [n].  Nothing is written on an error.
@@ -193,7 +134,7 @@ int smul_front(bn254s_ctx* c, const char* tag, int kind, const uint64_t* scalars
                int max_attempts, uint64_t* products, uint8_t* finite, uint64_t* offsets, uint64_t* outputs, uint8_t* attempts) {
   const std::string who = std::string(tag) + ": ";
   const size_t PW = point_words(kind), nb = (n + 7) / 8 /* words that hold n bytes */;
-  const size_t hw = kind == 0 ? bn254s_hash_to_g1_device_words(n) : bn254s_hash_to_g2_device_words(n);
+  const size_t hw = draw_device_words(kind, n);
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
   u64* d = c->words("smul", 2 * (4 + PW) * n /* scalars, x and their gathered copies */ + 3 * PW * n /* offset, output, product */ +
@@ -207,15 +148,13 @@ int smul_front(bn254s_ctx* c, const char* tag, int kind, const uint64_t* scalars
   unsigned short *d_step = (unsigned short*)(d_bytes + 4 * nb), *d_last = d_step + 4 * ((n + 3) / 4);
   unsigned* d_list = (unsigned*)(d_last + 4 * ((n + 3) / 4));
   unsigned* d_ctl = d_list + 2 * ((n + 1) / 2);
-  HIP_TRY(c, hipMemsetAsync(d_ctl, 0, CTL_WORDS * 4, st));
-  HIP_TRY(c, hipMemsetAsync(d_ctl + CTL_BAD, 0xFF, 8, st));
+  int rc = draw_ctl_clear(c, d_ctl);  // (CTL_CHK_BAD is not used here and stays at UINT_MAX)
+  if (rc != BN254S_OK) return rc;
   HIP_TRY(c, hipMemsetAsync(d_att, 0, 2 * nb * 8, st));  // attempts and rejected
   HIP_TRY(c, hipMemcpyAsync(d_s, scalars, n * 32, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_x, x, n * PW * 8, hipMemcpyHostToDevice, st));
-  const SmulSeed sd = {{seed[0], seed[1], seed[2], seed[3]}};
-  const char* curve = kind == 0 ? "the curve y^2 = x^3 + 3" : "the twist curve y^2 = x^3 + b'";
-  unsigned h_ctl[CTL_WORDS];
-  auto fail_ctl = [&]() -> int {  // what the control words say beyond a count; BN254S_OK if nothing
+  const char* curve = curve_name(kind);
+  auto fail_ctl = [&](const unsigned* h_ctl) -> int {  // what the control words say beyond a count; BN254S_OK if nothing
     if (h_ctl[CTL_BAD] != UINT_MAX) {
       c->set_err(who + "x_" + std::to_string(h_ctl[CTL_BAD]) + " is not on " + curve);
       return BN254S_E_INVALID_ARG;
@@ -230,70 +169,52 @@ int smul_front(bn254s_ctx* c, const char* tag, int kind, const uint64_t* scalars
     }
     return BN254S_OK;
   };
-  size_t m = n;  // jobs of the round
-  for (int round = 0;; round++) {
-    const unsigned* list = round ? d_list : nullptr;
+  // a round: the job check of the listed jobs with the drawn points as their offsets, then who keeps its point.  A job with a
+  // point off its curve never gets a step and is counted, so that the round does not end the loop before check() has named it.
+  auto body = [&](int round, const unsigned* list, size_t m, const HashedPoints& at) -> int {
     const unsigned grid = (unsigned)((m + 255) / 256);
-    k_smul_draw<<<grid, 256, 0, st>>>(sd, kind, list, d_att, m, d_in);
-    HIP_TRY(c, hipGetLastError());
-    HashedPoints at;
-    int rc = kind == 0 ? bn254s_hash_to_g1_device(c, d_in, m, 8, d_hash, &at) : bn254s_hash_to_g2_device(c, d_in, m, 8, d_hash, &at);
-    if (rc != BN254S_OK) return rc;
     if (round) {
       k_smul_gather<<<grid, 256, 0, st>>>(list, m, (int)PW, d_s, d_x, d_cs, d_cx);
       HIP_TRY(c, hipGetLastError());
     }
     HIP_TRY(c, hipMemsetAsync(d_step, SMUL_STEP_UNSET & 0xFF, m * 2, st));
-    rc = bn254s_job_check_device(c, kind, round ? d_cs : d_s, round ? d_cx : d_x, at.points, m, d_step, d_ctl + CTL_BAD);
+    const int rc = bn254s_job_check_device(c, kind, round ? d_cs : d_s, round ? d_cx : d_x, at.points, m, d_step, d_ctl + CTL_BAD);
     if (rc != BN254S_OK) return rc;
     k_smul_accept<<<grid, 256, 0, st>>>(list, m, (int)PW, d_step, at, d_off, d_rej, d_last, d_ctl, round);
     HIP_TRY(c, hipGetLastError());
-    unsigned count = 0;
-    HIP_TRY(c, hipMemcpyAsync(&count, d_ctl + CTL_COUNT + round, 4, hipMemcpyDeviceToHost, st));
+    return BN254S_OK;
+  };
+  unsigned count = 0;
+  rc = draw_rounds(c, who, "jobs", kind, SMUL_DOMAIN, seed, max_attempts, n, DrawBuffers{d_in, d_hash, d_att, d_rej, d_list, d_ctl}, body,
+                   fail_ctl, &count);
+  if (rc != BN254S_OK) return rc;
+  if (count != 0) {  // out of attempts: the smallest job that is still rejected, with the step of this, its last attempt
+    std::vector<uint8_t> rej(n);
+    std::vector<uint16_t> last(n);
+    HIP_TRY(c, hipMemcpyAsync(rej.data(), d_rej, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(last.data(), d_last, n * 2, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    if (count == 0) break;
-    HIP_TRY(c, hipMemcpyAsync(h_ctl, d_ctl, sizeof h_ctl, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    rc = fail_ctl();
-    if (rc != BN254S_OK) return rc;
-    if (round + 1 == max_attempts) {  // the smallest job that is still rejected, with the step of this, its last attempt
-      std::vector<uint8_t> rej(n);
-      std::vector<uint16_t> last(n);
-      HIP_TRY(c, hipMemcpyAsync(rej.data(), d_rej, n, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipMemcpyAsync(last.data(), d_last, n * 2, hipMemcpyDeviceToHost, st));
-      HIP_TRY(c, hipStreamSynchronize(st));
-      size_t i = 0;
-      while (i < n && !rej[i]) i++;
-      if (i == n) {
-        c->set_err(who + "a round counted rejected jobs and marked none");
-        return BN254S_E_INTERNAL;
-      }
-      c->set_err(who + "job " + std::to_string(i) + " cannot be proven: sum == -double at step " + std::to_string(last[i]) + " (row " +
-                 std::to_string(2 * last[i]) + " of its frame) with the offset of attempt " + std::to_string(round) + ", the last of " +
-                 std::to_string(max_attempts));
-      return BN254S_E_INVALID_POINT;
-    }
-    k_smul_compact<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(d_rej, n, d_att, d_list, d_ctl + CTL_LIST + round);
-    HIP_TRY(c, hipGetLastError());
-    unsigned listed = 0;  // (this path is the rare one: a second small copy costs nothing that matters)
-    HIP_TRY(c, hipMemcpyAsync(&listed, d_ctl + CTL_LIST + round, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (listed != count) {  // the next round would read list entries nobody wrote
-      c->set_err(who + "the list built after round " + std::to_string(round) + " has " + std::to_string(listed) + " jobs, " +
-                 std::to_string(count) + " were rejected (device self-check)");
+    size_t i = 0;
+    while (i < n && !rej[i]) i++;
+    if (i == n) {
+      c->set_err(who + "a round counted rejected jobs and marked none");
       return BN254S_E_INTERNAL;
     }
-    m = count;
+    c->set_err(who + "job " + std::to_string(i) + " cannot be proven: sum == -double at step " + std::to_string(last[i]) + " (row " +
+               std::to_string(2 * last[i]) + " of its frame) with the offset of attempt " + std::to_string(max_attempts - 1) + ", the last of " +
+               std::to_string(max_attempts));
+    return BN254S_E_INVALID_POINT;
   }
-  int rc = bn254s_job_outputs_device(c, kind, d_s, d_x, d_off, n, d_out, d_ofin, d_ctl + CTL_BAD);
+  rc = bn254s_job_outputs_device(c, kind, d_s, d_x, d_off, n, d_out, d_ofin, d_ctl + CTL_BAD);
   if (rc != BN254S_OK) return rc;
   const unsigned blocks = (unsigned)((n + 63) / 64);
   if (kind == 0) k_smul_sub<G1><<<blocks, 64, 0, st>>>(d_out, d_off, d_ofin, n, d_prod, d_fin, d_ctl);
   else k_smul_sub<G2><<<blocks, 64, 0, st>>>(d_out, d_off, d_ofin, n, d_prod, d_fin, d_ctl);
   HIP_TRY(c, hipGetLastError());
+  unsigned h_ctl[CTL_WORDS];
   HIP_TRY(c, hipMemcpyAsync(h_ctl, d_ctl, sizeof h_ctl, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipStreamSynchronize(st));
-  rc = fail_ctl();
+  rc = fail_ctl(h_ctl);
   if (rc != BN254S_OK) return rc;
   HIP_TRY(c, hipMemcpyAsync(products, d_prod, n * PW * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(c, hipMemcpyAsync(finite, d_fin, n, hipMemcpyDeviceToHost, st));

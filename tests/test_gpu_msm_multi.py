@@ -102,6 +102,28 @@ def test_g2_layouts(gpu_ctx, jobs, seg):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("kind", CURVES)
+def test_one_msm_of_257_is_the_chain(gpu_ctx, jobs, kind):
+    """One MSM of 257 inputs under a supplied R, one element into a second scan block: the smallest size at which the block-total and
+    add-back kernels run, here with head flags (257 products) and in g1_msm_chain / g2_msm_chain without (258 points, R among them).
+    Both are the same kernels in their two instantiations and must give the same words.  The inputs are random, so the links are
+    provable but for a chance of about 2^-245 (the job check); mm.msm_multi(kind, s, x, [257], R=R, check={0}) walks
+    all 257 links of either kind and finds them so.  That the words are right, not only equal, is what the layout tests above
+    check against the Python reference."""
+    s0, x0, o, _ = jobs[kind]
+    n = 257
+    s, x, R = np.ascontiguousarray(s0[:n]), np.ascontiguousarray(x0[:n]), np.ascontiguousarray(o[7:8])
+    got = gpu_ctx.msm_multi_chain(kind, s, x, [n], R=R)
+    offs, res = (gpu_ctx.g1_msm_chain if kind == 0 else gpu_ctx.g2_msm_chain)(s, x, R[0])
+    assert offs.shape == (n + 1, PW[kind])
+    assert np.array_equal(got.offsets, offs[:n])
+    assert np.array_equal(got.outputs, offs[1:n + 1])
+    assert np.array_equal(got.results[0], res)
+    assert got.finite[0] == 1
+    assert got.bad_link[0] == pk.MSM_LINK_NONE
+
+
+@pytest.mark.gpu
 def test_three_levels(gpu_ctx):
     """70 000 inputs x_i = (a + i d) G: more than 256^2 products, so the scan has three levels, and the long MSM spans 258 blocks
     of level 0 and two of level 1."""
