@@ -638,6 +638,74 @@ int bn254s_msm_multi(bn254s_ctx* ctx, int kind, const bn254s_params* params, con
                      size_t per_proof, uint64_t* results_out, uint8_t* finite_out, uint64_t* offsets_out, uint64_t* outputs_out,
                      uint64_t* R_out, uint8_t* attempts_out, uint32_t* bad_link_out, uint16_t* bad_step_out,
                      bn254s_proof** proofs_out /* ceil(n / per_proof) */);
+/* Statement verifiers (csrc/point_sum.hip; DESIGN.md "Statement verifiers").  The proofs of bn254s_scalar_mul and bn254s_msm_multi
+ * carry the reference's statement output_i = s_i x_i + offset_i.  What their caller wants to know, products[i] == s_i x_i or
+ * results[j] == the sum of s x over MSM j, follows from the proofs only together with the linkage between the arrays:
+ * product + offset == output, the offset chain inside an MSM, result + R == the last output.  The linkage is curve arithmetic and
+ * is checked on the device; the proofs go through bn254s_verify_batch.
+ *
+ * bn254s_point_sum_check_batch: for each of n relations, is c_i == a_i + b_i?  kind 0 = G1, 1 = G2 (on the twist); PW = 8 | 16
+ * words per point.  a_i may be the point at infinity (a_finite[i] == 0 and zero words); b_i and c_i are affine points.
+ * code_out[i] is the first of these that applies: */
+enum {
+  BN254S_SUM_OK = 0,           /* the relation holds */
+  BN254S_SUM_A_NOT_ZERO = 1,   /* a_finite[i] == 0 but a word of a_i is non-zero */
+  BN254S_SUM_A_OFF_CURVE = 2,  /* a_finite[i] != 0 and a_i is not on its curve */
+  BN254S_SUM_B_OFF_CURVE = 3,  /* b_i is not on its curve */
+  BN254S_SUM_C_OFF_CURVE = 4,  /* c_i is not on its curve */
+  BN254S_SUM_INFINITE = 5,     /* a_i == -b_i: the sum is O, which an affine c_i cannot state */
+  BN254S_SUM_X = 6,            /* the x coordinate of a_i + b_i is not that of c_i */
+  BN254S_SUM_Y = 7,            /* x agrees and y does not, i.e. c_i == -(a_i + b_i) */
+  /* link codes of the two verifiers below only */
+  BN254S_SUM_X_OFF_CURVE = 8,  /* an input point x of the job / of the MSM is not on its curve */
+  BN254S_SUM_HEAD = 9,         /* msm_multi: the offset of the first link of the MSM is not R_j, word for word */
+  BN254S_SUM_CHAIN = 10        /* msm_multi: offsets[i + 1] != outputs[i] inside the MSM, word for word */
+};
+/* The kernel takes no inversion: with d = x_b - x_a, e = y_b - y_a (d = 2 y_a, e = 3 x_a^2 where a_i == b_i) the relation holds
+ * exactly when x_c d^2 == e^2 - (x_a + x_b) d^2 and (y_c + y_a) d == e (x_a - x_c); where a_i is O it is c_i == b_i, x compared
+ * first.  A failing relation is a result, not an error: the call returns BN254S_OK.
+ * BN254S_E_INVALID_ARG, nothing written: a NULL pointer, n == 0, n >= UINT_MAX, a kind outside 0..1; a coordinate of a_i (rows
+ * with a_finite[i] != 0 only: the others are code 1 unless all zero), b_i or c_i that is p or more, found on the host before any
+ * device work - bn254s_last_error names "a_<i>" / "b_<i>" / "c_<i>".  All work runs on the context's stream. */
+int bn254s_point_sum_check_batch(bn254s_ctx* ctx, int kind /* 0 = G1, 1 = G2 on the twist */, const uint64_t* a /* n x PW */,
+                                 const uint8_t* a_finite /* n */, const uint64_t* b /* n x PW */, const uint64_t* c /* n x PW */,
+                                 size_t n, uint8_t* code_out /* n */);
+/* bn254s_verify_scalar_mul: the statement products[i] == s_i x_i of a bn254s_scalar_mul call, from the arrays it returned and
+ * the words of its proofs.  Proof k holds jobs k per_proof .. min(n, (k + 1) per_proof) - 1, as bn254s_prove_batch cuts them;
+ * words[k], n_words[k] and degree_bits[k] are per proof (the last proof of a call can be lower than the others), and
+ * bn254s_verify_batch is called once per run of consecutive proofs of equal (degree_bits, n_words).  Accepted iff
+ *   every x_i is on its curve                                                   (link_out[i] = BN254S_SUM_X_OFF_CURVE otherwise),
+ *   products[i] (with finite[i]) + offsets[i] == outputs[i] for every job       (link_out[i] = the code 1..7 of the relation),
+ *   every proof is accepted for its jobs (s_i, x_i, offsets[i], outputs[i])     (proof_status[k] as bn254s_verify_batch gives it).
+ * bn254s_verify_msm_multi: the statement results[j] == the sum of s x over MSM j of a bn254s_msm_multi call.  Per MSM j with
+ * first input f_j and last input l_j, link_out[j] is the first failing check in this order:
+ *   every x of the MSM is on its curve                                          (BN254S_SUM_X_OFF_CURVE),
+ *   offsets[f_j] == R_j word for word                                           (BN254S_SUM_HEAD),
+ *   offsets[i + 1] == outputs[i] word for word for f_j <= i < l_j               (BN254S_SUM_CHAIN),
+ *   results[j] (with finite[j]) + R_j == outputs[l_j]                           (the code 1..7 of the relation),
+ * and every proof must be accepted for its jobs (s_i, x_i, offsets[i], outputs[i]).
+ * Where the offsets or the R come from (seed, attempts) is deliberately NOT checked: that s x + offset == output is proven for
+ * the offset at hand, and subtracting that same offset gives s x whatever point it is.  Drawing the offsets again would double the
+ * device work and verify nothing about the statement.
+ * Returns BN254S_OK: everything above holds.  BN254S_E_VERIFY: something does not; link_out and proof_status (either may be
+ * NULL) are filled for every entry - the linkage and the proofs are both always evaluated, a failing link does not stop the
+ * proofs - and bn254s_last_error names the first linkage failure with its index ("verify_scalar_mul: job 64: products + offsets
+ * != outputs (x)", "verify_msm_multi: msm 3: offsets[40] != outputs[39] (link 7 -> 8)") or, where the linkage is whole,
+ * "proof k: <text of bn254s_verify_batch>" for the lowest rejected proof k of the call.  BN254S_E_INVALID_ARG before any device work, nothing written:
+ * a NULL pointer other than the two optional outputs, n == 0, m == 0, per_proof == 0, n_proofs != ceil(n / per_proof), some
+ * seg_len[j] == 0, sum seg_len != n, a kind outside 0..1, a params->struct_size mismatch, a coordinate of any point array that
+ * is p or more (rows of products / results with finite == 0 excepted), naming the array and the index; no context (checked
+ * last).  BN254S_E_HIP / BN254S_E_OOM pass through.  Anything other than BN254S_OK is not an acceptance. */
+int bn254s_verify_scalar_mul(bn254s_ctx* ctx, int kind, const bn254s_params* params, const uint64_t* const* words,
+                             const size_t* n_words, const uint32_t* degree_bits, size_t n_proofs, size_t per_proof,
+                             const uint64_t* scalars, const uint64_t* x, size_t n, const uint64_t* products, const uint8_t* finite,
+                             const uint64_t* offsets, const uint64_t* outputs, uint8_t* link_out /* n, may be NULL */,
+                             int32_t* proof_status /* n_proofs, may be NULL */);
+int bn254s_verify_msm_multi(bn254s_ctx* ctx, int kind, const bn254s_params* params, const uint64_t* const* words,
+                            const size_t* n_words, const uint32_t* degree_bits, size_t n_proofs, size_t per_proof,
+                            const uint64_t* scalars, const uint64_t* x, const size_t* seg_len, size_t m, size_t n, const uint64_t* R,
+                            const uint64_t* results, const uint8_t* finite, const uint64_t* offsets, const uint64_t* outputs,
+                            uint8_t* link_out /* m, may be NULL */, int32_t* proof_status /* n_proofs, may be NULL */);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

@@ -35,6 +35,9 @@ class UnprovableJobs(RuntimeError):
 
 JOB_STEP_NONE = 0xFFFF  # BN254S_JOB_STEP_NONE
 MSM_LINK_NONE = 0xFFFFFFFF  # BN254S_MSM_LINK_NONE
+# BN254S_SUM_*: the codes of point_sum_check_batch (0..7) and the link codes of verify_scalar_mul / verify_msm_multi (0..10)
+(SUM_OK, SUM_A_NOT_ZERO, SUM_A_OFF_CURVE, SUM_B_OFF_CURVE, SUM_C_OFF_CURVE, SUM_INFINITE, SUM_X, SUM_Y, SUM_X_OFF_CURVE, SUM_HEAD,
+ SUM_CHAIN) = range(11)
 
 # what msm_multi_chain / msm_multi return: results [m,PW], finite [m] uint8, offsets, outputs [n,PW], R [m,PW], attempts [m] uint8,
 # bad_link [m] uint32, bad_step [m] uint16, and the proofs (None from msm_multi_chain)
@@ -135,6 +138,12 @@ def load_library():
         lib.bn254s_msm_multi_chain.argtypes = [vp, C.c_int, vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_int] + [vp] * 8
         lib.bn254s_msm_multi.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_int,
                                          C.c_size_t] + [vp] * 8 + [C.POINTER(vp)]
+    if hasattr(lib, "bn254s_point_sum_check_batch"):   # (likewise; the three entry points of csrc/point_sum.hip come together)
+        lib.bn254s_point_sum_check_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp]
+        lib.bn254s_verify_scalar_mul.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t,
+                                                 vp, vp, vp, vp, vp, vp]
+        lib.bn254s_verify_msm_multi.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp,
+                                                C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "bn254s_map_to_g1"):   # (as for bn254s_selftest_logup below: an older build in an A/B run has none of them)
         lib.bn254s_hash_to_fq.argtypes = [vp, C.c_size_t, vp]
         lib.bn254s_hash_to_fq_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
@@ -815,6 +824,77 @@ class Context:
         self._check(self._lib.bn254s_msm_multi(self._h, kind, C.byref(params), vp(scalars), vp(x), vp(seg), m, n, vp(R), vp(seed),
                                                max_attempts, per_proof, *(vp(a) for a in out), slots), "bn254s_msm_multi")
         return MsmMulti(*out, _proofs(self._lib, slots))
+
+    def point_sum_check_batch(self, kind, a, a_finite, b, c):
+        """kind 0 = G1, 1 = G2; a, b, c [n, 8 | 16], a_finite [n] -> codes [n] uint8: is c_i == a_i + b_i, with a_i the point at
+        infinity where a_finite[i] is 0 (zero words), on the device without an inversion (bn254s_point_sum_check_batch).  SUM_OK,
+        or the first of SUM_A_NOT_ZERO .. SUM_Y that applies.  A coordinate >= p raises (-1, the message names the array and the
+        first such row)."""
+        pw = {0: 8, 1: 16}.get(kind, 8)
+        a, b, c = (np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, pw) for v in (a, b, c))
+        fin = np.ascontiguousarray(a_finite, dtype=np.uint8).reshape(-1)
+        n = a.shape[0]
+        if b.shape != a.shape or c.shape != a.shape or fin.shape != (n,):
+            raise ValueError(f"point_sum_check: a {a.shape}, a_finite {fin.shape}, b {b.shape}, c {c.shape}")
+        codes = np.zeros(n, np.uint8)
+        self._check(self._lib.bn254s_point_sum_check_batch(self._h, kind, _ptr(a), fin.ctypes.data_as(C.c_void_p), _ptr(b), _ptr(c), n,
+                                                           codes.ctypes.data_as(C.c_void_p)), "bn254s_point_sum_check_batch")
+        return codes
+
+    def _verify_statement(self, what, call, kind, proofs, n_links, params):
+        """The part the two statement verifiers share: the proof table, the call, and what its code means."""
+        params = params or default_params()
+        pairs = [pr if isinstance(pr, (tuple, list)) else (pr.words, pr.degree_bits) for pr in proofs]
+        arrs, table = _word_arrays([w for w, _ in pairs])
+        n_words = (C.c_size_t * len(arrs))(*[a.size for a in arrs])
+        bits = (C.c_uint32 * len(arrs))(*[int(d) for _, d in pairs])
+        link, status = np.zeros(n_links, np.uint8), np.zeros(len(arrs), np.int32)
+        rc = call(params, table, n_words, bits, len(arrs), link.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p))
+        if rc == -8:
+            e = VerifyError(self._lib.bn254s_last_error(self._h).decode())
+            e.link_codes, e.proof_status = link, status
+            raise e
+        self._check(rc, what)
+        return link, status
+
+    def verify_scalar_mul(self, kind, proofs, per_proof, scalars, x, products, finite, offsets, outputs, params: Optional[Params] = None):
+        """The statement products[i] == s_i x_i of a scalar_mul call (bn254s_verify_scalar_mul): every x_i on its curve,
+        products[i] + offsets[i] == outputs[i] on the device, and every proof accepted for its jobs (s_i, x_i, offsets[i],
+        outputs[i]) by verify_batch.  `proofs`: objects with `words` and `degree_bits`, or (words, degree_bits) pairs, proof k for
+        jobs k per_proof ...  Where the offsets come from (the seed, the attempts) is not checked: the statement does not depend
+        on it.  -> (link_codes [n] uint8, proof_status [n_proofs] int32), all zero; a rejection raises VerifyError with the
+        message of the first broken link, or of the first rejected proof where every link holds, and both arrays as its
+        `link_codes` and `proof_status`."""
+        pw, n, scalars, x, _ = self._job_arrays(kind, scalars, x, None)
+        products, offsets, outputs = (np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, pw) for a in (products, offsets, outputs))
+        finite = np.ascontiguousarray(finite, dtype=np.uint8).reshape(-1)
+        if not (products.shape == offsets.shape == outputs.shape == (n, pw)) or finite.shape != (n,):
+            raise ValueError(f"verify_scalar_mul: products {products.shape}, finite {finite.shape}, offsets {offsets.shape}, "
+                             f"outputs {outputs.shape} for {n} jobs")
+        call = lambda params, table, n_words, bits, k, link, status: self._lib.bn254s_verify_scalar_mul(
+            self._h, kind, C.byref(params), table, n_words, bits, k, per_proof, _ptr(scalars), _ptr(x), n, _ptr(products),
+            finite.ctypes.data_as(C.c_void_p), _ptr(offsets), _ptr(outputs), link, status)
+        return self._verify_statement("bn254s_verify_scalar_mul", call, kind, proofs, n, params)
+
+    def verify_msm_multi(self, kind, proofs, per_proof, scalars, x, seg_len, R, results, finite, offsets, outputs,
+                         params: Optional[Params] = None):
+        """The statement results[j] == the sum of s x over MSM j of a msm_multi call (bn254s_verify_msm_multi): per MSM every x on
+        its curve, the offset of its first link R_j and the offset of every later link the output before it, word for word,
+        results[j] + R_j == the last output on the device, and every proof accepted for its links.  Arguments and the return value
+        as for verify_scalar_mul, with link_codes [m] per MSM: SUM_X_OFF_CURVE, SUM_HEAD, SUM_CHAIN, then the relation's code."""
+        pw, n, scalars, x, _ = self._job_arrays(kind, scalars, x, None)
+        seg = np.ascontiguousarray(seg_len, dtype=np.uintp).reshape(-1)
+        m = seg.shape[0]
+        offsets, outputs = (np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, pw) for a in (offsets, outputs))
+        R, results = (np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, pw) for a in (R, results))
+        finite = np.ascontiguousarray(finite, dtype=np.uint8).reshape(-1)
+        if not (offsets.shape == outputs.shape == (n, pw)) or not (R.shape == results.shape == (m, pw)) or finite.shape != (m,):
+            raise ValueError(f"verify_msm_multi: R {R.shape}, results {results.shape}, finite {finite.shape}, offsets {offsets.shape}, "
+                             f"outputs {outputs.shape} for {m} MSMs of {n} inputs")
+        call = lambda params, table, n_words, bits, k, link, status: self._lib.bn254s_verify_msm_multi(
+            self._h, kind, C.byref(params), table, n_words, bits, k, per_proof, _ptr(scalars), _ptr(x), seg.ctypes.data_as(C.c_void_p),
+            m, n, _ptr(R), _ptr(results), finite.ctypes.data_as(C.c_void_p), _ptr(offsets), _ptr(outputs), link, status)
+        return self._verify_statement("bn254s_verify_msm_multi", call, kind, proofs, m, params)
 
     def ctl_values(self, kind, scalars, x, offset, outputs):
         """(input rows [n, 81|145|33], output rows [n, 33|65|17]): the extra looking values of the two CTLs."""
