@@ -706,6 +706,86 @@ int bn254s_verify_msm_multi(bn254s_ctx* ctx, int kind, const bn254s_params* para
                             const uint64_t* scalars, const uint64_t* x, const size_t* seg_len, size_t m, size_t n, const uint64_t* R,
                             const uint64_t* results, const uint8_t* finite, const uint64_t* offsets, const uint64_t* outputs,
                             uint8_t* link_out /* m, may be NULL */, int32_t* proof_status /* n_proofs, may be NULL */);
+/* Root statement verifiers (csrc/root_links.hip; DESIGN.md "Root statement verifiers").  The Fq-exp proofs of
+ * bn254s_g1_recover_from_x, bn254s_g2_recover_from_x, bn254s_fq_sqrt, bn254s_fq2_sqrt and bn254s_map_to_g1 say
+ * base^((p-1)/2) == output and nothing else.  What their caller wants to know - flags[i] says whether g(x_i) is a square and
+ * points[i] is the root with the wanted sign; points[i] is the map_to_g1 image of u_i - follows from the proofs only with the
+ * linkage: the base of job i is what the front-end says it is, the proven symbol matches the flag, the root squares back and has
+ * the right sign, the flags select the point's x.  The field part is checked on the device; the proofs go through
+ * bn254s_verify_batch against jobs that the verifier computes itself.
+ *
+ * bn254s_root_links_check_batch: `what` names the front-end whose arrays are checked:
+ *   what  input `in`        `out`                base of the job(s)                    radicand
+ *   0     x_i, 4 words      points, n x 8        g = x^3 + 3                           g             (G1 recover; the root is even)
+ *   1     x_i, 8 words      points, n x 16       norm(g), g = x^3 + b' in Fq2          g             (G2 recover; sgns)
+ *   2     x_i, 4 words      roots, n x 4         x_i                                   x_i           (Fq sqrt; sgns, root_ok)
+ *   3     x_i, 8 words      roots, n x 8         norm(x_i)                             x_i           (Fq2 sqrt; sgns, root_ok)
+ *   4     u_i, 4 words      points, n x 8        g(x1), g(x2) of the SvdW candidates:  g of the candidate that the two flags
+ *                                                jobs and flags 2i, 2i + 1             select: x1 if sq_flags[2i], else x2 if
+ *                                                                                      sq_flags[2i + 1], else x3; sign = parity of u_i
+ * code_out[i] is the first of these that applies: */
+enum {
+  BN254S_ROOT_OK = 0,          /* every check below passes */
+  BN254S_ROOT_JOB_SCALAR = 1,  /* fq_jobs given and the scalar words of a job of input i are not (p-1)/2 (what 4: of job 2i or 2i + 1) */
+  BN254S_ROOT_JOB_BASE = 2,    /* fq_jobs given and the base words of a job of input i are not the base computed here, word for word */
+  BN254S_ROOT_FLAG = 3,        /* a flag byte (flags, root_ok) or sgns[i] above 1; what 2, 3: square[i] set on a zero base, or
+                                  root_ok[i] != (base != 0 ? square[i] : sgns[i] == 0) */
+  BN254S_ROOT_CARRY = 4,       /* what 0, 1: the x words of points[i] are not x_i; what 4: not the candidate that the flags select */
+  BN254S_ROOT_NOT_ZERO = 5,    /* no root is claimed (what 0, 1: flag clear; 2, 3: root_ok clear) and the y / root words are not
+                                  all zero; never for what 4 */
+  BN254S_ROOT_SQUARE = 6,      /* a root is claimed and y^2 != radicand (in Fq2 for what 1, 3); for what 4 this is also "both flags
+                                  clear and g(x3) has no such root" */
+  BN254S_ROOT_SIGN = 7         /* y squares back but has the other sign: Fq the parity of the canonical value, Fq2 the parity of
+                                  c0, or of c1 when c0 is zero */
+};
+/* The kernel has no ladder and no exponentiation: a root is checked, never computed; what 4 takes the one inversion of the map.
+ * bases_out (may be NULL) receives the canonical base words, n x 4 (2n x 4 for what 4), whatever the codes are.  fq_jobs (may be
+ * NULL: codes 1 and 2 do not occur) is n x 8 (2n x 8): scalar | base.  sgns NULL = all 0; not read for what 0, 4.  root_ok is
+ * read for what 2, 3 only.  flags is n bytes, 2n for what 4.  A failing relation is a result, not an error: the call returns
+ * BN254S_OK.  BN254S_E_INVALID_ARG, nothing written, before any device work: a NULL required pointer, n == 0, n >= UINT_MAX
+ * (n >= 2^31 for what 4), a what outside 0..4, a coordinate of `in` that is p or more, a coordinate that is p or more in the y /
+ * root of a row whose root is claimed (what 0, 1: flags[i] != 0; 2, 3: root_ok[i] != 0; 4: every row) - bn254s_last_error names
+ * it, "root_links_check: x_<i> is not below p" / "... x_<i> has c1 not below p", "... points_<i> has y.c0 not below p"; no
+ * context (checked last).  Rows that are never read as a field element - the y of a clear flag, the root of a clear root_ok, the x of a point -
+ * are compared only and not range-checked. */
+int bn254s_root_links_check_batch(bn254s_ctx* ctx, int what, const uint64_t* in, const uint8_t* sgns /* NULL = all 0 */, size_t n,
+                                  const uint64_t* out /* points or roots */, const uint8_t* flags /* n; 2n for what 4 */,
+                                  const uint8_t* root_ok /* what 2, 3 only */, const uint64_t* fq_jobs /* may be NULL */,
+                                  uint8_t* code_out /* n */, uint64_t* bases_out /* may be NULL */);
+/* The five verifiers: the statement of a call of the front-end of the same name, from the arrays it returned and the words of
+ * its Fq-exp proofs; words, n_words, degree_bits, n_proofs, per_proof as for bn254s_verify_scalar_mul, with n jobs (2n for
+ * map_to_g1: n_proofs == ceil(2n / per_proof)).  Each runs the link check once and hands bn254s_verify_batch (kind 2, once per
+ * run of consecutive proofs of equal (degree_bits, n_words)) jobs of its own making: the scalar (p-1)/2, the base from the device
+ * and the output that the flag demands - 0 for a zero base (what 2, 3 only; a set flag there is code 3), else 1 where the flag
+ * is set and p - 1 where it is clear.  So an accepted proof proves the flag; fq_jobs is only compared, may be NULL, and the
+ * outputs of the proofs are not an argument.  Accepted iff every link_out[i] is BN254S_ROOT_OK and every proof is accepted.
+ * Returns BN254S_OK, or BN254S_E_VERIFY with link_out and proof_status (either may be NULL) filled for every entry - both are
+ * always evaluated - and bn254s_last_error naming the smallest failing input ("verify_g1_recover: input 7: y of the point does
+ * not square to x^3 + 3"; a job code names the job, for map_to_g1 with its candidate) or, where the linkage is whole,
+ * "proof k: <text of bn254s_verify_batch>" for the lowest rejected proof k.  BN254S_E_INVALID_ARG as for
+ * bn254s_root_links_check_batch and bn254s_verify_scalar_mul (per_proof == 0, a wrong n_proofs, a NULL words[k], a
+ * params->struct_size mismatch), the text with the verifier's name as its tag; the context is checked last.  Other codes of the
+ * device pass through.  Anything other than BN254S_OK is not an acceptance. */
+int bn254s_verify_g1_recover(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
+                             const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* xs, size_t n,
+                             const uint64_t* points, const uint8_t* flags, const uint64_t* fq_jobs /* may be NULL */,
+                             uint8_t* link_out /* n, may be NULL */, int32_t* proof_status /* n_proofs, may be NULL */);
+int bn254s_verify_g2_recover(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
+                             const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* xs,
+                             const uint8_t* sgns /* NULL = all 0 */, size_t n, const uint64_t* points, const uint8_t* flags,
+                             const uint64_t* fq_jobs, uint8_t* link_out, int32_t* proof_status);
+int bn254s_verify_fq_sqrt(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
+                          const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* xs,
+                          const uint8_t* sgns /* NULL = all 0 */, size_t n, const uint64_t* roots, const uint8_t* square,
+                          const uint8_t* root_ok, const uint64_t* fq_jobs, uint8_t* link_out, int32_t* proof_status);
+int bn254s_verify_fq2_sqrt(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
+                           const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* xs,
+                           const uint8_t* sgns /* NULL = all 0 */, size_t n, const uint64_t* roots, const uint8_t* square,
+                           const uint8_t* root_ok, const uint64_t* fq_jobs, uint8_t* link_out, int32_t* proof_status);
+int bn254s_verify_map_to_g1(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
+                            const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* u, size_t n,
+                            const uint64_t* points, const uint8_t* sq_flags /* 2n */, const uint64_t* fq_jobs /* 2n x 8, may be NULL */,
+                            uint8_t* link_out /* n */, int32_t* proof_status);
 /* ---- kernel-level entry points (parity tests and bench.py's roofline leg) ------------------------------ */
 /* PolynomialBatch::from_values on host column-major values[C][2^16]: outputs (any may be NULL)
  * coeffs[C][N], lde[C][2N] in Merkle-leaf (bit-reversed) order, cap[16*4]. */

@@ -22,12 +22,6 @@
 
 namespace {
 
-// src/fields/sgn.rs:20-27 on canonical words: the parity of c0, or of c1 when c0 is zero
-__device__ __forceinline__ bool sgn_words(const fqw& c0, const fqw& c1) {
-  const bool zero0 = (c0.l[0] | c0.l[1] | c0.l[2] | c0.l[3]) == 0;
-  return (c0.l[0] & 1) || (zero0 && (c1.l[0] & 1));
-}
-
 // xs, roots: n x 4 words; sgns, square, ok: n bytes; jobs: n x 8 words ((p-1)/2 | x)
 __global__ __launch_bounds__(G1R_LANES) void k_fq_sqrt(const u64* __restrict__ xs, const unsigned char* __restrict__ sgns, size_t n,
                                                        u64* __restrict__ roots, unsigned char* __restrict__ square,

@@ -1,6 +1,7 @@
-// The square root in Fq2 = Fq[u]/(u^2 + 1) that the kernels share (g2_recover.hip, map_to_g2.hip), in two Fq exponentiations with
-// the exponent (p+1)/4 of sqrt_ladder.h (p = 3 mod 4); why the formulas hold: the head of g2_recover.hip.  One lane per element,
-// blocks of G1R_LANES lanes, `tab` the ladder's table in LDS.
+// The square root in Fq2 = Fq[u]/(u^2 + 1) that the kernels share (g2_recover.hip, map_to_g2.hip, field_gadgets.hip), in two Fq
+// exponentiations with the exponent (p+1)/4 of sqrt_ladder.h (p = 3 mod 4); why the formulas hold: the head of g2_recover.hip.
+// One lane per element, blocks of G1R_LANES lanes, `tab` the ladder's table in LDS.  Also the sign of an Fq2 element on
+// canonical words (sgn_words), which the kernels that make a root and the one that checks it (root_links.hip) share.
 #pragma once
 #include "sqrt_ladder.h"
 #include "g2_recover_constants.inc"
@@ -20,6 +21,12 @@ __device__ __forceinline__ fq fq_select(bool c, const fq& a, const fq& b) {
 #pragma unroll
   for (int j = 0; j < FQ_NL; j++) r.l[j] = (a.l[j] & m) | (b.l[j] & ~m);
   return r;
+}
+
+// src/fields/sgn.rs:20-27 on canonical words: the parity of c0, or of c1 when c0 is zero
+__device__ __forceinline__ bool sgn_words(const fqw& c0, const fqw& c1) {
+  const bool zero0 = (c0.l[0] | c0.l[1] | c0.l[2] | c0.l[3]) == 0;
+  return (c0.l[0] & 1) || (zero0 && (c1.l[0] & 1));
 }
 
 // Step 1: alpha = nrm^((p+1)/4) for the norm nrm of g.  square: alpha^2 == nrm, that is, nrm and with it g is a square; bad: alpha^2

@@ -18,12 +18,6 @@
 
 namespace {
 
-// src/fields/sgn.rs:20-27 on canonical words: the parity of c0, or of c1 when c0 is zero
-__device__ __forceinline__ bool sgn_words(const fqw& c0, const fqw& c1) {
-  const bool zero0 = (c0.l[0] | c0.l[1] | c0.l[2] | c0.l[3]) == 0;
-  return (c0.l[0] & 1) || (zero0 && (c1.l[0] & 1));
-}
-
 // xs: n x 8 words (x.c0, x.c1); sgns: n bytes; points: n x 16 words (x, y); flags: n bytes; jobs: n x 8 words ((p-1)/2 | norm(g))
 __global__ __launch_bounds__(G1R_LANES) void k_g2_recover(const u64* __restrict__ xs, const unsigned char* __restrict__ sgns, size_t n,
                                                           u64* __restrict__ points, unsigned char* __restrict__ flags,

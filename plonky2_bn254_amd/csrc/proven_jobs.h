@@ -1,9 +1,12 @@
 // Host half of the proven front-ends (msm.hip, job_outputs.hip, job_check.hip, scalar_mul.hip, g1_recover.hip, g2_recover.hip, g2_subgroup.hip, g2_cofactor.hip,
 // map_to_g1.hip, map_to_g2.hip, field_gadgets.hip): the range check of coordinates, the argument ladder of the full calls, "prove the jobs and collect
-// their outputs", the release of the proofs on an error, and the linkage of Legendre jobs to their flags.  Host code only.
+// their outputs", the release of the proofs on an error, and the linkage of Legendre jobs to their flags; and of the statement
+// verifiers (point_sum.hip, root_links.hip): their shared argument predicate verifier_args_ok and verify_proof_runs,
+// "bn254s_verify_batch once per run of consecutive proofs of one height and size, every verdict kept".  Host code only.
 // A front-end brings its kernel, its own pointer / n predicate and its linkage rule: a flat loop over the collected outputs
 // that calls release_proofs when it fails.
 #pragma once
+#include <climits>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -115,6 +118,46 @@ inline int prove_legendre(bn254s_ctx* c, const std::string& tag, const bn254s_pa
     }
   }
   return BN254S_OK;
+}
+
+// The arguments that the statement verifiers (point_sum.hip, root_links.hip) share, in the order of the header; n: the jobs of
+// the call; the context is the caller's last rung.
+inline bool verifier_args_ok(int kind, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
+                             const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, size_t n) {
+  if (!params || !words || !n_words || !degree_bits) return false;
+  if (n == 0 || n >= (size_t)UINT_MAX || per_proof == 0 || n_proofs != (n + per_proof - 1) / per_proof) return false;
+  for (size_t k = 0; k < n_proofs; k++)
+    if (!words[k]) return false;
+  return true;
+}
+
+// bn254s_verify_batch of the proofs, one call per run of consecutive proofs of one height and size, against the jobs
+// (scalars, x, offsets, outputs) cut by per_proof; offsets == nullptr for kind 2, which has none.  status [n_proofs]; text:
+// "proof k: ..." of the lowest rejected proof, or empty.  Returns BN254S_OK, BN254S_E_VERIFY, or the code of a call that failed
+// itself.
+inline int verify_proof_runs(bn254s_ctx* c, int kind, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
+                             const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* scalars,
+                             const uint64_t* x, const uint64_t* offsets, const uint64_t* outputs, size_t n, int32_t* status,
+                             std::string& text) {
+  constexpr size_t STRIDE = 160;
+  const size_t PW = kind == 0 ? 8 : kind == 1 ? 16 : 4;
+  std::vector<size_t> n_jobs(n_proofs);
+  for (size_t k = 0; k < n_proofs; k++) n_jobs[k] = (k + 1) * per_proof <= n ? per_proof : n - k * per_proof;
+  std::vector<char> err(n_proofs * STRIDE);
+  int ret = BN254S_OK;
+  for (size_t lo = 0, hi; lo < n_proofs; lo = hi) {
+    for (hi = lo + 1; hi < n_proofs && degree_bits[hi] == degree_bits[lo] && n_words[hi] == n_words[lo];) hi++;
+    const size_t j = lo * per_proof;
+    const int rc = bn254s_verify_batch(c, kind, params, degree_bits[lo], words + lo, n_words[lo], scalars + 4 * j, x + PW * j,
+                                       offsets ? offsets + PW * j : nullptr, outputs + PW * j, n_jobs.data() + lo, hi - lo,
+                                       status + lo, err.data() + lo * STRIDE, STRIDE);
+    if (rc != BN254S_OK && rc != BN254S_E_VERIFY) return rc;
+    if (rc == BN254S_E_VERIFY) ret = rc;
+  }
+  text.clear();
+  for (size_t k = 0; k < n_proofs && text.empty(); k++)
+    if (status[k] != BN254S_OK) text = "proof " + std::to_string(k) + ": " + (err.data() + k * STRIDE);
+  return ret;
 }
 
 }  // namespace

@@ -38,6 +38,10 @@ MSM_LINK_NONE = 0xFFFFFFFF  # BN254S_MSM_LINK_NONE
 # BN254S_SUM_*: the codes of point_sum_check_batch (0..7) and the link codes of verify_scalar_mul / verify_msm_multi (0..10)
 (SUM_OK, SUM_A_NOT_ZERO, SUM_A_OFF_CURVE, SUM_B_OFF_CURVE, SUM_C_OFF_CURVE, SUM_INFINITE, SUM_X, SUM_Y, SUM_X_OFF_CURVE, SUM_HEAD,
  SUM_CHAIN) = range(11)
+# `what` of root_links_check_batch, and BN254S_ROOT_*: its codes, which are the link codes of the five root verifiers
+ROOT_WHAT = (G1_RECOVER, G2_RECOVER, FQ_SQRT, FQ2_SQRT, MAP_TO_G1) = range(5)
+(ROOT_OK, ROOT_JOB_SCALAR, ROOT_JOB_BASE, ROOT_FLAG, ROOT_CARRY, ROOT_NOT_ZERO, ROOT_SQUARE, ROOT_SIGN) = range(8)
+_ROOT_IN_WORDS, _ROOT_OUT_WORDS = (4, 8, 4, 8, 4), (8, 16, 4, 8, 8)
 
 # what msm_multi_chain / msm_multi return: results [m,PW], finite [m] uint8, offsets, outputs [n,PW], R [m,PW], attempts [m] uint8,
 # bad_link [m] uint32, bad_step [m] uint16, and the proofs (None from msm_multi_chain)
@@ -144,6 +148,14 @@ def load_library():
                                                  vp, vp, vp, vp, vp, vp]
         lib.bn254s_verify_msm_multi.argtypes = [vp, C.c_int, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp,
                                                 C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "bn254s_root_links_check_batch"):   # (likewise; the six entry points of csrc/root_links.hip come together)
+        lib.bn254s_root_links_check_batch.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+        head = [vp, C.POINTER(Params), vp, vp, vp, C.c_size_t, C.c_size_t]
+        lib.bn254s_verify_g1_recover.argtypes = head + [vp, C.c_size_t, vp, vp, vp, vp, vp]
+        lib.bn254s_verify_g2_recover.argtypes = head + [vp, vp, C.c_size_t, vp, vp, vp, vp, vp]
+        lib.bn254s_verify_fq_sqrt.argtypes = head + [vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+        lib.bn254s_verify_fq2_sqrt.argtypes = head + [vp, vp, C.c_size_t, vp, vp, vp, vp, vp, vp]
+        lib.bn254s_verify_map_to_g1.argtypes = head + [vp, C.c_size_t, vp, vp, vp, vp, vp]
     if hasattr(lib, "bn254s_map_to_g1"):   # (as for bn254s_selftest_logup below: an older build in an A/B run has none of them)
         lib.bn254s_hash_to_fq.argtypes = [vp, C.c_size_t, vp]
         lib.bn254s_hash_to_fq_batch.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
@@ -842,7 +854,7 @@ class Context:
         return codes
 
     def _verify_statement(self, what, call, kind, proofs, n_links, params):
-        """The part the two statement verifiers share: the proof table, the call, and what its code means."""
+        """The part the statement verifiers share: the proof table, the call, and what its code means."""
         params = params or default_params()
         pairs = [pr if isinstance(pr, (tuple, list)) else (pr.words, pr.degree_bits) for pr in proofs]
         arrs, table = _word_arrays([w for w, _ in pairs])
@@ -895,6 +907,84 @@ class Context:
             self._h, kind, C.byref(params), table, n_words, bits, k, per_proof, _ptr(scalars), _ptr(x), seg.ctypes.data_as(C.c_void_p),
             m, n, _ptr(R), _ptr(results), finite.ctypes.data_as(C.c_void_p), _ptr(offsets), _ptr(outputs), link, status)
         return self._verify_statement("bn254s_verify_msm_multi", call, kind, proofs, m, params)
+
+    def _root_arrays(self, what, tag, xs, sgns, out, flags, root_ok, fq_jobs):
+        """The arrays of a root-link call as the library takes them: (n, xs, sgns, out, flags, root_ok, fq_jobs), each contiguous
+        or None; the bytes are kept as the caller gave them so that the library sees a value above 1."""
+        if what not in ROOT_WHAT:
+            raise ValueError(f"{tag}: what {what!r} is none of 0..4")
+        xs = np.ascontiguousarray(xs, dtype=np.uint64).reshape(-1, _ROOT_IN_WORDS[what])
+        n = xs.shape[0]
+        nj = 2 * n if what == MAP_TO_G1 else n
+        out = np.ascontiguousarray(out, dtype=np.uint64).reshape(-1, _ROOT_OUT_WORDS[what])
+        flags = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+        sgns = None if sgns is None or what in (G1_RECOVER, MAP_TO_G1) else np.ascontiguousarray(sgns, dtype=np.uint8).reshape(-1)
+        root_ok = np.ascontiguousarray(root_ok, dtype=np.uint8).reshape(-1) if what in (FQ_SQRT, FQ2_SQRT) else None
+        fq_jobs = None if fq_jobs is None else np.ascontiguousarray(fq_jobs, dtype=np.uint64).reshape(-1, 8)
+        if out.shape[0] != n or flags.shape != (nj,) or (sgns is not None and sgns.shape != (n,)) or \
+                (root_ok is not None and root_ok.shape != (n,)) or (fq_jobs is not None and fq_jobs.shape != (nj, 8)):
+            raise ValueError(f"{tag}: {n} inputs with out {out.shape}, flags {flags.shape}, "
+                             f"sgns {None if sgns is None else sgns.shape}, root_ok {None if root_ok is None else root_ok.shape}, "
+                             f"fq_jobs {None if fq_jobs is None else fq_jobs.shape}")
+        return n, xs, sgns, out, flags, root_ok, fq_jobs
+
+    def root_links_check_batch(self, what, xs, out, flags, sgns=None, root_ok=None, fq_jobs=None):
+        """The field linkage of a Legendre-proven front-end on the device (bn254s_root_links_check_batch).  what: G1_RECOVER,
+        G2_RECOVER, FQ_SQRT, FQ2_SQRT or MAP_TO_G1; xs [n, 4 | 8] the inputs (u for MAP_TO_G1); out the points [n, 8 | 16] or roots
+        [n, 4 | 8]; flags [n] (sq_flags [2n] for MAP_TO_G1; `square` for the roots); sgns [n] (None: all 0; not read for G1_RECOVER,
+        MAP_TO_G1); root_ok [n] for the roots; fq_jobs [n | 2n, 8] or None -> (codes [n] uint8, bases [n | 2n, 4]): ROOT_OK or
+        the first of ROOT_JOB_SCALAR .. ROOT_SIGN that applies, and the canonical base of every job as computed on the device.
+        A coordinate >= p that would be read as a field element raises (-1, the message names the array and the row)."""
+        tag = "root_links_check"
+        n, xs, sgns, out, flags, root_ok, fq_jobs = self._root_arrays(what, tag, xs, sgns, out, flags, root_ok, fq_jobs)
+        codes, bases = np.zeros(n, np.uint8), np.zeros((flags.shape[0], 4), np.uint64)
+        bp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.bn254s_root_links_check_batch(self._h, what, _ptr(xs), bp(sgns), n, _ptr(out), bp(flags), bp(root_ok),
+                                                            bp(fq_jobs), bp(codes), _ptr(bases)), "bn254s_root_links_check_batch")
+        return codes, bases
+
+    def _verify_roots(self, what, fn, proofs, per_proof, xs, sgns, out, flags, root_ok, fq_jobs, params):
+        """The five root verifiers: the arrays, the call in the argument order of its `what`, _verify_statement."""
+        n, xs, sgns, out, flags, root_ok, fq_jobs = self._root_arrays(what, fn[len("bn254s_"):], xs, sgns, out, flags, root_ok, fq_jobs)
+        bp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        mid = ([_ptr(xs)] + ([] if what in (G1_RECOVER, MAP_TO_G1) else [bp(sgns)]) + [n, _ptr(out), bp(flags)] +
+               ([bp(root_ok)] if what in (FQ_SQRT, FQ2_SQRT) else []) + [bp(fq_jobs)])
+        call = lambda params, table, n_words, bits, k, link, status: getattr(self._lib, fn)(
+            self._h, C.byref(params), table, n_words, bits, k, per_proof, *mid, link, status)
+        return self._verify_statement(fn, call, 2, proofs, n, params)
+
+    def verify_g1_recover(self, proofs, per_proof, xs, points, flags, fq_jobs=None, params: Optional[Params] = None):
+        """The statement of a g1_recover_from_x call (bn254s_verify_g1_recover): flags[i] says whether x_i^3 + 3 is a square, and
+        points[i] is (x_i, y_i) with y_i its even root where it is and (x_i, 0) where it is not.  The linkage is checked on the
+        device, and every Fq-exp proof by verify_batch against jobs computed here: (p-1)/2, x_i^3 + 3, and 1 or p - 1 as the flag
+        says - so fq_jobs is only compared and may be None.  `proofs`: objects with `words` and `degree_bits`, or (words,
+        degree_bits) pairs, proof k for jobs k per_proof ...  -> (link_codes [n] uint8, proof_status [n_proofs] int32), all
+        zero; a rejection raises VerifyError with the message of the smallest failing input, or of the first rejected proof
+        where every link holds, and both arrays as its `link_codes` (ROOT_*) and `proof_status`."""
+        return self._verify_roots(G1_RECOVER, "bn254s_verify_g1_recover", proofs, per_proof, xs, None, points, flags, None, fq_jobs, params)
+
+    def verify_g2_recover(self, proofs, per_proof, xs, sgns, points, flags, fq_jobs=None, params: Optional[Params] = None):
+        """The statement of a g2_recover_from_x call (bn254s_verify_g2_recover): flags[i] says whether g = x_i^3 + b' is a square
+        of Fq2 (the proven symbol is that of norm(g)), and points[i] is (x_i, y_i) with y_i^2 = g and sgn(y_i) == sgns[i] (None:
+        all 0) where it is and (x_i, 0) where it is not.  Otherwise as verify_g1_recover."""
+        return self._verify_roots(G2_RECOVER, "bn254s_verify_g2_recover", proofs, per_proof, xs, sgns, points, flags, None, fq_jobs, params)
+
+    def verify_fq_sqrt(self, proofs, per_proof, xs, sgns, roots, square, root_ok, fq_jobs=None, params: Optional[Params] = None):
+        """The statement of an fq_sqrt call (bn254s_verify_fq_sqrt): square[i] says whether the Legendre symbol of x_i is 1 (the
+        proofs are judged against 1, p - 1, or 0 for x_i = 0), root_ok[i] whether a root with the parity sgns[i] exists, and
+        roots[i] is that root or zero.  Otherwise as verify_g1_recover."""
+        return self._verify_roots(FQ_SQRT, "bn254s_verify_fq_sqrt", proofs, per_proof, xs, sgns, roots, square, root_ok, fq_jobs, params)
+
+    def verify_fq2_sqrt(self, proofs, per_proof, xs, sgns, roots, square, root_ok, fq_jobs=None, params: Optional[Params] = None):
+        """The Fq2 twin of verify_fq_sqrt (bn254s_verify_fq2_sqrt): the symbol of norm(x_i), the square in Fq2, the sign of
+        sgn.rs:20-27."""
+        return self._verify_roots(FQ2_SQRT, "bn254s_verify_fq2_sqrt", proofs, per_proof, xs, sgns, roots, square, root_ok, fq_jobs, params)
+
+    def verify_map_to_g1(self, proofs, per_proof, u, points, sq_flags, fq_jobs=None, params: Optional[Params] = None):
+        """The statement of a map_to_g1 call (bn254s_verify_map_to_g1): sq_flags[2i], sq_flags[2i + 1] say whether g(x1), g(x2) of
+        the candidates of u_i are squares (2n jobs: len(proofs) == ceil(2n / per_proof)), and points[i] is the candidate that they
+        select with the root of g of the parity of u_i.  link_codes is [n], per input.  Otherwise as verify_g1_recover."""
+        return self._verify_roots(MAP_TO_G1, "bn254s_verify_map_to_g1", proofs, per_proof, u, None, points, sq_flags, None, fq_jobs, params)
 
     def ctl_values(self, kind, scalars, x, offset, outputs):
         """(input rows [n, 81|145|33], output rows [n, 33|65|17]): the extra looking values of the two CTLs."""
