@@ -289,7 +289,7 @@ int bn254s_g2_msm(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* 
 /* G1 point recovery from x: the witness side of G1Target::is_recoverable_from_x / recover_from_x (src/curves/g1.rs:76-95; native
  * form src/fields/recover.rs; is_square src/fields/fq.rs:283-295, sqrt_with_sgn src/fields/fq.rs:266-281).  For every x_i
  * (4 words, canonical: some x_i >= p is BN254S_E_INVALID_ARG, found on the host before any device work, and bn254s_last_error
- * names the first such i) the device computes g_i = x_i^3 + 3 and one exponentiation c = g_i^((p+1)/4) (csrc/g1_recover.hip):
+ * names the first such i) the device computes g_i = x_i^3 + 3 and one exponentiation c = g_i^((p+1)/4) (csrc/root_front.hip):
  *   flags_out[i]  = 1 iff g_i is a square in Fq (g_i is never zero: -3 is not a cube modulo p);
  *   points_out[i] = (x_i, y_i) with y_i^2 = g_i, y_i < p and y_i even ("sgn false") where the flag is 1, (x_i, 0) where it is 0;
  *   fq_jobs[i]    = (p-1)/2 | g_i (8 words; may be NULL): the Fq-exp job whose output is the Legendre symbol of g_i.
@@ -300,8 +300,8 @@ int bn254s_g1_recover_from_x_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 4,
 /* The front-end plus the Fq-exp proofs of the n Legendre jobs, cut into ceil(n / per_proof) proofs exactly as
  * bn254s_prove_batch (kind 2) cuts them.  The outputs of the proofs are checked word for word against the flags: job i must
  * give 1 where flags_out[i] is 1 and p - 1 where it is 0; a mismatch is BN254S_E_INTERNAL.  On any error every proof of the call
- * is freed and its slot in fq_proofs is NULL.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work (invalid
- * arguments are reported first). */
+ * is freed and its slot in fq_proofs is NULL, and points_out, flags_out and fq_jobs are written on success only.
+ * per_proof > 16384: BN254S_E_UNSUPPORTED before any device work (invalid arguments are reported first). */
 int bn254s_g1_recover_from_x(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* xs, size_t n, size_t per_proof,
                              uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs /* may be NULL */,
                              bn254s_proof** fq_proofs);
@@ -309,7 +309,7 @@ int bn254s_g1_recover_from_x(bn254s_ctx* ctx, const bn254s_params* params, const
  * (src/fields/fq2.rs:228-241) and Fq2Target::sqrt_with_sgn (fq2.rs:209-226; sign rule src/fields/sgn.rs:20-27).  For every x_i
  * (8 words: x.c0, x.c1, each canonical) and wanted sign sgns[i] (0 or 1; sgns == NULL: all 0) the device computes
  * g_i = x_i^3 + b' in Fq2 (b' = 3/(9+u), the twist coefficient), its norm N_i = g_i.c0^2 + g_i.c1^2 and the root by two
- * exponentiations with (p+1)/4 and one inversion (csrc/g2_recover.hip):
+ * exponentiations with (p+1)/4 and one inversion (csrc/root_front.hip):
  *   flags_out[i]  = 1 iff g_i is a square in Fq2, that is iff N_i is a square in Fq: x_i is the x of a point ON THE TWIST CURVE.
  *                   Membership in the r-torsion subgroup is NOT checked (the reference's gadgets do not check it either):
  *                   bn254s_g2_subgroup_check does that.
@@ -327,15 +327,16 @@ int bn254s_g2_recover_from_x_batch(bn254s_ctx* ctx, const uint64_t* xs /* n x 8:
 /* The front-end plus the Fq-exp proofs of the n Legendre jobs, cut into ceil(n / per_proof) proofs exactly as
  * bn254s_prove_batch (kind 2) cuts them.  The outputs of the proofs are checked word for word against the flags: job i must
  * give 1 where flags_out[i] is 1 and p - 1 where it is 0; a mismatch is BN254S_E_INTERNAL.  On any error every proof of the call
- * is freed and its slot in fq_proofs is NULL.  per_proof > 16384: BN254S_E_UNSUPPORTED before any device work (invalid
- * arguments are reported first).  points_out is the `x` argument of bn254s_g2_msm as it stands. */
+ * is freed and its slot in fq_proofs is NULL, and points_out, flags_out and fq_jobs are written on success only.
+ * per_proof > 16384: BN254S_E_UNSUPPORTED before any device work (invalid arguments are reported first).  points_out is the
+ * `x` argument of bn254s_g2_msm as it stands. */
 int bn254s_g2_recover_from_x(bn254s_ctx* ctx, const bn254s_params* params, const uint64_t* xs, const uint8_t* sgns, size_t n,
                              size_t per_proof, uint64_t* points_out, uint8_t* flags_out, uint64_t* fq_jobs /* may be NULL */,
                              bn254s_proof** fq_proofs);
 /* The field gadgets on their own: the witness side of FqTarget::is_square (src/fields/fq.rs:283-295), FqTarget::sqrt_with_sgn
  * (fq.rs:266-281, generator :357-365), Fq2Target::is_square (src/fields/fq2.rs:228-241), Fq2Target::sqrt_with_sgn (fq2.rs:209-226,
  * generator :305-313; sign rule src/fields/sgn.rs) and the two inv gadgets (fq.rs:241-255, fq2.rs:190-204; native inv.rs), for a
- * value that is not the g(x) of a curve (csrc/field_gadgets.hip; the recovery and map calls above fuse the same arithmetic behind
+ * value that is not the g(x) of a curve (csrc/root_front.hip, the inversions csrc/field_gadgets.hip; the recovery and map calls above fuse the same arithmetic behind
  * their equations).  For every x_i (Fq: 4 words; Fq2: 8 words c0, c1; each coordinate canonical) and wanted sign sgns[i] (0 or 1;
  * sgns == NULL: all 0), exactly and with canonical outputs:
  *   square_out[i]  = the is_square gadget: 1 iff b^((p-1)/2) == 1 for b = x_i (Fq) or b = norm(x_i) = c0^2 + c1^2 (Fq2).  0 for

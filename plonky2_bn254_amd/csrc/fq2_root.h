@@ -1,5 +1,5 @@
-// The square root in Fq2 = Fq[u]/(u^2 + 1) that the kernels share (g2_recover.hip, map_to_g2.hip, field_gadgets.hip), in two Fq
-// exponentiations with the exponent (p+1)/4 of sqrt_ladder.h (p = 3 mod 4); why the formulas hold: the head of g2_recover.hip.
+// The square root in Fq2 = Fq[u]/(u^2 + 1) that the kernels share (root_front.hip, map_to_g2.hip), in two Fq
+// exponentiations with the exponent (p+1)/4 of sqrt_ladder.h (p = 3 mod 4); why the formulas hold: the head of root_front.hip.
 // One lane per element, blocks of G1R_LANES lanes, `tab` the ladder's table in LDS.  Also the sign of an Fq2 element on
 // canonical words (sgn_words), which the kernels that make a root and the one that checks it (root_links.hip) share.
 #pragma once
@@ -29,15 +29,7 @@ __device__ __forceinline__ bool sgn_words(const fqw& c0, const fqw& c1) {
   return (c0.l[0] & 1) || (zero0 && (c1.l[0] & 1));
 }
 
-// Step 1: alpha = nrm^((p+1)/4) for the norm nrm of g.  square: alpha^2 == nrm, that is, nrm and with it g is a square; bad: alpha^2
-// is neither nrm nor -nrm, the ladder is wrong.
-__device__ __forceinline__ fq fq2_norm_root(u32 (*tab)[FQ_NL][G1R_LANES], const fq& nrm, bool& square, bool& bad) {
-  const fq alpha = sqrt_ladder(tab, nrm);
-  const fq a2 = fq_sqr(alpha);
-  square = fq_eq(a2, nrm);
-  bad = !square && !fq_eq(a2, fq_neg(nrm));  // neither root nor non-residue
-  return alpha;
-}
+// Step 1 is fq_root (sqrt_ladder.h) of the norm nrm of g: alpha = nrm^((p+1)/4), and nrm and with it g is a square iff alpha^2 == nrm.
 // Step 2: a root y of g from alpha and square of step 1; bad is raised where a check fails.
 // Every lane runs the ladder, so that a wave stays together: where g is no square it works on delta = 1 (t = 1, an inverse of 2)
 // and the caller masks its y.
@@ -56,7 +48,7 @@ __device__ __forceinline__ fq2 fq2_root_from_alpha(u32 (*tab)[FQ_NL][G1R_LANES],
   return y;
 }
 __device__ __forceinline__ fq2 fq2_root(u32 (*tab)[FQ_NL][G1R_LANES], const fq2& g, const fq& nrm, bool& square, bool& bad) {
-  const fq alpha = fq2_norm_root(tab, nrm, square, bad);
+  const fq alpha = fq_root(tab, nrm, square, bad);
   return fq2_root_from_alpha(tab, g, alpha, square, bad);
 }
 

@@ -25,7 +25,7 @@
 //  - Q + T (three times) and the comparison: the operands depend on P through psi, nothing is known about them - T is O
 //    for instance whenever psi(2Q) is, and U == -P is the very question.  g2_add_lean, the complete law of pt_add_complete
 //    (chain_scan.h), and a comparison that cross-multiplies and knows O (P and psi(P) are finite).
-// One lane per point, like k_g2_recover; x0 is a compile-time constant, so every lane of a wave doubles and adds in the same
+// One lane per point, like k_root; x0 is a compile-time constant, so every lane of a wave doubles and adds in the same
 // steps.  P stays affine through the ladder (mixed addition, Z2 = 1).
 #include <climits>
 #include "g2_endo.h"

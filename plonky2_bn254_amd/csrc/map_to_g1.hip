@@ -18,17 +18,11 @@
 #include <cstring>
 #include <string>
 #include <vector>
-#include "fq2_root.h"  // fq_select, fq_from_limbs
 #include "hash_to_fq.h"
 #include "job_device.h"
-#include "proven_jobs.h"
-#include "sqrt_ladder.h"
-#include "map_to_g1_constants.inc"
+#include "root_kinds.h"  // m2g1_candidates, curve_rhs, prove_legendre
 
 namespace {
-
-// x^3 + 3
-__device__ __forceinline__ fq g1_rhs(const fq& x, const fq& three) { return fq_add(fq_mul(fq_sqr(x), x), three); }
 
 // points: n x 8 words (x, y); flags: 2n bytes; jobs: 2n x 8 words (scalar (p-1)/2 | g(x_i)); job and flag 2k+i belong to x_{i+1}.
 // Every lane runs the same three ladders over the one table in LDS, so that a wave stays together; the choice goes through
@@ -42,38 +36,16 @@ __global__ __launch_bounds__(G1R_LANES) void k_m2g1_point(const u64* __restrict_
   if (k >= n) return;
   const fq uu = fq_from_canonical(u + 4 * k);
   const bool u_odd = u[4 * k] & 1;
-  const fq one = fq_one();
-  const fq three = fq_add(fq_dbl(one), one);
   fq x1, x2, x3;
-  {
-    fq tv1 = fq_dbl(fq_dbl(fq_sqr(uu)));  // u^2 g(Z), g(Z) = 4
-    const fq tv2 = fq_add(one, tv1);
-    tv1 = fq_sub(one, tv1);
-    const fq prod = fq_mul(tv1, tv2);  // zero only for u = +-1/2 (-1 is no square); fq_inv gives 0 there, the select says so
-    const fq tv3 = fq_select(fq_is_zero(prod), fq_zero(), fq_inv(prod));
-    const fq tv5 = fq_mul(fq_mul(fq_mul(uu, tv1), tv3), fq_from_limbs(M2G1_TV4));
-    const fq nz2 = fq_from_limbs(M2G1_NEG_Z_BY_2);
-    x1 = fq_sub(nz2, tv5);
-    x2 = fq_add(nz2, tv5);
-    const fq t = fq_mul(fq_sqr(tv2), tv3);
-    x3 = fq_add(one, fq_mul(fq_from_limbs(M2G1_TV6), fq_sqr(t)));
-  }
+  m2g1_candidates(uu, x1, x2, x3);  // root_kinds.h: the checker's, too
   fq x = x3;
-  bool any, bad;
-  fq c;
-  {
-    const fq g3 = g1_rhs(x3, three);
-    c = sqrt_ladder(tab, g3);
-    const fq c2 = fq_sqr(c);
-    any = fq_eq(c2, g3);
-    bad = !any && !fq_eq(c2, fq_neg(g3));  // neither root nor non-residue: the ladder is wrong
-  }
+  bool any, bad;  // bad: some c^2 is neither g nor -g, the ladder is wrong
+  fq c = fq_root(tab, curve_rhs(x3), any, bad);
   auto prefer = [&](const fq& xi, int i) {
-    const fq gi = g1_rhs(xi, three);
-    const fq ci = sqrt_ladder(tab, gi);  // overwrites the lane's own table entries: no barrier
-    const fq c2 = fq_sqr(ci);
-    const bool sq = fq_eq(c2, gi);
-    bad |= !sq && !fq_eq(c2, fq_neg(gi));
+    const fq gi = curve_rhs(xi);
+    bool sq, bd;
+    const fq ci = fq_root(tab, gi, sq, bd);  // overwrites the lane's own table entries: no barrier
+    bad |= bd;
     x = fq_select(sq, xi, x);
     c = fq_select(sq, ci, c);
     any |= sq;

@@ -59,12 +59,8 @@ __device__ __forceinline__ fq2 g_rhs(const fq2& x, const fq2& b2) { return fq2_a
 __device__ __forceinline__ bool fq_is_square(const fq& a, const M2GConsts& C) {
   return fq_is_zero(a) || fq_eq(fq_pow_words(a, C.leg), fq_one());
 }
-// src/fields/sgn.rs:20-27
-__device__ __forceinline__ bool f2_sgn(const fq2& a) {
-  const fqw c0 = fq_to_canonical(a.c0), c1 = fq_to_canonical(a.c1);
-  const bool zero0 = (c0.l[0] | c0.l[1] | c0.l[2] | c0.l[3]) == 0;
-  return (c0.l[0] & 1) || (zero0 && (c1.l[0] & 1));
-}
+// src/fields/sgn.rs:20-27 (sgn_words of fq2_root.h, on the canonical words)
+__device__ __forceinline__ bool f2_sgn(const fq2& a) { return sgn_words(fq_to_canonical(a.c0), fq_to_canonical(a.c1)); }
 // QuadExtField::sqrt of ark-ff 0.4 for a square a; *ok = false if the candidate does not square back
 __device__ __noinline__ fq2 f2_sqrt(const fq2& a, const M2GConsts& C, bool* ok) {
   fq2 r;
@@ -162,7 +158,7 @@ __global__ __launch_bounds__(64) void k_m2g_finish(const u64* __restrict__ o, co
 }
 
 // The point (x, y) of hash_to_g2.rs:119-145 without the proven Legendre symbols: the candidates, "g(x1) is a square" and "g(x2) is
-// a square" from the norm's exponentiation as k_g2_recover decides its flag (fq2_root.h), the choice of x, and y = sqrt(g(x)) with
+// a square" from the norm's exponentiation as G2 recovery decides its flag (fq2_root.h), the choice of x, and y = sqrt(g(x)) with
 // sgn(y) = sgn(u).  The two roots +-y have opposite signs under sgn.rs:20-27, so any root followed by the sign fix is the
 // reference's y.  Every lane runs the three norm ladders and one root ladder, so that a wave stays together.
 // points: n x 16 canonical words; *err: BN254S_E_INTERNAL if g of the chosen x is no square or a root does not square back.
@@ -177,11 +173,11 @@ __global__ __launch_bounds__(G1R_LANES) void k_m2g_point(const u64* __restrict__
   // from x3 down to x1, so that the first candidate with a square g(x) is the one that stays
   fq2 x = x3, g = g_rhs(x3, b2);
   bool square, bad;
-  fq alpha = fq2_norm_root(tab, fq2_norm(g), square, bad);
+  fq alpha = fq_root(tab, fq2_norm(g), square, bad);
   auto prefer = [&](const fq2& xi) {
     const fq2 gi = g_rhs(xi, b2);
     bool sq, bd;
-    const fq ai = fq2_norm_root(tab, fq2_norm(gi), sq, bd);
+    const fq ai = fq_root(tab, fq2_norm(gi), sq, bd);
     bad |= bd;
     x.c0 = fq_select(sq, xi.c0, x.c0);
     x.c1 = fq_select(sq, xi.c1, x.c1);

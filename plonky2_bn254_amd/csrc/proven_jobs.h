@@ -1,6 +1,6 @@
-// Host half of the proven front-ends (msm.hip, job_outputs.hip, job_check.hip, scalar_mul.hip, g1_recover.hip, g2_recover.hip, g2_subgroup.hip, g2_cofactor.hip,
+// Host half of the proven front-ends (msm.hip, job_outputs.hip, job_check.hip, scalar_mul.hip, root_front.hip, g2_subgroup.hip, g2_cofactor.hip,
 // map_to_g1.hip, map_to_g2.hip, field_gadgets.hip): the range check of coordinates, the argument ladder of the full calls, "prove the jobs and collect
-// their outputs", the release of the proofs on an error, and the linkage of Legendre jobs to their flags; and of the statement
+// their outputs" and the release of the proofs on an error (the linkage of Legendre jobs to their flags: root_kinds.h); and of the statement
 // verifiers (point_sum.hip, root_links.hip): their shared argument predicate verifier_args_ok and verify_proof_runs,
 // "bn254s_verify_batch once per run of consecutive proofs of one height and size, every verdict kept".  Host code only.
 // A front-end brings its kernel, its own pointer / n predicate and its linkage rule: a flat loop over the collected outputs
@@ -86,36 +86,6 @@ inline int prove_and_collect(bn254s_ctx* c, const std::string& tag, int kind, co
     }
     memcpy(outs.data() + PW * pos, o, 8 * len);
     pos += cnt;
-  }
-  return BN254S_OK;
-}
-
-// Proves the n Legendre jobs (8 words each: (p-1)/2 | base) as Fq-exp proofs and checks every proven output against its flag:
-// the trace generator computes base_i^((p-1)/2) on its own; it must be 1 where the flag is set and p - 1 where it is not.
-// zero_bases: the bases may be zero (field_gadgets.hip; a curve equation's never are), and the rule is three-valued: a clear flag
-// asks for 0 where the job's base is zero and for p - 1 where it is not.
-// fq_proofs: ceil(n / per_proof) slots; on any error every proof is freed and its slot is NULL.
-inline int prove_legendre(bn254s_ctx* c, const std::string& tag, const bn254s_params* params, const std::vector<u64>& jobs,
-                          const uint8_t* flags, size_t n, size_t per_proof, bn254s_proof** fq_proofs, bool zero_bases = false) {
-  std::vector<u64> s(4 * n), g(4 * n), outs;
-  for (size_t i = 0; i < n; i++) {
-    memcpy(s.data() + 4 * i, jobs.data() + 8 * i, 32);
-    memcpy(g.data() + 4 * i, jobs.data() + 8 * i + 4, 32);
-  }
-  int rc = prove_and_collect(c, tag, 2, params, s.data(), g.data(), nullptr, n, per_proof, fq_proofs, outs);
-  if (rc != BN254S_OK) return rc;
-  u64 pm1[4];
-  memcpy(pm1, G1R_P, 32);
-  pm1[0] -= 1;
-  static const u64 ONE[4] = {1, 0, 0, 0}, ZERO[4] = {0, 0, 0, 0};
-  for (size_t i = 0; i < n; i++) {
-    const bool zero = zero_bases && !flags[i] && memcmp(g.data() + 4 * i, ZERO, 32) == 0;
-    if (memcmp(outs.data() + 4 * i, flags[i] ? ONE : zero ? ZERO : pm1, 32) != 0) {
-      c->set_err(tag + ": the proven Legendre symbol of input " + std::to_string(i) + " is not " +
-                 (flags[i] ? "1, but its flag is set" : zero ? "0, but its base is zero" : "p - 1, but its flag is clear"));
-      release_proofs(fq_proofs, n, per_proof);
-      return BN254S_E_INTERNAL;
-    }
   }
   return BN254S_OK;
 }

@@ -1,4 +1,4 @@
-// Statement verifiers of the Legendre-proven front-ends (g1_recover.hip, g2_recover.hip, field_gadgets.hip, map_to_g1.hip).  Their
+// Statement verifiers of the Legendre-proven front-ends (root_front.hip, map_to_g1.hip).  Their
 // Fq-exp proofs say base^((p-1)/2) == output and nothing else.  What a caller wants to know - flags[i] says whether g(x_i) is a
 // square and points[i] is the root with the wanted sign; points[i] is the map_to_g1 image of u_i - follows from the proofs only
 // with the linkage: the base of job i is really x_i^3 + 3 (norm(x_i^3 + b'), x_i, norm(x_i), g of the SvdW candidate), the proven
@@ -9,30 +9,20 @@
 // and the five verifiers are host code over it and bn254s_verify_batch.
 //
 // No LDS table, no ladder, no exponentiation: a root is CHECKED, y^2 == radicand, never computed.  The cost is a few products per
-// input; map_to_g1 adds the one inversion of its tv3, under the same select as k_m2g1_point.  A lane's code depends on its own
-// input alone (no cross-lane operation), so it does not matter how a wave diverges on the early returns.  The base and its
-// comparison with the job are finished before the root equation starts.
+// input; map_to_g1 adds the one inversion of its tv3, in the m2g1_candidates that k_m2g1_point calls.  What a kind's rows hold,
+// its radicand, its base and the output that a flag demands are those of the producers: root_kinds.h.  A lane's code depends on
+// its own input alone (no cross-lane operation), so it does not matter how a wave diverges on the early returns.  The base and
+// its comparison with the job are finished before the root equation starts.
 //
 // The symbol itself is never computed here either: the verifiers hand bn254s_verify_batch the base from the device and the output
 // that the FLAG demands (1 | p - 1 | 0), so that an accepted proof proves the flag.  fq_jobs of the caller is only compared.
 #include <climits>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
-#include "fq2_root.h"  // fq_select, fq_from_limbs, sgn_words, the constants of the twist
-#include "map_to_g1_constants.inc"
-#include "proven_jobs.h"
+#include "root_kinds.h"
 
 namespace {
-
-enum { RL_G1_RECOVER = 0, RL_G2_RECOVER = 1, RL_FQ_SQRT = 2, RL_FQ2_SQRT = 3, RL_MAP_TO_G1 = 4, RL_KINDS = 5 };
-// words of an input, words of a row of points / roots, the words of such a row before its y / root, jobs per input
-constexpr size_t rl_in_words(int what) { return what == RL_G2_RECOVER || what == RL_FQ2_SQRT ? 8 : 4; }
-constexpr size_t rl_out_words(int what) { return what == RL_G2_RECOVER ? 16 : what == RL_FQ_SQRT ? 4 : 8; }
-constexpr size_t rl_root_at(int what) { return what == RL_FQ_SQRT || what == RL_FQ2_SQRT ? 0 : what == RL_G2_RECOVER ? 8 : 4; }
-constexpr size_t rl_jobs(int what) { return what == RL_MAP_TO_G1 ? 2 : 1; }
-constexpr bool rl_is_sqrt(int what) { return what == RL_FQ_SQRT || what == RL_FQ2_SQRT; }
 
 template <int N>
 __device__ __forceinline__ bool words_differ(const u64* __restrict__ a, const u64* __restrict__ b) {
@@ -74,18 +64,6 @@ __device__ __forceinline__ void words_store(u64* __restrict__ w, const fqw& a) {
 // the sign of canonical words: Fq the parity, Fq2 the rule of sgn.rs:20-27
 __device__ __forceinline__ bool sgn_of(const u64* __restrict__ w, const fq&) { return w[0] & 1; }
 __device__ __forceinline__ bool sgn_of(const u64* __restrict__ w, const fq2&) { return sgn_words(words_load(w), words_load(w + 4)); }
-// x^3 + b on G1 and on the twist
-__device__ __forceinline__ fq curve_rhs(const fq& x) {
-  const fq one = fq_one();
-  return fq_add(fq_mul(fq_sqr(x), x), fq_add(fq_dbl(one), one));
-}
-__device__ __forceinline__ fq2 curve_rhs(const fq2& x) {
-  fq2 b;
-  b.c0 = fq_from_limbs(G2R_B_C0);
-  b.c1 = fq_from_limbs(G2R_B_C1);
-  return fq2_add(fq2_mul(fq2_sqr(x), x), b);
-}
-
 // The claimed root yw (canonical words below p) of the radicand: codes 6, 7, 0
 template <class F>
 __device__ __forceinline__ unsigned root_code(const F& radicand, const u64* __restrict__ yw, bool want) {
@@ -101,27 +79,13 @@ __device__ __forceinline__ unsigned root_links_code(size_t k, const u64* __restr
                                                     const u64* __restrict__ out, const unsigned char* __restrict__ flags,
                                                     const unsigned char* __restrict__ root_ok, const u64* __restrict__ jobs,
                                                     u64* __restrict__ bases) {
-  constexpr int IW = (int)rl_in_words(WHAT), OW = (int)rl_out_words(WHAT);
-  using F = std::conditional_t<IW == 8, fq2, fq>;
+  constexpr int IW = (int)root_in_words(WHAT), OW = (int)root_out_words(WHAT);
+  using F = root_field<WHAT>;
   const u64* xw = in + IW * k;
   const u64* ow = out + OW * k;
-  if constexpr (WHAT == RL_MAP_TO_G1) {
-    const fq u = fq_from_canonical(xw);
-    const fq one = fq_one();
+  if constexpr (WHAT == ROOT_MAP_TO_G1) {
     fq x1, x2, x3;
-    {  // the candidates of k_m2g1_point
-      fq tv1 = fq_dbl(fq_dbl(fq_sqr(u)));
-      const fq tv2 = fq_add(one, tv1);
-      tv1 = fq_sub(one, tv1);
-      const fq prod = fq_mul(tv1, tv2);  // zero only for u = +-1/2
-      const fq tv3 = fq_select(fq_is_zero(prod), fq_zero(), fq_inv(prod));
-      const fq tv5 = fq_mul(fq_mul(fq_mul(u, tv1), tv3), fq_from_limbs(M2G1_TV4));
-      const fq nz2 = fq_from_limbs(M2G1_NEG_Z_BY_2);
-      x1 = fq_sub(nz2, tv5);
-      x2 = fq_add(nz2, tv5);
-      const fq t = fq_mul(fq_sqr(tv2), tv3);
-      x3 = fq_add(one, fq_mul(fq_from_limbs(M2G1_TV6), fq_sqr(t)));
-    }
+    m2g1_candidates(fq_from_canonical(xw), x1, x2, x3);
     {
       const fqw b1 = fq_to_canonical(curve_rhs(x1)), b2 = fq_to_canonical(curve_rhs(x2));
       if (bases) {
@@ -144,28 +108,17 @@ __device__ __forceinline__ unsigned root_links_code(size_t k, const u64* __restr
     F x;
     fe_from_canonical(xw, x);
     F radicand;
-    fqw base;
-    if constexpr (WHAT == RL_G1_RECOVER) {
-      radicand = curve_rhs(x);
-      base = fq_to_canonical(radicand);
-    } else if constexpr (WHAT == RL_G2_RECOVER) {
-      radicand = curve_rhs(x);
-      base = fq_to_canonical(fq2_norm(radicand));
-    } else if constexpr (WHAT == RL_FQ_SQRT) {
-      radicand = x;
-      base = words_load(xw);
-    } else {
-      radicand = x;
-      base = fq_to_canonical(fq2_norm(x));
-    }
+    fq b;
+    root_radicand_base<WHAT>(x, radicand, b);
+    const fqw base = root_base_words<WHAT>(xw, b);
     if (bases) words_store(bases + 4 * k, base);
     if (jobs) {
       if (job_scalar_differs(jobs + 8 * k)) return BN254S_ROOT_JOB_SCALAR;
       if (job_base_differs(jobs + 8 * k, base)) return BN254S_ROOT_JOB_BASE;
     }
-    const unsigned flag = flags[k], sgn = WHAT == RL_G1_RECOVER ? 0u : (unsigned)sgns[k];  // G1: the even root
+    const unsigned flag = flags[k], sgn = WHAT == ROOT_G1_RECOVER ? 0u : (unsigned)sgns[k];  // G1: the even root
     if (flag > 1 || sgn > 1) return BN254S_ROOT_FLAG;
-    if constexpr (rl_is_sqrt(WHAT)) {
+    if constexpr (root_is_sqrt(WHAT)) {
       const unsigned ok = root_ok[k];
       const bool zero = (base.l[0] | base.l[1] | base.l[2] | base.l[3]) == 0;
       if (ok > 1 || (flag && zero) || (ok != 0) != (zero ? sgn == 0 : flag != 0)) return BN254S_ROOT_FLAG;
@@ -199,7 +152,7 @@ __global__ __launch_bounds__(64) void k_root_links(const u64* __restrict__ in, c
 // context's stream, one wait.  The caller has checked ranges and counts.
 int root_run(bn254s_ctx* c, int what, const uint64_t* in, const uint8_t* sgns, size_t n, const uint64_t* out, const uint8_t* flags,
              const uint8_t* root_ok, const uint64_t* jobs, uint8_t* codes, uint64_t* bases, unsigned* first) {
-  const size_t IW = rl_in_words(what), OW = rl_out_words(what), nj = rl_jobs(what) * n;
+  const size_t IW = root_in_words(what), OW = root_out_words(what), nj = root_jobs(what) * n;
   const size_t nb = (n + 7) / 8, njb = (nj + 7) / 8;  // words that hold n, nj bytes
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t st = c->stream;
@@ -215,21 +168,21 @@ int root_run(bn254s_ctx* c, int what, const uint64_t* in, const uint8_t* sgns, s
   HIP_TRY(c, hipMemcpyAsync(d_out, out, n * OW * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(d_flags, flags, nj, hipMemcpyHostToDevice, st));
   if (jobs) HIP_TRY(c, hipMemcpyAsync(d_jobs, jobs, nj * 64, hipMemcpyHostToDevice, st));
-  if (what != RL_G1_RECOVER && what != RL_MAP_TO_G1) {
+  if (root_has_sgns(what)) {
     if (sgns)
       HIP_TRY(c, hipMemcpyAsync(d_sgns, sgns, n, hipMemcpyHostToDevice, st));
     else
       HIP_TRY(c, hipMemsetAsync(d_sgns, 0, n, st));
   }
-  if (rl_is_sqrt(what)) HIP_TRY(c, hipMemcpyAsync(d_ok, root_ok, n, hipMemcpyHostToDevice, st));
+  if (root_is_sqrt(what)) HIP_TRY(c, hipMemcpyAsync(d_ok, root_ok, n, hipMemcpyHostToDevice, st));
   const unsigned blocks = (unsigned)((n + 63) / 64);
   const u64* dj = jobs ? d_jobs : nullptr;
   switch (what) {
-    case RL_G1_RECOVER: k_root_links<RL_G1_RECOVER><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
-    case RL_G2_RECOVER: k_root_links<RL_G2_RECOVER><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
-    case RL_FQ_SQRT: k_root_links<RL_FQ_SQRT><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
-    case RL_FQ2_SQRT: k_root_links<RL_FQ2_SQRT><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
-    default: k_root_links<RL_MAP_TO_G1><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
+    case ROOT_G1_RECOVER: k_root_links<ROOT_G1_RECOVER><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
+    case ROOT_G2_RECOVER: k_root_links<ROOT_G2_RECOVER><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
+    case ROOT_FQ_SQRT: k_root_links<ROOT_FQ_SQRT><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
+    case ROOT_FQ2_SQRT: k_root_links<ROOT_FQ2_SQRT><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
+    default: k_root_links<ROOT_MAP_TO_G1><<<blocks, 64, 0, st>>>(d_in, d_sgns, n, d_out, d_flags, d_ok, dj, d_bases, d_code, d_ctl); break;
   }
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(codes, d_code, n, hipMemcpyDeviceToHost, st));
@@ -239,13 +192,13 @@ int root_run(bn254s_ctx* c, int what, const uint64_t* in, const uint8_t* sgns, s
   return BN254S_OK;
 }
 
-const char* in_name(int what) { return what == RL_MAP_TO_G1 ? "u" : "x"; }
-const char* out_name(int what) { return rl_is_sqrt(what) ? "roots" : "points"; }
+const char* in_name(int what) { return what == ROOT_MAP_TO_G1 ? "u" : "x"; }
+const char* out_name(int what) { return root_is_sqrt(what) ? "roots" : "points"; }
 
 // The shape of a call, without the context: pointers, n, what
 bool links_shape_ok(int what, const uint64_t* in, size_t n, const uint64_t* out, const uint8_t* flags, const uint8_t* root_ok) {
-  if (what < 0 || what >= RL_KINDS || !in || !out || !flags || (rl_is_sqrt(what) && !root_ok)) return false;
-  return n > 0 && n < (what == RL_MAP_TO_G1 ? (size_t)1 << 31 : (size_t)UINT_MAX);  // the first bad index travels as a 32-bit word
+  if (what < 0 || what >= ROOT_KINDS || !in || !out || !flags || (root_is_sqrt(what) && !root_ok)) return false;
+  return n > 0 && n < (what == ROOT_MAP_TO_G1 ? (size_t)1 << 31 : (size_t)UINT_MAX);  // the first bad index travels as a 32-bit word
 }
 
 // Every coordinate that the device reads as a field element is below p: all of `in`, and the y / root of the rows whose root is
@@ -253,16 +206,16 @@ bool links_shape_ok(int what, const uint64_t* in, size_t n, const uint64_t* out,
 // compared.  The first that is not names itself like coords_below_p.
 bool links_coords_below_p(bn254s_ctx* c, const std::string& tag, int what, const uint64_t* in, size_t n, const uint64_t* out,
                           const uint8_t* flags, const uint8_t* root_ok) {
-  const size_t IW = rl_in_words(what), OW = rl_out_words(what), at = rl_root_at(what);
+  const size_t IW = root_in_words(what), OW = root_out_words(what), at = root_at(what);
   if (!coords_below_p(c, tag, in_name(what), COORD_FQ2, (int)IW / 4, in, n)) return false;
-  const uint8_t* claimed = what == RL_MAP_TO_G1 ? nullptr : rl_is_sqrt(what) ? root_ok : flags;
-  const char* const* coord = what == RL_G2_RECOVER ? COORD_G2 + 2 : what == RL_FQ2_SQRT ? COORD_FQ2 : COORD_G1 + 1;
-  const size_t ncoord = (what == RL_G2_RECOVER || what == RL_FQ2_SQRT) ? 2 : 1;
+  const uint8_t* claimed = what == ROOT_MAP_TO_G1 ? nullptr : root_is_sqrt(what) ? root_ok : flags;
+  const char* const* coord = what == ROOT_G2_RECOVER ? COORD_G2 + 2 : what == ROOT_FQ2_SQRT ? COORD_FQ2 : COORD_G1 + 1;
+  const size_t ncoord = (what == ROOT_G2_RECOVER || what == ROOT_FQ2_SQRT) ? 2 : 1;
   for (size_t i = 0; i < n; i++)
     for (size_t k = 0; (!claimed || claimed[i]) && k < ncoord; k++)
       if (!fq_below_p(out + OW * i + at + 4 * k)) {
         if (c)
-          c->set_err(tag + ": " + out_name(what) + "_" + std::to_string(i) + (what == RL_FQ_SQRT ? " is" : std::string(" has ") + coord[k]) +
+          c->set_err(tag + ": " + out_name(what) + "_" + std::to_string(i) + (what == ROOT_FQ_SQRT ? " is" : std::string(" has ") + coord[k]) +
                      " not below p");
         return false;
       }
@@ -279,18 +232,18 @@ void legendre_exp(u64 e[4]) {
 
 const char* base_name(int what, size_t job) {
   switch (what) {
-    case RL_G1_RECOVER: return "x^3 + 3";
-    case RL_G2_RECOVER: return "norm(x^3 + b')";
-    case RL_FQ_SQRT: return "x";
-    case RL_FQ2_SQRT: return "norm(x)";
+    case ROOT_G1_RECOVER: return "x^3 + 3";
+    case ROOT_G2_RECOVER: return "norm(x^3 + b')";
+    case ROOT_FQ_SQRT: return "x";
+    case ROOT_FQ2_SQRT: return "norm(x)";
     default: return job % 2 ? "g(x2)" : "g(x1)";
   }
 }
 const char* radicand_name(int what) {
   switch (what) {
-    case RL_G1_RECOVER: return "x^3 + 3";
-    case RL_G2_RECOVER: return "x^3 + b'";
-    case RL_MAP_TO_G1: return "g of the candidate that the flags select";
+    case ROOT_G1_RECOVER: return "x^3 + 3";
+    case ROOT_G2_RECOVER: return "x^3 + b'";
+    case ROOT_MAP_TO_G1: return "g of the candidate that the flags select";
     default: return "x";
   }
 }
@@ -299,15 +252,15 @@ const char* radicand_name(int what) {
 // again here, on the host: one input per call at the most)
 std::string link_text(unsigned code, int what, size_t i, const uint8_t* sgns, const uint8_t* flags, const uint8_t* root_ok,
                       const uint64_t* jobs, const uint64_t* bases) {
-  const std::string root = rl_is_sqrt(what) ? "the root" : "y of the point";
-  const size_t nj = rl_jobs(what);
+  const std::string root = root_is_sqrt(what) ? "the root" : "y of the point";
+  const size_t nj = root_jobs(what);
   u64 e[4];
   legendre_exp(e);
   switch (code) {
     case BN254S_ROOT_JOB_SCALAR:
       for (size_t j = nj * i; j < nj * (i + 1); j++)
         if (memcmp(jobs + 8 * j, e, 32) != 0)
-          return "the scalar of job " + std::to_string(j) + (what == RL_MAP_TO_G1 ? std::string(" (") + base_name(what, j) + ")" : "") +
+          return "the scalar of job " + std::to_string(j) + (what == ROOT_MAP_TO_G1 ? std::string(" (") + base_name(what, j) + ")" : "") +
                  " is not (p - 1)/2";
       break;
     case BN254S_ROOT_JOB_BASE:
@@ -317,22 +270,21 @@ std::string link_text(unsigned code, int what, size_t i, const uint8_t* sgns, co
     case BN254S_ROOT_FLAG: {
       for (size_t j = nj * i; j < nj * (i + 1); j++)
         if (flags[j] > 1)
-          return std::string(rl_is_sqrt(what) ? "square" : what == RL_MAP_TO_G1 ? (j % 2 ? "the flag of g(x2)" : "the flag of g(x1)") : "the flag") +
+          return std::string(root_is_sqrt(what) ? "square" : what == ROOT_MAP_TO_G1 ? (j % 2 ? "the flag of g(x2)" : "the flag of g(x1)") : "the flag") +
                  " is " + std::to_string(flags[j]) + ", neither 0 nor 1";
       const unsigned sgn = sgns ? sgns[i] : 0;
       if (sgn > 1) return "the sign is " + std::to_string(sgn) + ", neither 0 nor 1";
-      if (!rl_is_sqrt(what)) break;
+      if (!root_is_sqrt(what)) break;
       if (root_ok[i] > 1) return "root_ok is " + std::to_string(root_ok[i]) + ", neither 0 nor 1";
-      static const u64 ZERO[4] = {0, 0, 0, 0};
-      const bool zero = memcmp(bases + 4 * i, ZERO, 32) == 0;
+      const bool zero = words_are_zero(bases + 4 * i);
       if (flags[i] && zero) return "square is set on the base zero, whose Legendre symbol is 0";
       return std::string("root_ok is ") + (root_ok[i] ? "set" : "clear") + ", but a root with the sign " + std::to_string(sgn) +
              (root_ok[i] ? " does not exist" : " exists") + (zero ? " (the one root of zero has the sign 0)" : " by the flag square");
     }
     case BN254S_ROOT_CARRY:
-      return what == RL_MAP_TO_G1 ? "x of the point is not the candidate that the flags select" : "the point does not carry x";
+      return what == ROOT_MAP_TO_G1 ? "x of the point is not the candidate that the flags select" : "the point does not carry x";
     case BN254S_ROOT_NOT_ZERO:
-      return std::string(rl_is_sqrt(what) ? "root_ok" : "the flag") + " is clear and " + root + " is not zero words";
+      return std::string(root_is_sqrt(what) ? "root_ok" : "the flag") + " is clear and " + root + " is not zero words";
     case BN254S_ROOT_SQUARE: return root + " does not square to " + radicand_name(what);
     case BN254S_ROOT_SIGN: return root + " squares to " + radicand_name(what) + " but has the other sign";
   }
@@ -340,34 +292,29 @@ std::string link_text(unsigned code, int what, size_t i, const uint8_t* sgns, co
 }
 
 // The five verifiers: the argument ladder of bn254s_verify_scalar_mul, the kernel once, bn254s_verify_batch of the proofs against
-// jobs made here - (p-1)/2, the base from the device, and the output that the flag demands: 0 for a zero base (sqrt kinds only:
-// a set flag there is code 3, and the proof is judged for what the base is), else 1 where the flag is set and p - 1 where it is
-// clear - and both verdicts reported.
+// jobs made here - (p-1)/2, the base from the device, and the output that the flag demands (legendre_output of root_kinds.h; on a
+// zero base, sqrt kinds only, a set flag is code 3 and the proof is judged for what the base is, 0) - and both verdicts reported.
 int verify_roots(bn254s_ctx* c, int what, const std::string& tag, const bn254s_params* params, const uint64_t* const* words,
                  const size_t* n_words, const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* in,
                  const uint8_t* sgns, size_t n, const uint64_t* out, const uint8_t* flags, const uint8_t* root_ok, const uint64_t* fq_jobs,
                  uint8_t* link_out, int32_t* proof_status) {
   if (!links_shape_ok(what, in, n, out, flags, root_ok)) return BN254S_E_INVALID_ARG;
-  const size_t nj = rl_jobs(what) * n;
+  const size_t nj = root_jobs(what) * n;
   if (!verifier_args_ok(2, params, words, n_words, degree_bits, n_proofs, per_proof, nj) || params->struct_size != sizeof(bn254s_params))
     return BN254S_E_INVALID_ARG;
   if (!links_coords_below_p(c, tag, what, in, n, out, flags, root_ok) || !c) return BN254S_E_INVALID_ARG;
   std::vector<uint8_t> link(n);
   std::vector<int32_t> status(n_proofs);
-  std::vector<u64> bases(4 * nj), scalars(4 * nj), outputs(4 * nj, 0);
+  std::vector<u64> bases(4 * nj), scalars(4 * nj), outputs(4 * nj);
   unsigned first = UINT_MAX;
   int rc = root_run(c, what, in, sgns, n, out, flags, root_ok, fq_jobs, link.data(), bases.data(), &first);
   if (rc != BN254S_OK) return rc;
-  u64 e[4], pm1[4];
+  u64 e[4];
   legendre_exp(e);
-  memcpy(pm1, G1R_P, 32);
-  pm1[0] -= 1;
-  static const u64 ZERO[4] = {0, 0, 0, 0};
   for (size_t j = 0; j < nj; j++) {
+    const bool zero = root_is_sqrt(what) && words_are_zero(bases.data() + 4 * j);  // the flag does not count there
     memcpy(scalars.data() + 4 * j, e, 32);
-    if (rl_is_sqrt(what) && memcmp(bases.data() + 4 * j, ZERO, 32) == 0) continue;  // 0
-    if (flags[j]) outputs[4 * j] = 1;
-    else memcpy(outputs.data() + 4 * j, pm1, 32);
+    memcpy(outputs.data() + 4 * j, legendre_output(flags[j] && !zero, zero), 32);
   }
   std::string text;
   rc = verify_proof_runs(c, 2, params, words, n_words, degree_bits, n_proofs, per_proof, scalars.data(), bases.data(), nullptr,
@@ -391,7 +338,7 @@ extern "C" int bn254s_root_links_check_batch(bn254s_ctx* c, int what, const uint
   if (!code_out || !links_shape_ok(what, in, n, out, flags, root_ok)) return BN254S_E_INVALID_ARG;
   if (!links_coords_below_p(c, "root_links_check", what, in, n, out, flags, root_ok) || !c) return BN254S_E_INVALID_ARG;
   std::vector<uint8_t> codes(n);
-  std::vector<u64> bases(4 * rl_jobs(what) * n);
+  std::vector<u64> bases(4 * root_jobs(what) * n);
   unsigned first;
   const int rc = root_run(c, what, in, sgns, n, out, flags, root_ok, fq_jobs, codes.data(), bases.data(), &first);
   if (rc != BN254S_OK) return rc;
@@ -404,34 +351,34 @@ extern "C" int bn254s_verify_g1_recover(bn254s_ctx* c, const bn254s_params* para
                                         const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* xs, size_t n,
                                         const uint64_t* points, const uint8_t* flags, const uint64_t* fq_jobs, uint8_t* link_out,
                                         int32_t* proof_status) {
-  return verify_roots(c, RL_G1_RECOVER, "verify_g1_recover", params, words, n_words, degree_bits, n_proofs, per_proof, xs, nullptr, n,
+  return verify_roots(c, ROOT_G1_RECOVER, "verify_g1_recover", params, words, n_words, degree_bits, n_proofs, per_proof, xs, nullptr, n,
                       points, flags, nullptr, fq_jobs, link_out, proof_status);
 }
 extern "C" int bn254s_verify_g2_recover(bn254s_ctx* c, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
                                         const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* xs,
                                         const uint8_t* sgns, size_t n, const uint64_t* points, const uint8_t* flags,
                                         const uint64_t* fq_jobs, uint8_t* link_out, int32_t* proof_status) {
-  return verify_roots(c, RL_G2_RECOVER, "verify_g2_recover", params, words, n_words, degree_bits, n_proofs, per_proof, xs, sgns, n,
+  return verify_roots(c, ROOT_G2_RECOVER, "verify_g2_recover", params, words, n_words, degree_bits, n_proofs, per_proof, xs, sgns, n,
                       points, flags, nullptr, fq_jobs, link_out, proof_status);
 }
 extern "C" int bn254s_verify_fq_sqrt(bn254s_ctx* c, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
                                      const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* xs,
                                      const uint8_t* sgns, size_t n, const uint64_t* roots, const uint8_t* square, const uint8_t* root_ok,
                                      const uint64_t* fq_jobs, uint8_t* link_out, int32_t* proof_status) {
-  return verify_roots(c, RL_FQ_SQRT, "verify_fq_sqrt", params, words, n_words, degree_bits, n_proofs, per_proof, xs, sgns, n, roots,
+  return verify_roots(c, ROOT_FQ_SQRT, "verify_fq_sqrt", params, words, n_words, degree_bits, n_proofs, per_proof, xs, sgns, n, roots,
                       square, root_ok, fq_jobs, link_out, proof_status);
 }
 extern "C" int bn254s_verify_fq2_sqrt(bn254s_ctx* c, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
                                       const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* xs,
                                       const uint8_t* sgns, size_t n, const uint64_t* roots, const uint8_t* square, const uint8_t* root_ok,
                                       const uint64_t* fq_jobs, uint8_t* link_out, int32_t* proof_status) {
-  return verify_roots(c, RL_FQ2_SQRT, "verify_fq2_sqrt", params, words, n_words, degree_bits, n_proofs, per_proof, xs, sgns, n, roots,
+  return verify_roots(c, ROOT_FQ2_SQRT, "verify_fq2_sqrt", params, words, n_words, degree_bits, n_proofs, per_proof, xs, sgns, n, roots,
                       square, root_ok, fq_jobs, link_out, proof_status);
 }
 extern "C" int bn254s_verify_map_to_g1(bn254s_ctx* c, const bn254s_params* params, const uint64_t* const* words, const size_t* n_words,
                                        const uint32_t* degree_bits, size_t n_proofs, size_t per_proof, const uint64_t* u, size_t n,
                                        const uint64_t* points, const uint8_t* sq_flags, const uint64_t* fq_jobs, uint8_t* link_out,
                                        int32_t* proof_status) {
-  return verify_roots(c, RL_MAP_TO_G1, "verify_map_to_g1", params, words, n_words, degree_bits, n_proofs, per_proof, u, nullptr, n,
+  return verify_roots(c, ROOT_MAP_TO_G1, "verify_map_to_g1", params, words, n_words, degree_bits, n_proofs, per_proof, u, nullptr, n,
                       points, sq_flags, nullptr, fq_jobs, link_out, proof_status);
 }

@@ -1,4 +1,4 @@
-// a^((p+1)/4) in Fq for the point-recovery kernels (g1_recover.hip, g2_recover.hip): p = 3 (mod 4), so the result squares to
+// a^((p+1)/4) in Fq for the root kernels (root_front.hip, map_to_g1.hip, map_to_g2.hip): p = 3 (mod 4), so the result squares to
 // a where a is a square and to -a where it is none.  One lane per element, blocks of G1R_LANES lanes.
 #pragma once
 #include "fq_dev.h"
@@ -36,5 +36,14 @@ __device__ __forceinline__ fq sqrt_ladder(u32 (*tab)[FQ_NL][G1R_LANES], const fq
     const int d = G1R_SQRT_DIGITS[i];  // the same in every lane; 32-bit entries, so that it is a scalar load
     if (d) c = fq_mul(c, tab_load(tab, d - 1));
   }
+  return c;
+}
+// c = a^((p+1)/4) and what it squares to.  square: c^2 == a, a is a square and c its root (also for a = 0, like the comparison with
+// -a); bad: c^2 is neither a nor -a, the ladder is wrong.
+__device__ __forceinline__ fq fq_root(u32 (*tab)[FQ_NL][G1R_LANES], const fq& a, bool& square, bool& bad) {
+  const fq c = sqrt_ladder(tab, a);
+  const fq c2 = fq_sqr(c);
+  square = fq_eq(c2, a);
+  bad = !square && !fq_eq(c2, fq_neg(a));  // neither root nor non-residue
   return c;
 }

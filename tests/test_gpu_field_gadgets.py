@@ -1,4 +1,4 @@
-"""The field gadgets on the GPU (csrc/field_gadgets.hip; reference src/fields/: is_square, sqrt_with_sgn, inv): the device
+"""The field gadgets on the GPU (csrc/root_front.hip, csrc/field_gadgets.hip; reference src/fields/: is_square, sqrt_with_sgn, inv): the device
 front-ends against the big-integer definitions of tools/field_gadgets_ref.py word for word - random inputs at the block boundary,
 the crafted inputs that a curve equation never produces (zero, c1 = 0, roots with c0 = 0, both branches on delta) -, against the
 fused recovery kernels, the proven forms with their three-valued Legendre linkage, and the error contract."""

@@ -1,5 +1,5 @@
 """G1 point recovery from x on the GPU (reference src/curves/g1.rs:76-95, src/fields/recover.rs): the device front-end
-(csrc/g1_recover.hip) against the Python reference (tools/synth.py g1_recover_from_x) word for word, the rejection of x >= p, the
+(csrc/root_front.hip) against the Python reference (tools/synth.py g1_recover_from_x) word for word, the rejection of x >= p, the
 proven Legendre symbols checked with verify_g1_recover, and the recovered points as the inputs of g1_msm."""
 import numpy as np
 import pytest

@@ -1,5 +1,5 @@
 """G2 point recovery from x on the GPU (reference src/curves/g2.rs:42-54, src/fields/fq2.rs:209-241): the device front-end
-(csrc/g2_recover.hip) against the Python reference (tools/synth.py g2_recover_from_x, ark's complex method: another algorithm than
+(csrc/root_front.hip) against the Python reference (tools/synth.py g2_recover_from_x, ark's complex method: another algorithm than
 the kernel's) word for word, the rejection of unreduced coordinates and of sign bytes above 1, the proven Legendre symbols checked
 with verify_g2_recover, and the recovered points as the inputs of g2_msm."""
 import ctypes as C

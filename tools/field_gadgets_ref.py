@@ -1,5 +1,5 @@
 """Big-integer definitions of the field gadgets (reference src/fields/: FqTarget / Fq2Target is_square, sqrt_with_sgn, inv; sign
-rule sgn.rs), written independently of the device algorithm of csrc/field_gadgets.hip: the Fq root is pow(x, (p+1)/4), the Fq2
+rule sgn.rs), written independently of the device algorithm of csrc/root_front.hip and csrc/field_gadgets.hip: the Fq root is pow(x, (p+1)/4), the Fq2
 root the "complex method" for p = 3 mod 4 in Fq2 arithmetic (Adj, Rodriguez-Henriquez, "Square root computation over even
 extension fields", algorithm 9), with no norm ladder and no delta.  The root with a given sign is unique (y and -y have opposite
 signs for y != 0), so any correct root normalised by sign is the expectation.
